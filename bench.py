@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Headline benchmark: light-client proof wall-time / proofs per hour on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, verifies the last proof, writes that proof if --dump-outputs is given and prints
+the line.  Everything else it can measure (the side fields, the CPU baseline, the N > 1 batch and sharded proof) runs only with --full.
 
 A step = one `data.prove(pw)` of eth-lc-plonky2/src/main.rs:229-232 - the region the reference times, witness generation
 (`generate_partial_witness`) INSIDE it - on a circuit built from the reference's own gadgets by the C++ host layer
@@ -14,7 +17,12 @@ is a host object (a few thousand values); the SHA-256 rows are generated on the 
 inputs compared with the natively computed contract states.  `data`: the two real mainnet updates of the reference repository
 (tests/golden/lc_updates.json), nothing synthetic.
 
-Side fields (`config.*`, N = 1 only, each with the HIP-event time per kernel family and a roofline block of its own):
+--dump-outputs DIR: after the timed steps, the last step's proof and public inputs (what data.prove(pw) hands its caller) go to
+DIR/proof.npy and DIR/public_inputs.npy.  The words are u64 field elements, which float64 cannot hold: each array is float64 of shape
+(words, 2), column 0 the low 32 bits of a word and column 1 the high 32 bits, both exact.  The inputs are fixed, so two builds that
+compute the same proof write the same files.
+
+Side fields (`config.*`, with --full, N = 1 only, each with the HIP-event time per kernel family and a roofline block of its own):
   real_lc_step / sync_committee_ssz / real_lc_step_recursive   the step at its true size (2^19 rows), BASELINE configs[1] (the
       SyncCommitteeSSZ gadget alone), and the step with the recursive verification of a stand-in inner proof;
   synthetic_plonky2_gate_set_2p22     the headline of rounds 1-3: a synthetic satisfiable circuit over plonky2's own gate set
@@ -31,15 +39,15 @@ rank's exit code on.  With WORLD_SIZE set (torch.distributed.run) the process is
 
 N > 1: one rank per GPU, every rank proves the same circuit for its own update (BASELINE configs[4], independent light-client
 updates: "replicas", no data-path collective) -> weak scaling; the only collectives are the timing barrier and the max-reduce of the
-elapsed time.  After that timed region the ranks (a) prove a batch of 32 updates data-parallel through batch.prove_batch (configs[4]
+elapsed time.  With --full, after that timed region the ranks (a) prove a batch of 32 updates data-parallel through batch.prove_batch (configs[4]
 as worded: 32 / N per rank, proofs gathered on rank 0) and (b) prove ONE proof together, sharded by LDE coset (BASELINE configs[3];
 eth-lc-plonky2_amd/parallel.py::ShardedProver over RCCL) - reported as `config.batch_of_32` and `config.sharded_proof`; `value` stays
 the replica throughput; a failure or a hang of one of these side measurements is reported inside the line (`.error`) and the exit code stays 0
 unless --strict-sharded is given.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (Poseidon leaf hashing, K4a, integer-VALU bound):
-algorithmic bytes per launch / HIP-event time per launch measured inside this run.  `cpu_baseline` is the oracle (oracle/, kind
-"port") timed on a bounded sample; the GPU proves the same sample and the two proofs must be equal word for word.
+algorithmic bytes per launch / HIP-event time per launch measured inside this run.  `cpu_baseline` (--full) is the oracle (oracle/,
+kind "port") timed on a bounded sample; the GPU proves the same sample and the two proofs must be equal word for word.
 """
 import argparse
 import json
@@ -129,7 +137,7 @@ def prof_delta(p1, p0):
 def light_client_workload(m, ctx, sync, flags=0, extra_committees=0, steps=3, warmup=1):
     """`steps` timed data.prove(pw) of the light-client circuit for updates 633 -> 634 (+ extra SyncCommitteeSSZ gadgets); the last
     proof is verified and its public inputs compared with the natively computed ones.  sync(): barrier + device synchronisation.
-    Returns (seconds for `steps` proofs, per-family profile delta, info, description)."""
+    Returns (seconds for `steps` proofs, per-family profile delta, info, description, (last proof, its public inputs))."""
     import numpy as np
     prev, cur = m.light_client.reference_updates()
     step = m.light_client.LightClientStep(ctx, prev, cur, flags=flags, extra_committees=extra_committees)
@@ -156,14 +164,30 @@ def light_client_workload(m, ctx, sync, flags=0, extra_committees=0, steps=3, wa
     if extra_committees:
         what += " + %d more SyncCommitteeSSZ gadgets" % extra_committees
     what += ": %d gates, 2^%d rows; data.prove(pw) with witness generation inside (SHA-256 rows generated on the device), proof verified" % (info.num_gates, info.degree_bits)
-    out = (dt, prof, {"degree_bits": info.degree_bits, "gates": int(info.num_gates), "build_ms": round(info.build_ms, 1), "attach_ms": round(info.attach_ms, 1)}, what)
+    out = (dt, prof, {"degree_bits": info.degree_bits, "gates": int(info.num_gates), "build_ms": round(info.build_ms, 1), "attach_ms": round(info.attach_ms, 1)}, what,
+           (proof, pis))
     step.close()
     return out
 
 
+def u64_as_float64(words):
+    """u64 words as float64 of shape (n, 2): low and high 32 bits, each exact in a double"""
+    import numpy as np
+    w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    return np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each u64 array of `arrays` ({name: words}) as path/<name>.npy, in the form of u64_as_float64"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, words in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), u64_as_float64(words))
+
+
 def side_light_client(m, ctx, sync, **kw):
     try:
-        dt, prof, info, what = light_client_workload(m, ctx, sync, steps=3, warmup=1, **kw)
+        dt, prof, info, what, _ = light_client_workload(m, ctx, sync, steps=3, warmup=1, **kw)
         return {"workload": what, "degree_bits": info["degree_bits"], "gates": info["gates"], "ms_per_proof": dt / 3 * 1e3,
                 "kernel_ms_per_proof": {k: round(v["ms"] / 3, 3) for k, v in prof.items() if v["launches"]},
                 "roofline": leaf_hash_roofline(prof["leaf_hash"], leaf_perms(info["degree_bits"], 3)), "host_build_ms": info["build_ms"], "device_build_ms": info["attach_ms"]}
@@ -309,15 +333,19 @@ def guarded(work, limit_s, on_timeout, exit_fn=os._exit, exit_code=3):
             timer.join()  # the timeout won: its thread reports and exits the process (with a test's exit_fn it returns, and so do we)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (proofs); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's proof and public inputs to DIR/proof.npy and "
+                    "DIR/public_inputs.npy (float64, shape (words, 2): low and high 32 bits of each u64 word)")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement: the side fields of config (N = 1), the CPU baseline, "
+                    "and for N > 1 the 32-update batch and the sharded proof; the --no-* options below leave parts of it out")
     ap.add_argument("--extra-committees", type=int, default=6, help="SyncCommitteeSSZ gadgets added to the light-client step of the headline: 6 -> 2.24 M gates, 2^22 rows")
     ap.add_argument("--degree-bits", type=int, default=22, help="log2 rows of the synthetic side workloads (and of the sharded proof for N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--force-sharded", action="store_true", help="also run the sharded-proof side measurement with one rank "
+    ap.add_argument("--force-sharded", action="store_true", help="with --full: also run the sharded-proof side measurement with one rank "
                     "(RCCL process group of size 1: exercises the N > 1 code path on a one-GPU box)")
     ap.add_argument("--cpu-sample-bits", type=int, default=18, help="log2 rows of the oracle's bounded sample")
     ap.add_argument("--no-real-gadgets", action="store_true", help="skip the light-client side workloads (2^19-row step, configs[1], recursive step)")
@@ -328,7 +356,14 @@ def parse():
     ap.add_argument("--no-batch", action="store_true", help="N > 1: skip the 32-update batch (configs[4] as worded)")
     ap.add_argument("--launch-dry-run", action="store_true", help="start the rank processes, let each report the environment it was "
                     "given and exit before anything touches torch or the GPU (CPU test of the launcher)")
-    return ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if a.force_sharded and not a.full:
+        ap.error("--force-sharded is a side measurement: give --full as well")
+    return a
 
 
 def _free_port():
@@ -518,7 +553,9 @@ def main():
         torch.cuda.synchronize()
 
     # ---- the headline: data.prove(pw) of the 2^22-row circuit of real gadgets, witness generation inside the timed region
-    dt, prof, info, what = light_client_workload(m, ctx, barrier, flags=0, extra_committees=a.extra_committees, steps=a.steps, warmup=a.warmup)
+    dt, prof, info, what, (proof, pis) = light_client_workload(m, ctx, barrier, flags=0, extra_committees=a.extra_committees, steps=a.steps, warmup=a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"proof": proof, "public_inputs": pis})
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -556,7 +593,7 @@ def main():
             out["config"]["sharded_proof"] = sharded
         if batch:
             out["config"]["batch_of_32"] = batch
-        if world == 1 and not from_watchdog:
+        if a.full and world == 1 and not from_watchdog:
             sync = barrier
             if not a.no_real_gadgets:
                 out["config"]["real_lc_step"] = side_light_client(m, ctx, sync)
@@ -576,7 +613,7 @@ def main():
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
     sharded, batch, rc = None, None, 0
-    multi = (world > 1 or a.force_sharded)
+    multi = a.full and (world > 1 or a.force_sharded)  # the N > 1 side measurements
     if multi and not a.no_batch:
         # BASELINE configs[4] as worded: a batch of 32 consecutive light-client updates data-parallel over the GPUs (32 / N per rank,
         # no data-path collective, the finished proofs gathered on rank 0).  The reference ships ONE consecutive pair, so every update

@@ -91,3 +91,34 @@ def test_watchdog_does_nothing_when_the_work_finishes_first():
         pass
     time.sleep(0.4)
     assert events == []
+
+
+def test_plain_run_options():
+    """a plain run is the headline alone: --full (the side measurements) is off by default, --steps sets the timed steps,
+    and --force-sharded, a side measurement, needs --full"""
+    sys.path.insert(0, ROOT)
+    import pytest
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    a = bench.parse(["--steps", "2", "--full", "--force-sharded", "--dump-outputs", "d"])
+    assert a.full is True and a.force_sharded is True and a.dump_outputs == "d"
+    for bad in (["--force-sharded"], ["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_holds_every_u64_word_exactly(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    p = 0xFFFFFFFF00000001  # the Goldilocks prime: proof words are below it
+    proof = np.array([0, 1, p - 1, 2**53 + 1, 0x123456789ABCDEF0], dtype=np.uint64)
+    pis = np.arange(16, dtype=np.uint64) * np.uint64(0x1000000001)
+    bench.dump_outputs(str(tmp_path / "out"), {"proof": proof, "public_inputs": pis})
+    for name, want in (("proof", proof), ("public_inputs", pis)):
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == (want.size, 2)
+        assert (got >= 0).all() and (got < 2.0**32).all() and (got == np.floor(got)).all()
+        words = (got[:, 1].astype(np.uint64) << np.uint64(32)) | got[:, 0].astype(np.uint64)
+        assert (words == want).all()
