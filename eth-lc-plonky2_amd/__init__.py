@@ -5,7 +5,7 @@ eth-lc-plonky2/src/main.rs:226-233) over the C ABI in include/lcp2.h.  The
 directory name follows the project ("eth-lc-plonky2_amd"); import it as
 `eth_lc_plonky2_amd` (shim module at the repository root).
 """
-from .binding import (CircuitData, ProofRejected, Context, Lcp2Error, Oracle, Params, load_library, standard_params,  # noqa: F401
+from .binding import (CircuitData, ProofRejected, Context, Lcp2Error, Oracle, Params, load_library, standard_params, params_config,  # noqa: F401
                       MEM_DEVICE, MEM_HOST, KERNEL_FAMILIES, GOLDILOCKS_P, proof_to_bytes, proof_from_bytes, proof_layout)
 from .build import build_native, build_host  # noqa: F401
 from . import binding  # noqa: F401,E402

@@ -99,6 +99,7 @@ def load_library():
         "lcp2_abi_version": (c.c_int, []),
         "lcp2_device_count": (c.c_int, []),
         "lcp2_params_standard": (c.c_int, [c.c_uint32, c.c_uint32, c.POINTER(Params)]),
+        "lcp2_params_config": (c.c_int, [c.c_uint32] * 8 + [c.POINTER(Params)]),
         "lcp2_ctx_create": (c.c_int, [c.c_int, c.c_void_p, c.POINTER(c.c_void_p)]),
         "lcp2_ctx_create_ex": (c.c_int, [c.c_int, c.c_void_p, c.c_uint32, c.POINTER(c.c_void_p)]),
         "lcp2_ctx_destroy": (None, [c.c_void_p]),
@@ -197,6 +198,18 @@ def standard_params(degree_bits, num_constants=4):
     lib = load_library()
     p = Params()
     rc = lib.lcp2_params_standard(degree_bits, num_constants, ctypes.byref(p))
+    if rc:
+        raise Lcp2Error(rc, lib.lcp2_status_str(rc).decode())
+    return p
+
+
+def params_config(degree_bits, num_constants=4, rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28,
+                  arity_bits=4, final_poly_bits=5):
+    """lcp2_params_config: the standard wire shape under a FriConfig with ConstantArityBits(arity_bits, final_poly_bits)"""
+    lib = load_library()
+    p = Params()
+    rc = lib.lcp2_params_config(degree_bits, num_constants, rate_bits, cap_height, proof_of_work_bits, num_query_rounds,
+                                arity_bits, final_poly_bits, ctypes.byref(p))
     if rc:
         raise Lcp2Error(rc, lib.lcp2_status_str(rc).decode())
     return p

@@ -1017,4 +1017,17 @@ void launch_fill(hipStream_t s, u64 *p, u64 n, u64 v) {
   hipLaunchKernelGGL(k_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, n, v);
 }
 
+// the trim check of a quotient with Q < 2^q chunks: row blockIdx.y, a grid-stride walk over its `width` words
+__global__ __launch_bounds__(256) void k_any_nonzero(const u64 *p, u64 pitch, u64 width, unsigned long long *flag) {
+  const u64 *row = p + (u64)blockIdx.y * pitch;
+  bool any = false;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < width; i += (u64)gridDim.x * blockDim.x) any = any || gl_canon(row[i]) != 0;
+  if (any) *flag = 1;  // every writer writes the same word
+}
+void launch_any_nonzero(hipStream_t s, const u64 *p, u64 pitch, u64 width, u32 rows, unsigned long long *flag) {
+  if (!width || !rows) return;
+  const u64 want = (width + 255) / 256;
+  hipLaunchKernelGGL(k_any_nonzero, dim3((unsigned)(want < 1024 ? want : 1024), rows), dim3(256), 0, s, p, pitch, width, flag);
+}
+
 }  // namespace lcp2

@@ -29,18 +29,28 @@ extern "C" int lcp2_device_count(void) {
   return n;
 }
 
-extern "C" int lcp2_params_standard(uint32_t degree_bits, uint32_t num_constants, lcp2_params *p) {
-  if (!p || degree_bits == 0 || degree_bits > 28) return LCP2_E_INVALID;
+extern "C" int lcp2_params_config(uint32_t degree_bits, uint32_t num_constants, uint32_t rate_bits, uint32_t cap_height,
+                                  uint32_t proof_of_work_bits, uint32_t num_query_rounds, uint32_t arity_bits, uint32_t final_poly_bits,
+                                  lcp2_params *p) {
+  if (!p || degree_bits == 0 || degree_bits > 28 || rate_bits == 0 || rate_bits > 8 || arity_bits == 0 || arity_bits > 5) return LCP2_E_INVALID;
   memset(p, 0, sizeof *p);
   p->degree_bits = degree_bits;
   p->num_wires = 135; p->num_routed_wires = 80; p->num_constants = num_constants;
-  p->rate_bits = 3; p->cap_height = 4; p->num_challenges = 2; p->quotient_degree_factor = 8;
-  p->proof_of_work_bits = 16; p->num_query_rounds = 28;
-  // FriReductionStrategy::ConstantArityBits(4, 5)
+  p->rate_bits = rate_bits; p->cap_height = cap_height; p->num_challenges = 2; p->quotient_degree_factor = 8;
+  p->proof_of_work_bits = proof_of_work_bits; p->num_query_rounds = num_query_rounds;
+  // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits) (fri/reduction_strategies.rs)
   uint32_t d = degree_bits, n = 0;
-  while (d > 5 && d + p->rate_bits - 4 >= p->cap_height && n < LCP2_MAX_FRI_LAYERS) { p->fri_arity_bits[n++] = 4; d -= 4; }
+  while (d > final_poly_bits && d + rate_bits >= cap_height + arity_bits) {
+    if (d < arity_bits) return LCP2_E_INVALID;  // plonky2 asserts degree_bits >= arity_bits here
+    if (n == LCP2_MAX_FRI_LAYERS) return LCP2_E_UNSUPPORTED;
+    p->fri_arity_bits[n++] = arity_bits;
+    d -= arity_bits;
+  }
   p->num_fri_layers = n;
   return LCP2_OK;
+}
+extern "C" int lcp2_params_standard(uint32_t degree_bits, uint32_t num_constants, lcp2_params *p) {
+  return lcp2_params_config(degree_bits, num_constants, 3, 4, 16, 28, 4, 5, p);
 }
 
 // ------------------------------------------------------------------ context

@@ -77,6 +77,8 @@ struct lcp2_circuit {
   ~lcp2_circuit() { for (hipEvent_t e : wit_ready) if (e) (void)hipEventDestroy(e); }
   bool check_pending = false;  // the gate-check verdict of stage_quotient_values has not been read yet (it arrives with the quotient cap)
   uint32_t world() const { return bc ? (1u << p.rate_bits) / bc : 1; }
+  // q = ceil(log2 Q): K6 evaluates the quotient on the 2^q n-point coset 7 H_{2^q n}, the first 2^q n leaves of every LDE
+  uint32_t qbits() const { uint32_t q = 0; while ((1u << q) < p.quotient_degree_factor) q++; return q; }
   uint32_t rank() const { return bc ? bf / bc : 0; }
   u64 rows() const { return rows_mode ? (1ull << p.degree_bits) / world() : (1ull << p.degree_bits); }
   u64 row0() const { return rows_mode ? rows() * rank() : 0; }
@@ -92,7 +94,7 @@ const char *params_problem(const lcp2_params &p, bool *unsupported) {
   if (p.num_routed_wires > p.num_wires || p.num_routed_wires == 0) return "bad routed wire count";
   if (p.cap_height > p.degree_bits + p.rate_bits) return "cap_height exceeds the LDE tree";
   *unsupported = true;
-  if (p.quotient_degree_factor != (1u << p.rate_bits)) return "quotient_degree_factor must equal 2^rate_bits";
+  if (p.quotient_degree_factor < 2 || p.quotient_degree_factor > (1u << p.rate_bits)) return "quotient_degree_factor must lie in [2, 2^rate_bits]";
   if (p.num_challenges < 1 || p.num_challenges > QUOTIENT_MAX_CH) return "num_challenges must be 1 or 2";
   if ((p.num_routed_wires + p.quotient_degree_factor - 1) / p.quotient_degree_factor > PERM_MAX_CHUNKS) return "too many routed wires";
   if (p.num_query_rounds > 64 || p.num_fri_layers > LCP2_MAX_FRI_LAYERS) return "too many queries / layers";
@@ -327,6 +329,7 @@ static int circuit_create(lcp2_ctx *ctx, const lcp2_circuit_desc *d, uint32_t bf
   std::unique_ptr<lcp2_circuit> c(new lcp2_circuit());
   c->ctx = ctx; c->p = p; c->npi = d->num_public_inputs; c->num_selectors = d->num_selectors; c->num_regs = std::max(d->num_regs, 1u);
   if (bc) {
+    if (p.quotient_degree_factor != (1u << p.rate_bits)) return ctx->fail(LCP2_E_UNSUPPORTED, "sharded circuit: needs quotient_degree_factor = 2^rate_bits");
     if (p.cap_height < p.rate_bits) return ctx->fail(LCP2_E_INVALID, "sharded circuit: needs cap_height >= rate_bits");
     if ((bc & (bc - 1)) || bf % bc || bf + bc > (1u << p.rate_bits)) return ctx->fail(LCP2_E_INVALID, "sharded circuit: block range must be an aligned power of two");
     c->bf = bf; c->bc = bc; c->cap_final = false;
@@ -390,11 +393,13 @@ static int circuit_create(lcp2_ctx *ctx, const lcp2_circuit_desc *d, uint32_t bf
     if (be.status) return be.status;
     LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
-  {  // 1 / Z_H(7 w_N^j) depends on j mod 2^rate_bits = bitrev of the top rate_bits of the leaf index
-    std::vector<u64> t(1u << p.rate_bits);
-    u64 shift_n = gl_pow(GL_GENERATOR, n), wr = gl_root_of_unity(p.rate_bits);
-    for (u32 top = 0; top < (1u << p.rate_bits); top++) {
-      u32 r = bitrev32(top, p.rate_bits);
+  const u32 qb = c->qbits();
+  const u64 NQ = n << qb;  // the quotient's domain (= N when Q = 2^rate_bits)
+  {  // 1 / Z_H(7 w_NQ^j) depends on j mod 2^q = bitrev of the top q bits of the leaf index
+    std::vector<u64> t(1u << qb);
+    u64 shift_n = gl_pow(GL_GENERATOR, n), wr = gl_root_of_unity(qb);
+    for (u32 top = 0; top < (1u << qb); top++) {
+      u32 r = bitrev32(top, qb);
       t[top] = gl_inv(gl_sub(gl_mul(shift_n, gl_pow(wr, r)), 1));
     }
     LCP2_TRY(upload(ctx, c->d_zh_inv, t.data(), t.size() * 8));
@@ -404,7 +409,7 @@ static int circuit_create(lcp2_ctx *ctx, const lcp2_circuit_desc *d, uint32_t bf
   LCP2_HIP(ctx, c->chunk_q.alloc((size_t)CH * nchunks * n * 8));
   LCP2_HIP(ctx, c->row_tot.alloc((size_t)CH * n * 8));
   LCP2_HIP(ctx, c->scan_tmp.alloc(std::max(scan_scratch_words(n, 4), (u64)16) * 8));
-  LCP2_HIP(ctx, c->qvals.alloc((size_t)CH * N * 8));
+  LCP2_HIP(ctx, c->qvals.alloc((size_t)CH * NQ * 8));
   LCP2_HIP(ctx, c->planes.alloc((size_t)4 * n * 8));
   LCP2_HIP(ctx, c->small.alloc((SMALL_GATE_SCALE + (size_t)QUOTIENT_MAX_CH * d->num_gates + 8) * 8));
   {
@@ -743,12 +748,16 @@ int stage_quotient_values(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash
     qs.limbs = (u32 *)c->alpha_limbs.p;
     launch_quotient_setup(s, qs);
   }
-  // ---- K6: quotient values on the coset, coset iNTT, chunking, commitment
+  // ---- K6: quotient values on the coset, coset iNTT, chunking, commitment.  The quotient lives on the 2^q n-point coset
+  // 7 H_{2^q n}, q = ceil(log2 Q) <= rate_bits: a natural index j 2^(rate_bits - q) of the LDE is the leaf bitrev_{d+q}(j) < 2^q n,
+  // so the first 2^q n leaves of every LDE are that coset in its own leaf order, and K6 reads them in place (column stride N)
+  const u32 qb = c->qbits(), lgNQ = p.degree_bits + qb;
+  const u64 NQ = n << qb;
   {
     QuotientArgs a{};
     a.wires = c->wires.lde.u(); a.consts = c->cs.lde.u(); a.zs = c->zs.lde.u(); a.l0 = c->d_l0.u(); a.zh_inv = c->d_zh_inv.u();
     u64 ls, hs;
-    a.points = ntt.shift_table(gl_root_of_unity(lgN), lgN, 0, false, GL_GENERATOR, ls, hs);
+    a.points = ntt.shift_table(gl_root_of_unity(lgNQ), lgNQ, 0, false, GL_GENERATOR, ls, hs);
     a.k_is = c->d_kis.u(); a.betas = d_betas; a.gammas = d_gammas; a.alphas = d_alphas; a.pis = d_small + SMALL_PI_HASH; a.imm = c->d_imm.u();
     a.kis_pow7 = 1;
     for (u32 j = 0; j < NR; j++) a.kis_pow7 &= c->k_is[j] == (j ? gl_mul(c->k_is[j - 1], 7) : 1);  // plonky2's coset shifts
@@ -756,12 +765,12 @@ int stage_quotient_values(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash
     a.alpha_limbs = (const u32 *)c->alpha_limbs.p;
     a.code = (const u32 *)c->d_code.p; a.gates = (const GateDev *)c->d_gates.p; a.out = c->qvals.u();
     a.stage_list = (const u32 *)c->d_stage.p; a.num_wires = W; a.use_native = 1; a.rc = ctx->d_rc;
-    a.N = N; a.lgN = lgN; a.rate_bits = p.rate_bits; a.num_gates = NG; a.num_selectors = c->num_selectors;
+    a.N = NQ; a.lgN = lgNQ; a.rate_bits = qb; a.num_gates = NG; a.num_selectors = c->num_selectors;
     a.num_constants = NC; a.num_routed = NR; a.chunk = Q; a.nchunks = nchunks; a.num_challenges = CH; a.num_regs = c->dev_regs;
-    a.leaf0 = (u64)c->bf * n; a.count = (u64)c->nblocks() * n; a.stride = a.count;
+    a.leaf0 = (u64)c->bf * n; a.count = c->sharded() ? (u64)c->nblocks() * n : NQ; a.stride = c->sharded() ? a.count : N;
     if (be.status) return be.status;
     // a sharded circuit fills its own leaf blocks and leaves zeros elsewhere: the ranks' buffers sum (or OR) to the values
-    if (c->sharded()) LCP2_HIP(ctx, hipMemsetAsync(c->qvals.p, 0, (size_t)CH * N * 8, s));
+    if (c->sharded()) LCP2_HIP(ctx, hipMemsetAsync(c->qvals.p, 0, (size_t)CH * NQ * 8, s));
     ProfScope ps(ctx, LCP2_K_QUOTIENT, (double)a.count * 8.0 * (W + ncs + CH * (1.0 + npp) + 2.0 + CH) + 8.0 * n * (W + NC));
     // the gate constraints on the n rows of H first (1/8 of the work below): a witness that violates one is the Err of prove()
     QuotientArgs h = a;
@@ -792,7 +801,10 @@ int stage_quotient_values(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash
 int stage_quotient_commit(lcp2_circuit *c, u64 *cap_out) {
   LCP2_STAGE_PROLOGUE
   if (c->stage != lcp2_circuit::ST_QVALS) return ctx->fail(LCP2_E_INVALID, "lcp2_quotient_commit: no quotient values");
-  LCP2_HIP(ctx, c->quot.coeffs.ensure((size_t)CH * N * 8));
+  const u32 qb = c->qbits();
+  const u64 NQ = n << qb;
+  const bool trim = Q != (1u << qb);  // Q chunks of the 2^q chunks: the coefficients from Q n to 2^q n must vanish
+  LCP2_HIP(ctx, c->quot.coeffs.ensure((size_t)CH * NQ * 8));
   if (c->local_quotient()) {
     const u32 R = 1u << p.rate_bits;
     if (!c->q_combine.p) {
@@ -808,18 +820,26 @@ int stage_quotient_commit(lcp2_circuit *c, u64 *cap_out) {
     ProfScope ps(ctx, LCP2_K_INTT, 16.0 * N * CH);
     launch_quotient_combine(s, c->qvals.u(), c->quot.coeffs.u(), c->q_combine.u(), n, R, N, CH);
     LCP2_HIP(ctx, hipGetLastError());
-  } else {
-    ProfScope ps(ctx, LCP2_K_INTT, 16.0 * N * CH);
-    ntt.inverse_bitrev_in(c->qvals.u(), N, c->quot.coeffs.u(), N, lgN, CH, GL_GENERATOR);
+  } else if (!trim) {
+    ProfScope ps(ctx, LCP2_K_INTT, 16.0 * NQ * CH);
+    ntt.inverse_bitrev_in(c->qvals.u(), NQ, c->quot.coeffs.u(), NQ, p.degree_bits + qb, CH, GL_GENERATOR);
+  } else {  // plonky2's trim_to_len(quotient_degree): the check's verdict arrives with the cap, the first Q n coefficients move up
+    ProfScope ps(ctx, LCP2_K_INTT, 16.0 * NQ * CH);
+    ntt.inverse_bitrev_in(c->qvals.u(), NQ, c->qvals.u(), NQ, p.degree_bits + qb, CH, GL_GENERATOR);
+    launch_set_words(s, c->small.u() + SMALL_TRIM, SmallWords{}, 1);
+    launch_any_nonzero(s, c->qvals.u() + (u64)Q * n, NQ, NQ - (u64)Q * n, CH, (unsigned long long *)(c->small.u() + SMALL_TRIM));
+    launch_copy_2d(s, c->quot.coeffs.u(), (u64)Q * n, c->qvals.u(), NQ, (u64)Q * n, CH);
+    LCP2_HIP(ctx, hipGetLastError());
   }
   if (be.status) return be.status;
-  // N = Q n: the 8n coefficients of challenge c are exactly its Q chunks of n coefficients, already contiguous
+  // the Q n coefficients of challenge c are exactly its Q chunks of n coefficients, contiguous
   LCP2_TRY(commit_coeffs_dev(ctx, c->quot.coeffs.u(), CH * Q, p.degree_bits, p.rate_bits, p.cap_height, &c->quot, false));
-  u64 bad_row = ~0ull;
+  u64 bad_row = ~0ull, high = 0;
   {
     Download d(ctx);
     LCP2_TRY(queue_cap(d, c, c->quot, cap_out));
     if (c->check_pending) LCP2_TRY(d.add(&bad_row, c->small.u() + SMALL_CHECK, 8));
+    if (trim) LCP2_TRY(d.add(&high, c->small.u() + SMALL_TRIM, 8));
     LCP2_TRY(d.wait());
   }
   if (c->check_pending && bad_row != ~0ull) {  // plonky2 would have produced an invalid proof here; this is the Err of prove()
@@ -828,6 +848,10 @@ int stage_quotient_commit(lcp2_circuit *c, u64 *cap_out) {
     return ctx->fail(LCP2_E_UNSAT, "the witness violates a gate constraint on row " + std::to_string(bad_row - 1 + c->row0()));
   }
   c->check_pending = false;
+  if (high) {  // plonky2 panics in trim_to_len here: a gate's filtered constraints have a degree above Q + 1
+    c->stage = lcp2_circuit::ST_ZS;
+    return ctx->fail(LCP2_E_INVALID, "the constraint degree exceeds quotient_degree_factor + 1 (the quotient has more than quotient_degree_factor chunks)");
+  }
   c->stage = lcp2_circuit::ST_QUOT;
   return LCP2_OK;
 }
@@ -1369,7 +1393,7 @@ extern "C" int lcp2_quotient_buffer(lcp2_circuit *c, uint64_t **device_ptr, size
   if (!c || !device_ptr || !words) return LCP2_E_INVALID;
   if (!c->ctx) return LCP2_E_NODEVICE;
   *device_ptr = (uint64_t *)c->qvals.p;
-  *words = ((size_t)c->p.num_challenges << (c->p.degree_bits + c->p.rate_bits));
+  *words = ((size_t)c->p.num_challenges << (c->p.degree_bits + c->qbits()));
   return LCP2_OK;
 }
 extern "C" int lcp2_quotient_commit(lcp2_circuit *c, uint64_t *cap) {

@@ -24,7 +24,7 @@ constexpr u32 EVAL_CHUNK = 4096;
 
 // word offsets inside lcp2_circuit::small (per-proof scalars on the device)
 constexpr size_t SMALL_BETAS = 0, SMALL_GAMMAS = 4, SMALL_ALPHAS = 8, SMALL_ALPHA_INV = 12, SMALL_PI_HASH = 16, SMALL_POW = 20,
-                 SMALL_CHECK = 21, SMALL_NONCANON = 22, SMALL_PERM_PREFIX = 24, SMALL_ALPHA_POW = 32, SMALL_GATE_SCALE = SMALL_ALPHA_POW + QUOTIENT_MAX_CH * QUOTIENT_ALPHA_POWS;
+                 SMALL_CHECK = 21, SMALL_NONCANON = 22, SMALL_TRIM = 23, SMALL_PERM_PREFIX = 24, SMALL_ALPHA_POW = 32, SMALL_GATE_SCALE = SMALL_ALPHA_POW + QUOTIENT_MAX_CH * QUOTIENT_ALPHA_POWS;
 
 struct GateDev {  // = lcp2_gate
   u32 selector_index, selector_value, group_start, group_end, code_offset, code_len, num_constraints, flags;
@@ -132,6 +132,8 @@ void launch_fri_fold(hipStream_t s, const u64 *c0, const u64 *c1, u64 *o0, u64 *
 void launch_gather_ext_leaves(hipStream_t s, const u64 *p0, const u64 *p1, u32 arity, const u64 *leaf_idx, u32 k, u64 *out);
 void launch_pow_search(hipStream_t s, const PowArgs &a, u64 count);
 void launch_fill(hipStream_t s, u64 *p, u64 n, u64 v);
+// *flag = 1 if a word of p[r * pitch + i] (r < rows, i < width) is a non-zero field element (flag zeroed by the caller)
+void launch_any_nonzero(hipStream_t s, const u64 *p, u64 pitch, u64 width, u32 rows, unsigned long long *flag);
 
 // ---- challenge-dependent setup on the device.  The challenges of a proof are a handful of words that the host draws from the
 // transcript; everything the kernels need that is derived from them (powers, inverses, limb tables) is computed by these small

@@ -304,10 +304,12 @@ std::unique_ptr<CircuitData> CircuitBuilder::build() {
   const uint32_t NR = cfg.num_routed_wires, npi = (uint32_t)d->public_inputs.size();
   GateSetLayout gs = build_gate_set(cfg.max_quotient_degree_factor + 1);
   CircuitDescription &D = data->desc_;
-  if (lcp2_params_standard(degree_bits, gs.num_selectors + cfg.num_constants, &D.params) != LCP2_OK) throw std::runtime_error("bad circuit size");
-  D.params.num_wires = cfg.num_wires; D.params.num_routed_wires = NR; D.params.rate_bits = cfg.rate_bits; D.params.cap_height = cfg.cap_height;
+  // the FRI schedule follows the config's own rate_bits / cap_height
+  if (lcp2_params_config(degree_bits, gs.num_selectors + cfg.num_constants, cfg.rate_bits, cfg.cap_height, cfg.proof_of_work_bits,
+                         cfg.num_query_rounds, cfg.fri_arity_bits, cfg.fri_final_poly_bits, &D.params) != LCP2_OK)
+    throw std::runtime_error("bad circuit size or FRI config");
+  D.params.num_wires = cfg.num_wires; D.params.num_routed_wires = NR;
   D.params.num_challenges = cfg.num_challenges; D.params.quotient_degree_factor = cfg.max_quotient_degree_factor;
-  D.params.proof_of_work_bits = cfg.proof_of_work_bits; D.params.num_query_rounds = cfg.num_query_rounds;
   D.num_selectors = gs.num_selectors; D.gates = gs.gates; D.code = gs.code; D.imm = gs.imm; D.num_public_inputs = npi; D.num_regs = gs.num_regs;
   const uint32_t NC = D.params.num_constants;
   D.constants_sigmas.assign((size_t)(NC + NR) * n, 0);

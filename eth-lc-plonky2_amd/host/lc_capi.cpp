@@ -6,6 +6,7 @@
 #include <memory>
 #include <string>
 #include "light_client_update.hpp"
+#include "recursion.hpp"
 
 using namespace lc;
 
@@ -21,6 +22,9 @@ struct lch_session {
   PartialWitness pw;
   lch_info info{};
   std::vector<uint64_t> expected;    // the public inputs a correct proof carries
+  bool wrap = false;                 // lch_wrap_create: proves with lch_wrap_prove, its witness is an inner proof
+  ProofWithPublicInputsTarget wrap_inner;
+  uint64_t inner_proof_words = 0;
 };
 
 extern "C" const char *lch_last_error(void) { return g_error.c_str(); }
@@ -118,8 +122,69 @@ extern "C" int lch_get_info(const lch_session *s, lch_info *out) {
   return LCP2_OK;
 }
 
+extern "C" int lch_wrap_create(lcp2_ctx *ctx, const lch_session *inner, uint32_t rate_bits, uint32_t cap_height, uint32_t proof_of_work_bits,
+                               uint32_t num_query_rounds, lch_session **out) {
+  if (!ctx || !inner || !out) return fail(LCP2_E_INVALID, "null argument");
+  *out = nullptr;
+  try {
+    std::unique_ptr<lch_session> s(new lch_session());
+    CircuitConfig cfg = CircuitConfig::standard_recursion_config();
+    cfg.rate_bits = rate_bits; cfg.cap_height = cap_height; cfg.proof_of_work_bits = proof_of_work_bits; cfg.num_query_rounds = num_query_rounds;
+    auto t0 = std::chrono::steady_clock::now();
+    WrapCircuit w = build_wrap_circuit(cfg, *inner->data);
+    s->info.build_ms = ms_since(t0);
+    s->data = std::move(w.data);
+    s->wrap = true;
+    s->wrap_inner = std::move(w.inner_proof);
+    s->inner_proof_words = inner->info.proof_words;
+    s->expected = inner->expected;  // the inner public inputs are registered as the wrap's own
+    s->info.num_gates = w.num_gates;
+    t0 = std::chrono::steady_clock::now();
+    s->data->attach_gpu(ctx);
+    s->info.attach_ms = ms_since(t0);
+    s->info.degree_bits = s->data->degree_bits();
+    s->info.num_public_inputs = s->data->description().num_public_inputs;
+    s->info.proof_words = lcp2_proof_words(&s->data->description().params);
+    s->info.inner_degree_bits = inner->info.degree_bits;
+    s->info.inner_public_inputs = inner->info.num_public_inputs;
+    if (s->info.num_public_inputs != inner->info.num_public_inputs) return fail(LCP2_E_INVALID, "wrap circuit: public input count");
+    *out = s.release();
+    return LCP2_OK;
+  } catch (const std::bad_alloc &) {
+    return fail(LCP2_E_OOM, "out of host memory");
+  } catch (const std::exception &e) {
+    return fail(LCP2_E_INVALID, e.what());
+  }
+}
+
+extern "C" int lch_wrap_prove(lch_session *s, const uint64_t *inner_proof, size_t inner_proof_words, const uint64_t *inner_public_inputs,
+                              size_t num_inner_public_inputs, uint64_t *proof, size_t proof_words, uint64_t *public_inputs, size_t num_public_inputs) {
+  if (!s || !inner_proof || !proof || (!inner_public_inputs && num_inner_public_inputs) || (!public_inputs && num_public_inputs))
+    return fail(LCP2_E_INVALID, "null argument");
+  if (!s->wrap) return fail(LCP2_E_INVALID, "not a wrap session (lch_wrap_create)");
+  if (inner_proof_words != s->inner_proof_words || num_inner_public_inputs != s->wrap_inner.public_inputs.size() ||
+      proof_words != s->info.proof_words || num_public_inputs != s->info.num_public_inputs)
+    return fail(LCP2_E_INVALID, "buffer lengths do not match the inner session / lch_get_info");
+  try {
+    ProofWithPublicInputs in;
+    in.proof.assign(inner_proof, inner_proof + inner_proof_words);
+    in.public_inputs.assign(inner_public_inputs, inner_public_inputs + num_inner_public_inputs);
+    PartialWitness pw;
+    set_proof_with_pis_target(pw, s->wrap_inner, in);
+    const ProofWithPublicInputs p = s->data->prove(pw);
+    memcpy(proof, p.proof.data(), proof_words * 8);
+    if (num_public_inputs) memcpy(public_inputs, p.public_inputs.data(), num_public_inputs * 8);
+    return LCP2_OK;
+  } catch (const UnsatisfiedError &e) {  // the inner proof does not verify: the wrap circuit's witness is inconsistent
+    return fail(LCP2_E_UNSAT, e.what());
+  } catch (const std::exception &e) {
+    return fail(LCP2_E_HIP, e.what());
+  }
+}
+
 extern "C" int lch_prove(lch_session *s, uint64_t *proof, size_t proof_words, uint64_t *public_inputs, size_t num_public_inputs) {
   if (!s || !proof || (!public_inputs && num_public_inputs)) return fail(LCP2_E_INVALID, "null argument");
+  if (s->wrap) return fail(LCP2_E_INVALID, "a wrap session proves with lch_wrap_prove");
   if (proof_words != s->info.proof_words || num_public_inputs != s->info.num_public_inputs) return fail(LCP2_E_INVALID, "buffer lengths do not match lch_get_info");
   try {
     const ProofWithPublicInputs p = s->data->prove(s->pw);

@@ -44,6 +44,17 @@ int lch_get_info(const lch_session *s, lch_info *out);
 int lch_prove(lch_session *s, uint64_t *proof, size_t proof_words, uint64_t *public_inputs, size_t num_public_inputs);
 /* data.verify(proof): LCP2_OK or LCP2_E_VERIFY */
 int lch_verify(const lch_session *s, const uint64_t *proof, size_t proof_words, const uint64_t *public_inputs, size_t num_public_inputs);
+/* Shrinking a proof by recursion (plonky2's test_size_optimized_recursion): lch_wrap_create builds a circuit under the standard wire
+ * shape with the given FRI config (quotient_degree_factor 8, ConstantArityBits(4, 5)) that verifies one proof of `inner` - its verifier
+ * data built in as constants - and registers the inner public inputs as its own; `inner` may itself be a wrap session and must outlive
+ * the call only.  lch_wrap_prove proves it for one inner proof (inner_proof_words / num_inner_public_inputs: the inner session's
+ * lch_get_info); LCP2_E_UNSAT if the inner proof does not verify.  lch_get_info, lch_verify, lch_expected_public_inputs (those of the
+ * innermost session) and lch_destroy work on wrap sessions; lch_prove does not.  E.g. rate_bits 7 / cap_height 4 / 16 PoW bits /
+ * 12 queries, then rate_bits 8 / cap_height 0 / 20 / 10. */
+int lch_wrap_create(lcp2_ctx *ctx, const lch_session *inner, uint32_t rate_bits, uint32_t cap_height, uint32_t proof_of_work_bits,
+                    uint32_t num_query_rounds, lch_session **out);
+int lch_wrap_prove(lch_session *s, const uint64_t *inner_proof, size_t inner_proof_words, const uint64_t *inner_public_inputs,
+                   size_t num_inner_public_inputs, uint64_t *proof, size_t proof_words, uint64_t *public_inputs, size_t num_public_inputs);
 /* LCH_SYNC_COMMITTEE_ONLY: the native SSZ root the proved public inputs must equal (8 big-endian u32 words); else cur_state then new_state (16 words) */
 int lch_expected_public_inputs(const lch_session *s, uint64_t *out, size_t count);
 const char *lch_last_error(void);

@@ -38,6 +38,7 @@ struct VerifyError : std::runtime_error { using std::runtime_error::runtime_erro
 struct CircuitConfig {
   uint32_t num_wires = 135, num_routed_wires = 80, num_constants = 2, rate_bits = 3, cap_height = 4, num_challenges = 2,
            max_quotient_degree_factor = 8, proof_of_work_bits = 16, num_query_rounds = 28;
+  uint32_t fri_arity_bits = 4, fri_final_poly_bits = 5;  // FriReductionStrategy::ConstantArityBits(fri_arity_bits, fri_final_poly_bits)
   static CircuitConfig standard_recursion_config() { return CircuitConfig(); }
 };
 

@@ -441,4 +441,24 @@ void verify_proof(CircuitBuilder &B, const ProofWithPublicInputsTarget &pt, cons
   }
 }
 
+WrapCircuit build_wrap_circuit(const CircuitConfig &config, const CircuitData &inner) {
+  const CommonCircuitData common = CommonCircuitData::of(inner.description());
+  uint64_t digest[4];
+  std::vector<uint64_t> cap;
+  inner.verifier_only_data(digest, cap);
+  CircuitBuilder builder(config);
+  WrapCircuit w;
+  w.inner_proof = add_virtual_proof_with_pis(builder, common);
+  const VerifierCircuitTarget vd = constant_verifier_data(builder, digest, cap);
+  verify_proof(builder, w.inner_proof, vd, common);
+  for (Target t : w.inner_proof.public_inputs) builder.register_public_input(t);
+  w.num_gates = builder.num_gates();
+  w.data = builder.build();
+  return w;
+}
+
+void set_wrap_witness(PartialWitness &witness, const WrapCircuit &wrap, const ProofWithPublicInputs &inner_proof) {
+  set_proof_with_pis_target(witness, wrap.inner_proof, inner_proof);
+}
+
 }  // namespace lc

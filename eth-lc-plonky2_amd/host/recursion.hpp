@@ -54,6 +54,17 @@ void set_proof_with_pis_target(PartialWitness &witness, const ProofWithPublicInp
 void set_verifier_data_target(PartialWitness &witness, const VerifierCircuitTarget &target, const uint64_t circuit_digest[4],
                               const std::vector<uint64_t> &constants_sigmas_cap);
 
+// A circuit under `config` that verifies one proof of `inner` (attached to a device: its verifier data is taken from there and
+// built in as constants, plonky2's constant_verifier_data) and registers the inner public inputs as its own: the step that
+// shrinks a proof by recursion (plonky2's test_size_optimized_recursion).  Its proofs can be wrapped again.
+struct WrapCircuit {
+  std::unique_ptr<CircuitData> data;
+  ProofWithPublicInputsTarget inner_proof;
+  size_t num_gates = 0;  // before padding
+};
+WrapCircuit build_wrap_circuit(const CircuitConfig &config, const CircuitData &inner);
+void set_wrap_witness(PartialWitness &witness, const WrapCircuit &wrap, const ProofWithPublicInputs &inner_proof);
+
 // the pieces, usable on their own (plonky2: hash_n_to_hash_no_pad, verify_merkle_proof_to_cap_with_cap_index, RecursiveChallenger)
 std::array<Target, 4> hash_n_to_hash_no_pad(CircuitBuilder &builder, const std::vector<Target> &inputs);
 void verify_merkle_proof_to_cap(CircuitBuilder &builder, const std::vector<Target> &leaf_data, const std::vector<BoolTarget> &leaf_index_bits,

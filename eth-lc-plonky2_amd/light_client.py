@@ -46,6 +46,10 @@ def load_host_library():
     lib.lch_verify.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]
     lib.lch_expected_public_inputs.restype = c.c_int
     lib.lch_expected_public_inputs.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t]
+    lib.lch_wrap_create.restype = c.c_int
+    lib.lch_wrap_create.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.POINTER(c.c_void_p)]
+    lib.lch_wrap_prove.restype = c.c_int
+    lib.lch_wrap_prove.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]
     lib.lch_last_error.restype = c.c_char_p
     _host = lib
     return lib
@@ -105,3 +109,31 @@ class LightClientStep:
             self.close()
         except Exception:
             pass
+
+
+class WrapStep(LightClientStep):
+    """lch_wrap_create: a circuit under a high-rate FRI config that verifies one proof of `inner` (a LightClientStep or another
+    WrapStep) and carries its public inputs; prove(inner_proof, inner_pis) = lch_wrap_prove"""
+
+    def __init__(self, ctx, inner, rate_bits, cap_height, proof_of_work_bits, num_query_rounds):
+        self.lib = load_host_library()
+        self.ctx, self.inner_info = ctx, inner.info
+        h = ctypes.c_void_p()
+        rc = self.lib.lch_wrap_create(ctx.handle, inner.handle, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, ctypes.byref(h))
+        if rc:
+            raise _b.Lcp2Error(rc, self.lib.lch_last_error().decode())
+        self.handle = h
+        self.info = Info()
+        self.lib.lch_get_info(self.handle, ctypes.byref(self.info))
+        self.expected_public_inputs = inner.expected_public_inputs.copy()
+
+    def prove(self, inner_proof, inner_pis):
+        ip = np.ascontiguousarray(inner_proof, dtype=np.uint64)
+        ipi = np.ascontiguousarray(inner_pis, dtype=np.uint64)
+        proof = np.zeros(self.info.proof_words, dtype=np.uint64)
+        pis = np.zeros(self.info.num_public_inputs, dtype=np.uint64)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        rc = self.lib.lch_wrap_prove(self.handle, vp(ip), ip.size, vp(ipi), ipi.size, vp(proof), proof.size, vp(pis), pis.size)
+        if rc:
+            raise _b.Lcp2Error(rc, self.lib.lch_last_error().decode())
+        return proof, pis

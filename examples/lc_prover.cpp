@@ -11,6 +11,8 @@
 // their SSZ root (1 025 two_to_one_sha256), the root a public input checked against the native SSZ root.
 // --extra-committees C adds C more SyncCommitteeSSZ gadgets (1 025 two_to_one_sha256 = 317 750 rows each) on the update's own
 // committee: with C = 6 the circuit has 7 x 1 025 + 32 hashes and 2^22 rows, the reference's scale, made of real gadgets.
+// --shrink wraps the last light-client proof twice by recursion (plonky2's test_size_optimized_recursion: rate_bits 7, cap 4,
+// 12 queries, 16 PoW bits, then rate_bits 8, cap 0, 10 queries, 20 PoW bits), verifies each step and prints its size.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +21,7 @@
 #include <sstream>
 #include <string>
 #include "../eth-lc-plonky2_amd/host/light_client_update.hpp"
+#include "../eth-lc-plonky2_amd/host/recursion.hpp"
 
 using namespace lc;
 
@@ -40,8 +43,8 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 int main(int argc, char **argv) {
-  if (argc < 3) { fprintf(stderr, "usage: %s <prev_update.json> <cur_update.json> [--witness-only] [--device N] [--repeat K] [--extra-committees C] [--bls-proof-stand-in] [--sync-committee-only]\n", argv[0]); return 2; }
-  bool witness_only = false, bls = false, ssz_only = false;
+  if (argc < 3) { fprintf(stderr, "usage: %s <prev_update.json> <cur_update.json> [--witness-only] [--device N] [--repeat K] [--extra-committees C] [--bls-proof-stand-in] [--sync-committee-only] [--shrink]\n", argv[0]); return 2; }
+  bool witness_only = false, bls = false, ssz_only = false, shrink = false;
   int device = 0, repeat = 1, extra = 0;
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--witness-only")) witness_only = true;
@@ -50,6 +53,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--extra-committees") && i + 1 < argc) extra = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--bls-proof-stand-in")) bls = true;
     else if (!strcmp(argv[i], "--sync-committee-only")) ssz_only = true;
+    else if (!strcmp(argv[i], "--shrink")) shrink = true;
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
   try {
@@ -171,6 +175,7 @@ int main(int argc, char **argv) {
     data->attach_gpu(ctx);
     printf("constants/sigmas committed on the GPU in %.1f ms\n", ms_since(t0));
     const bool prof = getenv("LCP2_PROF") != nullptr;  // HIP-event time per kernel family of the last proof
+    ProofWithPublicInputs last;
     for (int k = 0; k < repeat; k++) {
       if (prof && k == repeat - 1) { lcp2_prof_enable(ctx, 1); lcp2_prof_reset(ctx); }
       t0 = std::chrono::steady_clock::now();
@@ -180,6 +185,7 @@ int main(int argc, char **argv) {
       data->verify(proof);
       printf("proof %d: proved in %.1f ms (witness generation included), verified in %.1f ms, %zu proof words, %zu public inputs\n", k, prove_ms,
              ms_since(t0), proof.proof.size(), proof.public_inputs.size());
+      if (k == repeat - 1) last = proof;
     }
     if (prof) {
       static const char *names[LCP2_K_COUNT] = {"intt", "lde", "leaf_hash", "merkle", "perm_z", "quotient", "openings", "fri", "pow", "sha256_witness", "other"};
@@ -192,6 +198,36 @@ int main(int argc, char **argv) {
         if (launches) printf("  %-15s %8.3f ms  (%llu scopes)\n", names[f], ms, (unsigned long long)launches);
       }
       printf("  %-15s %8.3f ms\n", "sum of kernels", sum);
+    }
+    if (shrink && repeat < 1) throw std::runtime_error("--shrink needs a proof (--repeat >= 1)");
+    if (shrink) {  // plonky2's test_size_optimized_recursion: wrap the proof twice under high-rate FRI configs
+      auto bytes_of = [](const CircuitData &d, const ProofWithPublicInputs &p) { return lcp2_proof_bytes(&d.description().params, p.public_inputs.size(), 1); };
+      printf("shrink step 0 (light-client step): degree_bits %u, %zu gates, %zu bytes\n", data->degree_bits(), gates, bytes_of(*data, last));
+      struct Step { uint32_t rate_bits, cap_height, pow_bits, queries; } steps[2] = {{7, 4, 16, 12}, {8, 0, 20, 10}};
+      const CircuitData *inner = data.get();
+      std::vector<WrapCircuit> wraps;
+      for (int k = 0; k < 2; k++) {
+        CircuitConfig cfg = CircuitConfig::standard_recursion_config();
+        cfg.rate_bits = steps[k].rate_bits; cfg.cap_height = steps[k].cap_height; cfg.proof_of_work_bits = steps[k].pow_bits; cfg.num_query_rounds = steps[k].queries;
+        t0 = std::chrono::steady_clock::now();
+        wraps.push_back(build_wrap_circuit(cfg, *inner));
+        WrapCircuit &w = wraps.back();
+        w.data->attach_gpu(ctx);
+        const double build_ms = ms_since(t0);
+        PartialWitness wpw;
+        set_wrap_witness(wpw, w, last);
+        t0 = std::chrono::steady_clock::now();
+        ProofWithPublicInputs p = w.data->prove(wpw);
+        const double prove_ms = ms_since(t0);
+        w.data->verify(p);
+        if (p.public_inputs != last.public_inputs) throw std::runtime_error("wrap: public inputs differ from the inner proof's");
+        printf("shrink step %d (rate_bits %u, cap_height %u, %u queries, %u PoW bits): degree_bits %u, %zu gates, built %.1f ms, proved %.1f ms, "
+               "verified, %zu bytes\n", k + 1, cfg.rate_bits, cfg.cap_height, cfg.num_query_rounds, cfg.proof_of_work_bits, w.data->degree_bits(),
+               w.num_gates, build_ms, prove_ms, bytes_of(*w.data, p));
+        last = std::move(p);
+        inner = w.data.get();
+      }
+      wraps.clear();
     }
     data.reset();
     bls_circuit.data.reset();

@@ -65,16 +65,29 @@ typedef struct {
   uint32_t rate_bits;              /* 3 */
   uint32_t cap_height;             /* 4 */
   uint32_t num_challenges;         /* 2 */
-  uint32_t quotient_degree_factor; /* 8 */
+  uint32_t quotient_degree_factor; /* 8; Q, 2 <= Q <= 2^rate_bits (constraint degree <= Q + 1) and
+                                      ceil(num_routed_wires / Q) <= 10 (80 routed wires: Q = 8) */
   uint32_t proof_of_work_bits;     /* 16 */
   uint32_t num_query_rounds;       /* 28 */
-  uint32_t num_fri_layers;         /* derived by lcp2_params_standard */
+  uint32_t num_fri_layers;         /* derived by lcp2_params_standard / lcp2_params_config */
   uint32_t fri_arity_bits[LCP2_MAX_FRI_LAYERS];
 } lcp2_params;
 
 /* Fills `p` with standard_recursion_config() for a circuit of 2^degree_bits rows,
  * including the ConstantArityBits(4, 5) reduction schedule. */
 int lcp2_params_standard(uint32_t degree_bits, uint32_t num_constants, lcp2_params *p);
+/* The same wire shape (135 wires, 80 routed, 2 challenges, quotient_degree_factor 8) under any FriConfig with plonky2's
+ * ConstantArityBits(arity_bits, final_poly_bits) reduction: the high-rate configs that shrink a proof by recursion, e.g.
+ * rate_bits 7 / 12 queries / 16 PoW bits, or rate_bits 8 / cap_height 0 / 10 queries / 20 PoW bits.
+ * lcp2_params_standard(d, nc, p) = lcp2_params_config(d, nc, 3, 4, 16, 28, 4, 5, p).  LCP2_E_INVALID for degree_bits outside
+ * [1, 28], rate_bits outside [1, 8], arity_bits outside [1, 5]; LCP2_E_UNSUPPORTED for a schedule of more than
+ * LCP2_MAX_FRI_LAYERS layers.
+ * The quotient (compute_quotient_polys) is evaluated on the 2^q n-point coset 7 H_{2^q n}, q = ceil(log2 Q), which is the first
+ * 2^q n leaves of every LDE; its interpolant has Q chunks of n coefficients (the rest must vanish: a constraint of degree above
+ * Q + 1 is LCP2_E_INVALID from lcp2_prove / lcp2_quotient, where plonky2's trim_to_len panics). */
+int lcp2_params_config(uint32_t degree_bits, uint32_t num_constants, uint32_t rate_bits, uint32_t cap_height,
+                       uint32_t proof_of_work_bits, uint32_t num_query_rounds, uint32_t arity_bits, uint32_t final_poly_bits,
+                       lcp2_params *p);
 
 typedef struct lcp2_ctx lcp2_ctx;
 typedef struct lcp2_oracle lcp2_oracle; /* = plonky2 PolynomialBatch, device resident */
@@ -410,7 +423,8 @@ int lcp2_hash_no_pad(const uint64_t *values, size_t count, uint64_t out[4]); /* 
  *   lcp2_quotient_commit -> sum caps -> lcp2_fri_open_begin -> sum LCP2_SECTION_OPENINGS -> lcp2_fri_open_commit ->
  *   sum LCP2_SECTION_FRI_CAP0 -> lcp2_fri_open_finish -> sum LCP2_SECTION_AFTER_CAPS.
  * At build: lcp2_circuit_create_sharded, lcp2_circuit_digest (cap share; digest not valid yet), sum the cap,
- * lcp2_circuit_set_constants_cap.  lcp2_prove / lcp2_quotient / lcp2_fri_open refuse a sharded circuit. */
+ * lcp2_circuit_set_constants_cap.  lcp2_prove / lcp2_quotient / lcp2_fri_open refuse a sharded circuit.  A sharded circuit needs
+ * quotient_degree_factor = 2^rate_bits (LCP2_E_UNSUPPORTED otherwise). */
 int lcp2_circuit_create_sharded(lcp2_ctx *ctx, const lcp2_circuit_desc *desc, uint32_t block_first, uint32_t block_count,
                                 lcp2_circuit **out);
 int lcp2_circuit_set_constants_cap(lcp2_circuit *c, const uint64_t *cap);

@@ -1,0 +1,378 @@
+"""High-rate FRI configs and quotient degree factors below 2^rate_bits (plonky2's recursion-shrinking configs).
+
+plonky2 0.1.4 evaluates the quotient on the 2^q n-point coset, q = ceil(log2 Q), and only asserts q <= rate_bits; the library
+does the same on the first 2^q n leaves of every LDE.  The oracle refuses Q != 2^rate_bits, so a high-rate proof is checked
+against the oracle through its openings: with the challenges fixed, every opening is the value of a unique polynomial at zeta
+or g zeta, independent of rate_bits."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import oracle_lib
+
+E_INVALID, E_UNSAT, E_UNSUPPORTED = -1, -5, -6
+
+# (rate_bits, cap_height, proof_of_work_bits, num_query_rounds): plonky2's test_size_optimized_recursion configs, then a middle one
+SHRINK_1 = (7, 4, 16, 12)
+SHRINK_2 = (8, 0, 20, 10)
+
+
+def _schedule(p):
+    return [p.fri_arity_bits[i] for i in range(p.num_fri_layers)]
+
+
+def _with(p, **kw):
+    arities = kw.pop("fri_arity_bits", None)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if arities is not None:
+        p.num_fri_layers = len(arities)
+        for i in range(8):
+            p.fri_arity_bits[i] = arities[i] if i < len(arities) else 0
+    return p
+
+
+# ------------------------------------------------------------------ CPU
+
+def test_params_config_reproduces_params_standard():
+    import eth_lc_plonky2_amd as m
+    for d in range(5, 29):
+        for nc in (4, 5):
+            a, b = m.standard_params(d, nc), m.params_config(d, nc, 3, 4, 16, 28, 4, 5)
+            assert bytes(a) == bytes(b), d
+
+
+@pytest.mark.parametrize("args,want", [
+    ((19, 4, 7, 4, 16, 12, 4, 5), [4, 4, 4, 4]),   # 19 -> 15 -> 11 -> 7 -> 3
+    ((12, 4, 7, 4, 16, 12, 4, 5), [4, 4]),         # 12 -> 8 -> 4
+    ((19, 4, 8, 0, 20, 10, 4, 5), [4, 4, 4, 4]),
+    ((6, 4, 8, 0, 20, 10, 4, 5), [4]),             # 6 > 5: one layer down to 2
+    ((5, 4, 8, 0, 20, 10, 4, 5), []),
+    ((10, 4, 5, 2, 16, 20, 3, 2), [3, 3, 3]),      # 10 -> 7 -> 4 -> 1
+    ((7, 4, 1, 0, 16, 28, 3, 0), [3, 3]),          # 7 -> 4 -> 1, then 1 + 1 < 0 + 3
+    ((20, 4, 1, 4, 16, 28, 2, 0), [2] * 8),        # exactly LCP2_MAX_FRI_LAYERS: 20 + 1 - 2k >= 4 + 2 up to k = 8
+])
+def test_params_config_builds_constant_arity_schedules(args, want):
+    """FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits): while degree_bits > final_poly_bits and
+    degree_bits + rate_bits - arity_bits >= cap_height, one more layer of arity_bits"""
+    import eth_lc_plonky2_amd as m
+    p = m.params_config(*args)
+    assert _schedule(p) == want
+    d, nc, rate, cap, pow_bits, queries, _, _ = args
+    assert (p.degree_bits, p.num_constants, p.rate_bits, p.cap_height, p.proof_of_work_bits, p.num_query_rounds) == (d, nc, rate, cap, pow_bits, queries)
+    assert (p.num_wires, p.num_routed_wires, p.num_challenges, p.quotient_degree_factor) == (135, 80, 2, 8)
+
+
+def test_params_config_refuses_bad_arguments():
+    import eth_lc_plonky2_amd as m
+    for args in [(0, 4, 3, 4, 16, 28, 4, 5), (29, 4, 3, 4, 16, 28, 4, 5), (10, 4, 0, 4, 16, 28, 4, 5), (10, 4, 9, 4, 16, 28, 4, 5),
+                 (10, 4, 3, 4, 16, 28, 0, 5), (10, 4, 3, 4, 16, 28, 6, 5)]:
+        with pytest.raises(m.Lcp2Error) as e:
+            m.params_config(*args)
+        assert e.value.status == E_INVALID, args
+    with pytest.raises(m.Lcp2Error) as e:  # nine layers of arity 2 do not fit LCP2_MAX_FRI_LAYERS
+        m.params_config(22, 4, 1, 4, 16, 28, 2, 0)
+    assert e.value.status == E_UNSUPPORTED
+
+
+@pytest.mark.parametrize("args", [(12, 4, *SHRINK_1[:2], 16, 12, 4, 5), (19, 4, 7, 4, 16, 12, 4, 5), (12, 4, 8, 0, 20, 10, 4, 5),
+                                  (19, 4, 8, 0, 20, 10, 4, 5), (9, 4, 5, 2, 16, 20, 3, 2)])
+def test_proof_layout_is_consistent_for_high_rate_configs(args):
+    """the offsets tile the proof: Merkle paths of d + rate_bits - cap_height siblings, one cap entry at cap_height 0"""
+    import eth_lc_plonky2_amd as m
+    lib = m.load_library()
+    p = m.params_config(*args)
+    L = m.proof_layout(p)
+    capw = 4 << p.cap_height
+    assert L.total == lib.lcp2_proof_words(ctypes.byref(p)) and L.cap_words == capw
+    assert (L.wires_cap, L.zs_cap, L.quot_cap, L.op_constants) == (0, capw, 2 * capw, 3 * capw)
+    ch, Q = p.num_challenges, p.quotient_degree_factor
+    npp = (p.num_routed_wires + Q - 1) // Q - 1
+    assert L.fri_caps == L.op_quotient + 2 * ch * Q and L.queries == L.fri_caps + p.num_fri_layers * capw
+    lg = p.degree_bits + p.rate_bits
+    pos = 0
+    for o, cols in enumerate((p.num_constants + p.num_routed_wires, p.num_wires, ch * (1 + npp), ch * Q)):
+        assert (L.q_init_off[o], L.q_init_cols[o]) == (pos, cols)
+        pos += cols + 4 * (lg - p.cap_height)
+    assert L.q_init_sib == lg - p.cap_height
+    for layer in range(p.num_fri_layers):
+        lg -= p.fri_arity_bits[layer]
+        assert (L.q_step_off[layer], L.q_step_sib[layer]) == (pos, lg - p.cap_height)
+        pos += (2 << p.fri_arity_bits[layer]) + 4 * (lg - p.cap_height)
+    assert L.query_words == pos and L.final_poly == L.queries + p.num_query_rounds * pos
+    assert L.final_len == 1 << (p.degree_bits - sum(_schedule(p)))
+    assert L.pow_witness == L.final_poly + 2 * L.final_len and L.total == L.pow_witness + 1
+
+
+@pytest.mark.parametrize("rate,Q,nr,ok", [
+    (7, 8, 80, True), (8, 8, 80, True), (4, 8, 80, True), (3, 6, 60, True), (3, 5, 50, True), (2, 3, 30, True), (1, 2, 20, True),
+    (3, 16, 80, False), (2, 8, 80, False), (1, 4, 40, False), (3, 1, 20, False), (3, 0, 80, False),
+])
+def test_verifier_create_accepts_q_up_to_2_pow_rate(rate, Q, nr, ok):
+    """lcp2_verifier_create (the host verifier, no device) runs build()'s shape check: 2 <= Q <= 2^rate_bits"""
+    import eth_lc_plonky2_amd as m
+    params = m.standard_params(5, 4)
+    circ, _, _ = m.circuit.synthetic_circuit(params, seed=3)
+    circ.params = _with(m.standard_params(5, 4), rate_bits=rate, quotient_degree_factor=Q, num_routed_wires=nr)
+    digest, cap = np.zeros(4, np.uint64), np.zeros(4 << params.cap_height, np.uint64)
+    if ok:
+        m.CircuitData.verifier_only(circ, digest, cap).close()
+    else:
+        with pytest.raises(m.Lcp2Error) as e:
+            m.CircuitData.verifier_only(circ, digest, cap)
+        assert e.value.status in (E_INVALID, E_UNSUPPORTED)
+
+
+# ------------------------------------------------------------------ circuits
+
+def low_degree_circuit(params, seed, max_degree, npi=2, poseidon_row=False):
+    """A satisfiable circuit of Noop, Constant, PublicInput, BaseSum<2> and Arithmetic rows whose selector groups are laid out
+    for constraint degree max_degree (= Q + 1), with copy constraints among the routed wires (num_routed_wires may be below
+    the 80 of synthetic_circuit: the permutation argument has ceil(num_routed_wires / Q) chunks).  poseidon_row: the gate set
+    is plonky2's standard one (PoseidonGate, degree 7) and one row runs a permutation.
+    Returns (circuit, wires, public_inputs)."""
+    from eth_lc_plonky2_amd import circuit as cm
+    from eth_lc_plonky2_amd import gl_np as gl
+    from eth_lc_plonky2_amd import poseidon_py as pos
+    if poseidon_row:
+        gs = cm.standard_gateset()
+    else:
+        gs = cm.GateSet([("NoopGate", 0, cm.gate_noop), ("ConstantGate", 1, cm.gate_constant),
+                         ("PublicInputGate", 1, cm.gate_public_input), ("BaseSumGate", 2, cm.gate_base_sum(cm.BASE_SUM_LIMBS)),
+                         ("ArithmeticGate", 3, cm.gate_arithmetic)], max_degree=max_degree)
+    params.num_constants = gs.num_selectors + 2
+    G = {name: gs.index(name) for name in gs.names}
+    rng = np.random.default_rng(seed)
+    n, Wn, NR = 1 << params.degree_bits, params.num_wires, params.num_routed_wires
+    rows = np.arange(n)
+    gate_of_row = np.full(n, G["ArithmeticGate"], dtype=np.int64)
+    gate_of_row[rows % 16 == 5] = G["BaseSumGate"]
+    gate_of_row[0] = G["PublicInputGate"]
+    gate_of_row[1:3] = G["ConstantGate"]
+    prow = 3
+    if poseidon_row:
+        gate_of_row[prow] = G["PoseidonGate"]
+    gate_of_row[n - 4:] = G["NoopGate"]
+    arith = np.nonzero(gate_of_row == G["ArithmeticGate"])[0]
+    arith = arith[:arith.size // 2 * 2]
+    gate_of_row[np.setdiff1d(np.nonzero(gate_of_row == G["ArithmeticGate"])[0], arith)] = G["NoopGate"]
+    wires = rng.integers(0, gl.P, size=(Wn, n), dtype=np.uint64)
+    c0 = rng.integers(0, gl.P, size=n, dtype=np.uint64)
+    c1 = rng.integers(0, gl.P, size=n, dtype=np.uint64)
+    pis = rng.integers(0, gl.P, size=npi, dtype=np.uint64)
+    sig_row, sig_col = np.tile(rows, (NR, 1)), np.tile(np.arange(NR)[:, None], (1, n))
+
+    def link2(ra, ca, rb, cb):
+        sig_row[ca, ra], sig_col[ca, ra] = rb, cb
+        sig_row[cb, rb], sig_col[cb, rb] = ra, ca
+
+    wires[0, 1:3], wires[1, 1:3] = c0[1:3], c1[1:3]
+    first, second = arith[0::2], arith[1::2]
+    for k in range(cm.ARITH_OPS):
+        x, y, z = wires[4 * k, first], wires[4 * k + 1, first], wires[4 * k + 2, first]
+        out = gl.add(gl.mul(gl.mul(x, y), c0[first]), gl.mul(z, c1[first]))
+        wires[4 * k + 3, first] = out
+        wires[4 * k, second] = out
+        if 4 * k + 3 < NR:
+            link2(second, 4 * k, first, 4 * k + 3)
+        y2, z2 = wires[4 * k + 1, second], wires[4 * k + 2, second]
+        wires[4 * k + 3, second] = gl.add(gl.mul(gl.mul(out, y2), c0[second]), gl.mul(z2, c1[second]))
+    bs = np.nonzero(gate_of_row == G["BaseSumGate"])[0]
+    val = rng.integers(0, 1 << 63, size=bs.size, dtype=np.uint64)
+    wires[0, bs] = val
+    for i in range(cm.BASE_SUM_LIMBS):
+        wires[1 + i, bs] = (val >> np.uint64(i)) & np.uint64(1)
+    if poseidon_row:
+        state = [int(v) for v in rng.integers(0, gl.P, size=12, dtype=np.uint64)]
+        wires[:pos.NUM_WIRES, prow] = np.array(pos.gate_row(state, 0), dtype=np.uint64)
+    wires[:4, 0] = np.array(pos.hash_no_pad(pis), dtype=np.uint64)
+    k_is = gl.powers(7, NR)
+    sig = cm.sigma_values(sig_row, sig_col, k_is, params.degree_bits)
+    consts = np.concatenate([gs.selector_columns(gate_of_row), c0[None, :], c1[None, :]])
+    circ = cm.Circuit(params, gs, np.concatenate([consts, sig]), k_is, npi)
+    return circ, wires, pis
+
+
+def _low_params(m, degree_bits, rate, Q, nr, **kw):
+    p = m.params_config(degree_bits, 4, rate, kw.pop("cap_height", 2), kw.pop("pow_bits", 8), kw.pop("queries", 12), 2, 3)
+    return _with(p, quotient_degree_factor=Q, num_routed_wires=nr, **kw)
+
+
+def test_low_degree_circuit_satisfies_the_oracle(oracle):
+    """the helper's circuit is satisfiable (the oracle's row-wise check of gates and copy constraints)"""
+    import eth_lc_plonky2_amd as m
+    params = _low_params(m, 7, 2, 4, 40)
+    circ, wires, pis = low_degree_circuit(params, seed=1, max_degree=5)
+    oc = oracle_lib.OracleCircuit(oracle, circ)
+    assert oc.check_witness(wires, pis)[0] == 0
+    oc.close()
+
+
+# ------------------------------------------------------------------ GPU: the openings do not depend on rate_bits
+
+def _openings_at(m, gpu_ctx, circ, wires, pis, ch):
+    """drive the seams with fixed challenges and return the LCP2_SECTION_OPENINGS words"""
+    data = m.CircuitData.build(gpu_ctx, circ)
+    try:
+        data.commit_wires(wires)
+        data.perm_zs(ch["betas"][:2], ch["gammas"][:2])
+        data.quotient(ch["alphas"][:2], m.binding.hash_no_pad(pis))
+        proof = np.zeros(data.proof_words, dtype=np.uint64)
+        data.fri_open_begin(ch["zeta"], m.binding.ChallengerState(), proof)
+        lo, cnt = data.proof_section(m.binding.SECTION_OPENINGS)
+        return proof[lo:lo + cnt].copy()
+    finally:
+        data.close()
+
+
+def _base_openings(m, gpu_ctx, oracle, circ, wires, pis):
+    """the proof at rate_bits = q equals the oracle's; its challenges and openings"""
+    oc = oracle_lib.OracleCircuit(oracle, circ)
+    want = oc.prove(wires, pis)
+    oc.close()
+    data = m.CircuitData.build(gpu_ctx, circ)
+    got = data.prove(wires, pis)
+    assert (got == want).all(), "GPU proof at rate_bits = q differs from the oracle's"
+    ch = data.last_challenges()
+    lo, cnt = data.proof_section(m.binding.SECTION_OPENINGS)
+    data.close()
+    return ch, got[lo:lo + cnt].copy()
+
+
+@pytest.mark.gpu
+def test_openings_of_the_synthetic_circuit_do_not_depend_on_rate(gpu_ctx, oracle):
+    """Q = 8: rate 3 (the oracle) against rates 4, 5, 7 and 8 with the same challenges"""
+    import eth_lc_plonky2_amd as m
+    d = 7
+    base = m.params_config(d, 4, 3, 4, 16, 12, 4, 5)
+    circ, wires, pis = m.circuit.synthetic_circuit(base, seed=901)
+    ch, want = _base_openings(m, gpu_ctx, oracle, circ, wires, pis)
+    for rate, cap in ((4, 4), (5, 2), (7, 4), (8, 0)):
+        circ.params = m.params_config(d, 4, rate, cap, 16, 12, 4, 5)
+        got = _openings_at(m, gpu_ctx, circ, wires, pis, ch)
+        assert (got == want).all(), f"rate_bits {rate}: {int((got != want).sum())} opening words differ"
+
+
+@pytest.mark.gpu
+def test_openings_of_a_low_degree_circuit_do_not_depend_on_rate(gpu_ctx, oracle):
+    """Q = 4 with selector groups for degree 5: rate 2 (the oracle) against rates 3 and 6"""
+    import eth_lc_plonky2_amd as m
+    d = 7
+    circ, wires, pis = low_degree_circuit(_low_params(m, d, 2, 4, 40), seed=902, max_degree=5)
+    ch, want = _base_openings(m, gpu_ctx, oracle, circ, wires, pis)
+    for rate in (3, 6):
+        circ.params = _low_params(m, d, rate, 4, 40, num_constants=circ.params.num_constants)
+        got = _openings_at(m, gpu_ctx, circ, wires, pis, ch)
+        assert (got == want).all(), f"rate_bits {rate}: {int((got != want).sum())} opening words differ"
+
+
+# ------------------------------------------------------------------ GPU: whole proofs
+
+def _sections(m, p):
+    L = m.proof_layout(p)
+    out = {"wires_cap": L.wires_cap, "zs_cap": L.zs_cap, "quotient_cap": L.quot_cap, "openings": L.op_constants,
+           "quotient_openings": L.op_quotient, "queries": L.queries, "final_poly": L.final_poly, "pow_witness": L.pow_witness}
+    if p.num_fri_layers:
+        out["fri_caps"] = L.fri_caps
+    return out
+
+
+def _whole_proof_checks(m, gpu_ctx, circ, wires, pis):
+    params = circ.params
+    data = m.CircuitData.build(gpu_ctx, circ)
+    proof = data.prove(wires, pis)
+    data.verify(proof, pis)
+    assert (data.prove(wires, pis) == proof).all(), "proving twice gave two proofs"
+    digest, cap = data.digest()
+    vo = m.CircuitData.verifier_only(circ, digest, cap)
+    vo.verify(proof, pis)
+    for name, at in _sections(m, params).items():
+        bad = proof.copy()
+        bad[at] = np.uint64((int(bad[at]) + 1) % m.GOLDILOCKS_P)
+        with pytest.raises(m.Lcp2Error):
+            vo.verify(bad, pis)
+    raw = m.proof_to_bytes(params, proof, pis)
+    back, pis2 = m.proof_from_bytes(params, raw, len(pis))
+    assert (np.asarray(back) == proof).all() and list(pis2) == list(pis)
+    vo.close()
+    return data, proof
+
+
+def _arith_pairs(circ):
+    """the ArithmeticGate row pairs of a circuit (from its selector column) and its two gate constants"""
+    gs = circ.gateset
+    g = gs.index("ArithmeticGate")
+    arith = np.nonzero(circ.constants_sigmas[gs.gates[g].selector_index] == g)[0]
+    ns = gs.num_selectors
+    return arith[0::2], arith[1::2], circ.constants_sigmas[ns], circ.constants_sigmas[ns + 1]
+
+
+def _broken_witnesses_are_unsat(m, data, circ, wires, pis):
+    """a broken gate row (the output of the last operation of a second row: no copy constraint) and a broken copy constraint
+    (a second row's first multiplicand no longer equals the first row's output; the row itself still holds) are LCP2_E_UNSAT"""
+    from eth_lc_plonky2_amd import circuit as cm
+    from eth_lc_plonky2_amd import gl_np as gl
+    first, second, c0, c1 = _arith_pairs(circ)
+    s = int(second[len(second) // 2])
+    w2 = wires.copy()
+    w2[4 * cm.ARITH_OPS - 1, s] ^= np.uint64(1)
+    with pytest.raises(m.Lcp2Error) as e:
+        data.prove(w2, pis)
+    assert e.value.status == E_UNSAT
+    w3 = wires.copy()
+    w3[0, s] ^= np.uint64(1)
+    one = slice(s, s + 1)
+    w3[3, s] = gl.add(gl.mul(gl.mul(w3[0, one], w3[1, one]), c0[one]), gl.mul(w3[2, one], c1[one]))[0]
+    with pytest.raises(m.Lcp2Error) as e:
+        data.prove(w3, pis)
+    assert e.value.status == E_UNSAT
+
+
+WHOLE = [
+    ("shrink_1", lambda m: m.params_config(8, 4, *SHRINK_1[:2], SHRINK_1[2], SHRINK_1[3], 4, 5)),
+    ("shrink_2", lambda m: m.params_config(8, 4, *SHRINK_2[:2], SHRINK_2[2], SHRINK_2[3], 4, 5)),
+    ("rate5_cap2_arities_321", lambda m: _with(m.params_config(8, 4, 5, 2, 12, 16, 4, 5), fri_arity_bits=[3, 2, 1])),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,make", WHOLE, ids=[w[0] for w in WHOLE])
+def test_high_rate_proofs_verify(gpu_ctx, name, make):
+    """Q = 8 under high-rate configs: verifies (handle and verifier-only handle), every section is bound, bytes round-trip,
+    deterministic; a broken gate row or copy constraint is LCP2_E_UNSAT"""
+    import eth_lc_plonky2_amd as m
+    params = make(m)
+    circ, wires, pis = m.circuit.synthetic_circuit(params, seed=910)
+    data, _ = _whole_proof_checks(m, gpu_ctx, circ, wires, pis)
+    _broken_witnesses_are_unsat(m, data, circ, wires, pis)
+    data.close()
+
+
+@pytest.mark.gpu
+def test_q6_at_rate_3(gpu_ctx):
+    """Q = 6 < 2^rate_bits = 8 (selector groups for degree 7, 60 routed wires: 10 chunks): whole proof checks, a broken gate
+    row and a broken copy constraint are LCP2_E_UNSAT, a sharded create is LCP2_E_UNSUPPORTED"""
+    import eth_lc_plonky2_amd as m
+    params = _low_params(m, 8, 3, 6, 60, cap_height=4, pow_bits=10, queries=20)
+    circ, wires, pis = low_degree_circuit(params, seed=920, max_degree=7)
+    data, _ = _whole_proof_checks(m, gpu_ctx, circ, wires, pis)
+    _broken_witnesses_are_unsat(m, data, circ, wires, pis)
+    data.close()
+    with pytest.raises(m.Lcp2Error) as e:
+        m.CircuitData.build_sharded(gpu_ctx, circ, 0, 4)
+    assert e.value.status == E_UNSUPPORTED
+
+
+@pytest.mark.gpu
+def test_poseidon_rows_under_q6_are_invalid(gpu_ctx):
+    """PoseidonGate (degree 7) with its selector exceeds Q + 1 = 7: the quotient has more than Q chunks, where plonky2's
+    trim_to_len panics; the library returns LCP2_E_INVALID"""
+    import eth_lc_plonky2_amd as m
+    params = _low_params(m, 7, 3, 6, 60, cap_height=4)
+    circ, wires, pis = low_degree_circuit(params, seed=930, max_degree=9, poseidon_row=True)
+    data = m.CircuitData.build(gpu_ctx, circ)
+    with pytest.raises(m.Lcp2Error) as e:
+        data.prove(wires, pis)
+    assert e.value.status == E_INVALID and "constraint degree exceeds" in str(e.value), str(e.value)
+    data.close()
