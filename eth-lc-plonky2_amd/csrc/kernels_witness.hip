@@ -173,7 +173,7 @@ __global__ void k_scatter_cells(const CellDev *__restrict__ cells, u64 ncells, u
 }
 
 // One lane per PoseidonGate row: the permutation in its plain round form (constants, S-box, MDS), recording what enters every
-// S-box that has a wire - plonky2 gates/poseidon.rs PoseidonGenerator::run_once; wire layout as in kernels_prover.hip
+// S-box that has a wire - plonky2 gates/poseidon.rs PoseidonGenerator::run_once; wire layout as in kernels_quotient.hip
 // q_poseidon_native.  A few thousand rows per light-client proof (the recursive verifier's Merkle paths, its Challenger and the
 // sponge over the inner proof's public inputs): canonical arithmetic throughout, speed is irrelevant here.
 __global__ void k_poseidon_gate_rows(const PoseidonRowDev *__restrict__ rows, u64 nrows, u64 *__restrict__ wires, u64 n, const u64 *__restrict__ rc) {

@@ -427,7 +427,7 @@ __device__ __forceinline__ void pos_mds_h(u32 lo[12], u32 hi[12], const u64 *__r
 // Three partial rounds (see the tables above): state = u after the constant layer of the first of them, on return u of the round
 // after the third.  kc: the group's 14 constants.  next_w(i, ul, uh): element 0 after round i (1, 2) comes in as lazy halves and
 // leaves as the S-box output that enters the following round - the permutation raises it to the 7th power, the PoseidonGate
-// evaluator of the quotient (kernels_prover.hip) emits its difference to the gate's S-box wire and continues from the wire.
+// evaluator of the quotient (kernels_quotient.hip) emits its difference to the gate's S-box wire and continues from the wire.
 template <class Consts /* pointer to the 14 constants, any address space */, class NextW>
 __device__ __forceinline__ void pos_partial3_core(u32 lo[12], u32 hi[12], Consts kc, NextW next_w) {
   constexpr PosPartialTables T = pos_partial_tables();

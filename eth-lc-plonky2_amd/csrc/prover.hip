@@ -121,21 +121,6 @@ int check_params(lcp2_ctx *ctx, const lcp2_params &p) {
   return LCP2_OK;
 }
 
-// alpha_c^e, e < QUOTIENT_TERM_POWS, as three 22-bit limbs (QuotientArgs::alpha_limbs)
-std::vector<uint32_t> alpha_limb_table(const u64 *alphas, u32 CH) {
-  std::vector<uint32_t> t((size_t)QUOTIENT_MAX_CH * QUOTIENT_TERM_POWS * 4, 0);
-  for (u32 c = 0; c < CH; c++) {
-    u64 pw = 1;
-    const u64 al = gl_canon(alphas[c]);
-    for (u32 e = 0; e < QUOTIENT_TERM_POWS; e++) {
-      uint32_t *w = &t[((size_t)c * QUOTIENT_TERM_POWS + e) * 4];
-      w[0] = (uint32_t)(pw & 0x3FFFFF); w[1] = (uint32_t)((pw >> 22) & 0x3FFFFF); w[2] = (uint32_t)(pw >> 44);
-      pw = gl_mul(pw, al);
-    }
-  }
-  return t;
-}
-
 int upload(lcp2_ctx *ctx, DevBuf &b, const void *src, size_t bytes) {
   LCP2_HIP(ctx, b.ensure(bytes));
   if (bytes) LCP2_HIP(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -278,36 +263,32 @@ static int check_native_gates(lcp2_circuit *c) {
   const u64 cnt = 256;
   u64 seed = 0x9E3779B97F4A7C15ull;
   auto rnd = [&]() { seed += 0x9E3779B97F4A7C15ull; u64 z = seed; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return gl_canon(z ^ (z >> 31)); };
-  std::vector<u64> hw((size_t)p.num_wires * cnt), hc((size_t)p.num_constants * cnt), hs(SMALL_GATE_SCALE + (size_t)QUOTIENT_MAX_CH * c->gates.size(), 0);
+  std::vector<u64> hw((size_t)p.num_wires * cnt), hc((size_t)p.num_constants * cnt);
   for (auto &v : hw) v = rnd();
   for (auto &v : hc) v = rnd();
-  for (u32 i = 0; i < 4; i++) hs[SMALL_PI_HASH + i] = rnd();
   DevBuf dw, dc;
   LCP2_TRY(upload(ctx, dw, hw.data(), hw.size() * 8));
   LCP2_TRY(upload(ctx, dc, hc.data(), hc.size() * 8));
+  LCP2_HIP(ctx, c->alpha_limbs.ensure((size_t)QUOTIENT_MAX_CH * QUOTIENT_TERM_POWS * 16));
+  u64 *d_small = c->small.u();
+  QuotientSetupArgs qs{};
+  for (u32 i = 0; i < 4; i++) qs.pi_hash[i] = rnd();
+  qs.num_challenges = p.num_challenges; qs.num_gates = (u32)c->gates.size(); qs.gates = (const GateDev *)c->d_gates.p; qs.small = d_small;
+  qs.limbs = (u32 *)c->alpha_limbs.p;
+  QuotientArgs a{};
+  a.wires = dw.u(); a.consts = dc.u(); a.stride = cnt; a.count = cnt;
+  a.alphas = d_small + SMALL_ALPHAS; a.alpha_inv = d_small + SMALL_ALPHA_INV; a.pis = d_small + SMALL_PI_HASH; a.gate_scale = d_small + SMALL_GATE_SCALE;
+  a.alpha_limbs = (const u32 *)c->alpha_limbs.p;
+  a.imm = c->d_imm.u(); a.code = (const u32 *)c->d_code.p; a.gates = (const GateDev *)c->d_gates.p; a.stage_list = (const u32 *)c->d_stage.p;
+  a.num_wires = p.num_wires; a.num_gates = (u32)c->gates.size(); a.num_selectors = c->num_selectors; a.num_constants = p.num_constants;
+  a.num_challenges = p.num_challenges; a.num_regs = c->num_regs; a.rc = ctx->d_rc;
   u64 bad = ~0ull;
   // two settings of the challenges: random ones, and alpha = 0 (there the combination is the FIRST constraint alone, the corner in
-  // which a forward and a last-to-first evaluator differ if one of them folds in the wrong direction)
+  // which a forward and a last-to-first evaluator differ if one of them folds in the wrong direction).  Everything derived from
+  // them, and the reset flag, comes from the setup kernel of a proof (k_quotient_setup).
   for (int zero_alpha = 0; zero_alpha < 2 && bad == ~0ull; zero_alpha++) {
-    for (u32 k = 0; k < p.num_challenges; k++) {
-      const u64 al = zero_alpha ? 0 : gl_canon(rnd() | 1);
-      hs[SMALL_ALPHAS + k] = al;
-      hs[SMALL_ALPHA_INV + k] = al ? gl_inv(al) : 0;
-      for (size_t g = 0; g < c->gates.size(); g++)
-        hs[SMALL_GATE_SCALE + g * QUOTIENT_MAX_CH + k] = c->gates[g].num_constraints ? gl_pow(al, c->gates[g].num_constraints - 1) : 1;
-    }
-    hs[SMALL_CHECK] = ~0ull;
-    LCP2_HIP(ctx, hipMemcpyAsync(c->small.p, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    const std::vector<uint32_t> limbs = alpha_limb_table(&hs[SMALL_ALPHAS], p.num_challenges);
-    LCP2_TRY(upload(ctx, c->alpha_limbs, limbs.data(), limbs.size() * 4));
-    QuotientArgs a{};
-    u64 *d_small = c->small.u();
-    a.wires = dw.u(); a.consts = dc.u(); a.stride = cnt; a.count = cnt;
-    a.alphas = d_small + SMALL_ALPHAS; a.alpha_inv = d_small + SMALL_ALPHA_INV; a.pis = d_small + SMALL_PI_HASH; a.gate_scale = d_small + SMALL_GATE_SCALE;
-    a.alpha_limbs = (const u32 *)c->alpha_limbs.p;
-    a.imm = c->d_imm.u(); a.code = (const u32 *)c->d_code.p; a.gates = (const GateDev *)c->d_gates.p; a.stage_list = (const u32 *)c->d_stage.p;
-    a.num_wires = p.num_wires; a.num_gates = (u32)c->gates.size(); a.num_selectors = c->num_selectors; a.num_constants = p.num_constants;
-    a.num_challenges = p.num_challenges; a.num_regs = c->num_regs; a.rc = ctx->d_rc;
+    for (u32 k = 0; k < p.num_challenges; k++) qs.alphas[k] = zero_alpha ? 0 : gl_canon(rnd() | 1);
+    launch_quotient_setup(ctx->stream, qs);
     launch_native_check(ctx->stream, a, c->dev_gates, (unsigned long long *)(d_small + SMALL_CHECK));
     LCP2_HIP(ctx, hipGetLastError());
     LCP2_TRY(download(ctx, &bad, d_small + SMALL_CHECK, 8));
@@ -764,7 +745,7 @@ int stage_quotient_values(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash
     a.alpha_inv = d_small + SMALL_ALPHA_INV; a.gate_scale = d_small + SMALL_GATE_SCALE; a.alpha_pow = d_small + SMALL_ALPHA_POW;
     a.alpha_limbs = (const u32 *)c->alpha_limbs.p;
     a.code = (const u32 *)c->d_code.p; a.gates = (const GateDev *)c->d_gates.p; a.out = c->qvals.u();
-    a.stage_list = (const u32 *)c->d_stage.p; a.num_wires = W; a.use_native = 1; a.rc = ctx->d_rc;
+    a.stage_list = (const u32 *)c->d_stage.p; a.num_wires = W; a.rc = ctx->d_rc;
     a.N = NQ; a.lgN = lgNQ; a.rate_bits = qb; a.num_gates = NG; a.num_selectors = c->num_selectors;
     a.num_constants = NC; a.num_routed = NR; a.chunk = Q; a.nchunks = nchunks; a.num_challenges = CH; a.num_regs = c->dev_regs;
     a.leaf0 = (u64)c->bf * n; a.count = c->sharded() ? (u64)c->nblocks() * n : NQ; a.stride = c->sharded() ? a.count : N;

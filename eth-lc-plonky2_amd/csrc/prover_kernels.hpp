@@ -1,4 +1,4 @@
-// Argument blocks and launch wrappers of the prover kernels (kernels_prover.hip).
+// Argument blocks and launch wrappers of the prover kernels (kernels_prover.hip; K6, the quotient: kernels_quotient.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -58,13 +58,12 @@ struct QuotientArgs {
   // forward-emitting gates (LCP2_GATE_EMIT_FORWARD): sum_i alpha^i c_i = alpha^(m-1) * Horner(c_0 .. c_{m-1}; 1/alpha)
   const u32 *stage_list;   // LDG column lists: entry < num_wires: wire column, else constants column (entry - num_wires)
   u32 num_wires;
-  u32 use_native;          // 1: gates flagged LCP2_GATE_NATIVE_* run their native evaluator, 0: everything is interpreted
   const u64 *rc;           // Poseidon round constants (native PoseidonGate evaluator)
   const u64 *alpha_pow;    // [QUOTIENT_MAX_CH][QUOTIENT_ALPHA_POWS] alpha_c^e: weights of the permutation-term blocks
   u32 limbs_lds_word;       // where in a kernel's dynamic LDS (in u64 words) the copy of alpha_limbs for the generated gates sits (set per launch)
   const u32 *alpha_limbs;  // [QUOTIENT_MAX_CH][QUOTIENT_TERM_POWS][4]: alpha_c^e cut into three 22-bit limbs (+ one word of padding): a
                            // generated gate adds constraint x limbs into six 64-bit column sums per challenge, one multiply-accumulate
-                           // each and no reduction, and folds the columns once per point (kernels_prover.hip QTerms)
+                           // each and no reduction, and folds the columns once per point (quotient_common.hpp QTerms)
   const u64 *alpha_inv;    // [CH], 0 where alpha = 0
   const u64 *gate_scale;   // [num_gates][QUOTIENT_MAX_CH] alpha^(num_constraints - 1)
   const u32 *code;

@@ -1,6 +1,7 @@
-// K6 device code shared by the compile units that hold gate evaluators (kernels_prover.hip: interpreter, native plonky2 gates, light
-// gates, permutation pass; kernels_gates_*.hip: the generated straight-line evaluators of csrc/generated_gates_*.hpp): operand access,
-// the weighted-term accumulators, the gate-program interpreter and the filter.  Device functions only; nothing here is a kernel.
+// K6 device code shared by the compile units that hold gate evaluators (kernels_quotient.hip: native plonky2 gates, light gates,
+// permutation pass; kernels_gates_*.hip: the generated straight-line evaluators of csrc/generated_gates_*.hpp): operand access, the
+// weighted-term accumulators, the gate-program interpreter, the filter, and the skeleton every gate kernel is made of (q_point,
+// q_wave_holds, q_gate_value, q_gate_store; q_claim_check for the build()-time kernels).  Device functions only; nothing here is a kernel.
 #pragma once
 #include "internal.hpp"
 #include "poseidon.hpp"
@@ -78,16 +79,33 @@ __device__ u64 q_sbox(u64 x);
 // (any u64: it need not even be canonical) is two 32-bit halves, and each of the six half x limb products - below 2^54 - is one
 // v_mad_u64_u32 into a 64-bit column sum that 128 terms cannot overflow.  12 instructions per constraint and two challenges
 // instead of 40; the columns are folded (sum_l (col_l + col_(3+l) 2^32) 2^(22 l) mod p) once per point.
-struct QTerms {
+struct QTermCols {
   u64 col[QUOTIENT_MAX_CH][6];
-  u32 CH;
-  __device__ __forceinline__ void init(u32 ch) {
-    CH = ch;
+  __device__ __forceinline__ void clear() {
 #pragma unroll
     for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
 #pragma unroll
       for (u32 l = 0; l < 6; l++) col[c][l] = 0;
   }
+  __device__ __forceinline__ void fold(u64 out[QUOTIENT_MAX_CH], u32 ch) const {  // out[c], c < ch
+#pragma unroll
+    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) {
+      if (c < ch) {
+        u64 v[3];
+#pragma unroll
+        for (u32 l = 0; l < 3; l++) {  // col_l + col_(3+l) 2^32 as a 128-bit value
+          const u64 lo = col[c][l] + (col[c][3 + l] << 32);
+          const u64 hi = (col[c][3 + l] >> 32) + (lo < col[c][l] ? 1 : 0);
+          v[l] = gl_reduce128(lo, hi);
+        }
+        out[c] = gl_add(v[0], gl_add(gl_shl<22>(v[1]), gl_shl<44>(v[2])));
+      }
+    }
+  }
+};
+struct QTerms : QTermCols {
+  u32 CH;
+  __device__ __forceinline__ void init(u32 ch) { CH = ch; clear(); }
   template <u32 E>  // x * alpha^E
   __device__ __forceinline__ void add(const QuotientArgs &a, u64 x) {
     static_assert(E < QUOTIENT_TERM_POWS, "too many constraints for the alpha power table");
@@ -108,21 +126,7 @@ struct QTerms {
       }
     }
   }
-  __device__ __forceinline__ void fold(u64 out[QUOTIENT_MAX_CH]) const {
-#pragma unroll
-    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) {
-      if (c < CH) {
-        u64 v[3];
-#pragma unroll
-        for (u32 l = 0; l < 3; l++) {  // col_l + col_(3+l) 2^32 as a 128-bit value
-          const u64 lo = col[c][l] + (col[c][3 + l] << 32);
-          const u64 hi = (col[c][3 + l] >> 32) + (lo < col[c][l] ? 1 : 0);
-          v[l] = gl_reduce128(lo, hi);
-        }
-        out[c] = gl_add(v[0], gl_add(gl_shl<22>(v[1]), gl_shl<44>(v[2])));
-      }
-    }
-  }
+  __device__ __forceinline__ void fold(u64 out[QUOTIENT_MAX_CH]) const { QTermCols::fold(out, CH); }
 };
 // The same for the generated gates, with the limb table in LDS (the kernel stages it: 4 KB) and no branch on the challenge count
 // (with one challenge the second slot's limbs are zeros).  Why: a branch per constraint cuts an evaluator into hundreds of basic
@@ -130,15 +134,9 @@ struct QTerms {
 // there; and in ONE block it hoists the ~600 scalar loads of a constant-space table to the top.  LDS reads are ordered by the
 // window barriers of the generated code (Q_WINDOW_BARRIER) like the wire loads are, so the generator's schedule survives.
 typedef const __attribute__((address_space(3))) u32 *lds_u32_ptr;
-struct QTermsLds {
-  u64 col[QUOTIENT_MAX_CH][6];
+struct QTermsLds : QTermCols {
   lds_u32_ptr limbs;
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
-#pragma unroll
-      for (u32 l = 0; l < 6; l++) col[c][l] = 0;
-  }
+  __device__ __forceinline__ void init() { clear(); }
   // The column sums are plain integer additions: in one basic block hipcc reassociates the whole sum of a gate's ~100 terms into
   // an order of its own, with every term (or its operands) alive until the end.  Passing the sums through an empty asm at the
   // window boundaries of the generated code cuts the expression trees there.
@@ -163,19 +161,7 @@ struct QTermsLds {
       }
     }
   }
-  __device__ __forceinline__ void fold(u64 out[QUOTIENT_MAX_CH]) const {
-#pragma unroll
-    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) {
-      u64 v[3];
-#pragma unroll
-      for (u32 l = 0; l < 3; l++) {
-        const u64 lo = col[c][l] + (col[c][3 + l] << 32);
-        const u64 hi = (col[c][3 + l] >> 32) + (lo < col[c][l] ? 1 : 0);
-        v[l] = gl_reduce128(lo, hi);
-      }
-      out[c] = gl_add(v[0], gl_add(gl_shl<22>(v[1]), gl_shl<44>(v[2])));
-    }
-  }
+  __device__ __forceinline__ void fold(u64 out[QUOTIENT_MAX_CH]) const { QTermCols::fold(out, QUOTIENT_MAX_CH); }
 };
 // (an evaluator that uses the weighted terms never touches acc / step until finish_terms(): the compiler keeps only what is used)
 struct QEmit {
@@ -271,20 +257,39 @@ __device__ __forceinline__ void q_interpret(const QuotientArgs &a, const GateDev
     lds[dst * T + tid] = r;
   }
 }
-__device__ __forceinline__ void q_gate_finish(const QuotientArgs &a, u32 g, const GateDev &G, u64 i, const QEmit &emit, u64 val[QUOTIENT_MAX_CH]) {
-  const u32 CH = a.num_challenges;
-  const bool fwd = (G.flags & LCP2_GATE_EMIT_FORWARD) != 0;
+// filter_g(point): the selector polynomial of gate g's group with the factor of g's own value left out
+__device__ __forceinline__ u64 q_filter(const QuotientArgs &a, const GateDev &G, u64 i) {
   const u64 s = a.consts[(u64)G.selector_index * a.stride + i];
   u64 f = 1;
   for (u32 j = G.group_start; j < G.group_end; j++)
     if (j != G.selector_value) f = gl_mul(f, gl_sub((u64)j, s));
   if (a.num_selectors > 1) f = gl_mul(f, gl_sub(0xFFFFFFFFull, s));
+  return f;
+}
+__device__ __forceinline__ void q_gate_finish(const QuotientArgs &a, u32 g, const GateDev &G, u64 i, const QEmit &emit, u64 val[QUOTIENT_MAX_CH]) {
+  const u32 CH = a.num_challenges;
+  const bool fwd = (G.flags & LCP2_GATE_EMIT_FORWARD) != 0;
+  const u64 f = q_filter(a, G, i);
 #pragma unroll
   for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
     if (c < CH) {
       const u64 sum = (fwd && !emit.weighted && emit.step[c] != 0) ? gl_mul(emit.acc[c], konst(a.gate_scale)[g * QUOTIENT_MAX_CH + c]) : emit.acc[c];
       val[c] = gl_mul(f, sum);
     }
+}
+// An evaluator is a type with  static void run(a, G, i, lds, T, tid, emit): the interpreter here, the native plonky2 gates in
+// kernels_quotient.hip, the generated programs in kernels_gates.hpp.
+struct QInterpreted {
+  static __device__ __forceinline__ void run(const QuotientArgs &a, const GateDev &G, u64 i, u64 *lds, u32 T, u32 tid, QEmit &emit) { q_interpret(a, G, i, lds, T, tid, emit); }
+};
+// val[c] <- filter_g(point) * sum_i alpha_c^i constraint_{g,i}(point) with evaluator EVAL
+template <class EVAL>
+__device__ __forceinline__ void q_gate_value(const QuotientArgs &a, u32 g, const GateDev &G, u64 i, u64 *lds, u32 T, u32 tid, u64 val[QUOTIENT_MAX_CH]) {
+  QEmit emit;
+  q_emit_begin(a, G, emit);
+  emit.tl.limbs = (lds_u32_ptr)(lds + a.limbs_lds_word);  // read by the generated evaluators alone (their kernels call q_stage_limbs)
+  EVAL::run(a, G, i, lds, T, tid, emit);
+  q_gate_finish(a, g, G, i, emit, val);
 }
 #endif
 __device__ __forceinline__ GateDev q_load_gate(const QuotientArgs &a, u32 g) {
@@ -294,4 +299,59 @@ __device__ __forceinline__ GateDev q_load_gate(const QuotientArgs &a, u32 g) {
   G.code_offset = gw[4]; G.code_len = gw[5]; G.num_constraints = gw[6]; G.flags = gw[7];
   return G;
 }
+
+// ---- the skeleton of a gate kernel (k_q_gate, k_q_gen, k_q_light): CHECK = false adds filter * constraints into out[c][point] of
+// the LDE points (the first kernel of a proof stores); CHECK = true is the same evaluation over the rows of H (lcp2_prove's
+// LCP2_E_UNSAT): on a row only its own gate has a non-zero filter, so a wave skips a gate that none of its rows holds, and a
+// non-zero value is a violated constraint.  A kernel is  q_point || return; per gate: q_load_gate, q_wave_holds || skip,
+// q_gate_value; q_gate_store.  None of the pieces holds a barrier, and the early exits are `if`s in the kernel itself: folded into
+// one bool-returning prologue they cost every kernel scalar registers (the merged condition lives in an SGPR pair, not in vcc).
+// i <- this thread's point; false: past the end (CHECK: the tail re-checks the last row so that every lane votes below)
+template <bool CHECK>
+__device__ __forceinline__ bool q_point(const QuotientArgs &a, u64 &i) {
+  const u64 i0 = (u64)blockIdx.x * QUOTIENT_THREADS + threadIdx.x;
+  i = !CHECK || i0 < a.count ? i0 : a.count - 1;
+  return CHECK || i0 < a.count;
+}
+// CHECK: does a row of this wave hold gate G (wave-uniform)
+template <bool CHECK>
+__device__ __forceinline__ bool q_wave_holds(const QuotientArgs &a, const GateDev &G, u64 i) {
+  if (!CHECK) return true;
+  const u64 sel = a.consts[(u64)G.selector_index * a.stride + i];
+  return __any(sel == G.selector_value);
+}
+template <bool CHECK>
+__device__ __forceinline__ void q_gate_store(const QuotientArgs &a, u64 i, const u64 (&val)[QUOTIENT_MAX_CH], u32 accumulate, unsigned long long *flag) {
+  if (CHECK) {
+    bool bad = false;
+#pragma unroll
+    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
+      if (c < a.num_challenges && val[c] != 0) bad = true;
+    if (bad) atomicMin(flag, (unsigned long long)i + 1);
+  } else {
+    const u64 ig = a.leaf0 + i;
+#pragma unroll
+    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
+      if (c < a.num_challenges) a.out[(u64)c * a.N + ig] = accumulate ? gl_add(a.out[(u64)c * a.N + ig], val[c]) : val[c];
+  }
+}
+// build()-time check of a claim: gate g's program, interpreted, against evaluator EVAL on the random point i of a.wires / a.consts
+template <class EVAL>
+__device__ __forceinline__ void q_claim_check(const QuotientArgs &a, u32 g, u64 i, u64 *lds, u32 T, u32 tid, unsigned long long *flag) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const GateDev G = q_load_gate(a, g);
+  u64 r0[QUOTIENT_MAX_CH], r1[QUOTIENT_MAX_CH];
+  q_gate_value<QInterpreted>(a, g, G, i, lds, T, tid, r0);
+  q_gate_value<EVAL>(a, g, G, i, lds, T, tid, r1);
+  bool bad = false;
+#pragma unroll
+  for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
+    if (c < a.num_challenges && r0[c] != r1[c]) bad = true;
+  if (bad) atomicMin(flag, (unsigned long long)i + 1);
+#endif
+}
+
+// ---- launch geometry (host): one thread per point, and the dynamic LDS of a kernel that interprets (registers + staging slots)
+inline dim3 q_grid(const QuotientArgs &a) { return dim3((unsigned)((a.count + QUOTIENT_THREADS - 1) / QUOTIENT_THREADS)); }
+inline size_t q_interp_lds_bytes(const QuotientArgs &a) { return (size_t)(a.num_regs + QUOTIENT_STAGE) * QUOTIENT_THREADS * sizeof(u64); }
 }  // namespace lcp2
