@@ -9,6 +9,15 @@
  * Poseidon is pinned by the upstream permutation vectors.  Everything derived
  * from a whole proof (caps, challenges, openings, FRI) is "parity unpinned":
  * the reference holds no fixture for it and cannot be built here (no Rust).
+ *
+ * QUOTIENT DOMAIN (plonk.c): any quotient_degree_factor Q >= 2 with q = ceil(log2 Q) <= rate_bits is proved and verified, as
+ * plonky2 0.1.4 does (quotient_degree_bits = log2_ceil(Q), assert q <= rate_bits).  The combined constraint polynomial is
+ * evaluated on the 2^q n-point coset 7 <w_{2^q n}>, whose values of the committed polynomials come from their COEFFICIENTS
+ * through orc_lde_batch at rate q (an FFT of that size; they are then checked to be the rows i << (rate_bits - q) of the
+ * committed LDE), divided by Z_H (2^q distinct values), interpolated by orc_coset_ifft at size 2^q n and trimmed to Q n
+ * coefficients: a non-zero coefficient above is ORC_E_QUOTIENT_DEGREE from orc_prove (plonky2's trim_to_len panics).  The Q
+ * chunks are committed at the full rate_bits.  The verifier and the FRI code use rate_bits only for the LDE size and Q only
+ * for the chunk count and the partial-product chunking.
  */
 #ifndef ORACLE_H
 #define ORACLE_H

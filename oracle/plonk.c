@@ -113,11 +113,22 @@ struct orc_circuit {
 };
 #define NPP(p) (((p).num_routed_wires + (p).quotient_degree_factor - 1) / (p).quotient_degree_factor - 1)
 
+/* quotient_degree_bits = log2_ceil(quotient_degree_factor)  (circuit_data.rs) */
+static unsigned quotient_degree_bits(const orc_params *p) {
+  unsigned q = 0;
+  while (((uint32_t)1 << q) < p->quotient_degree_factor) q++;
+  return q;
+}
+static int quotient_shape_ok(const orc_params *p) {
+  if (p->quotient_degree_factor < 2 || p->rate_bits > 8 || quotient_degree_bits(p) > p->rate_bits) return 0; /* prover.rs asserts q <= rate_bits */
+  return (p->num_routed_wires + p->quotient_degree_factor - 1) / p->quotient_degree_factor <= 16; /* the term arrays of prover and verifier */
+}
+
 static orc_circuit *circuit_new(const orc_params *p, const uint64_t *constants_sigmas, const uint64_t *k_is, uint32_t num_selectors,
                                 const orc_gate *gates, uint32_t num_gates, const uint32_t *code, size_t code_words,
                                 const uint64_t *imm, size_t num_imm, uint32_t npi, int commit) {
   if (p->num_challenges > 4 || p->num_query_rounds > 64 || p->num_fri_layers > ORC_MAX_FRI_LAYERS) return NULL;
-  if (p->quotient_degree_factor != (1u << p->rate_bits)) return NULL; /* the LDE doubles as the quotient domain */
+  if (!quotient_shape_ok(p)) return NULL;
   orc_circuit *c = (orc_circuit *)xcalloc(1, sizeof *c);
   c->p = *p; c->n = (size_t)1 << p->degree_bits; c->num_selectors = num_selectors; c->num_gates = num_gates; c->npi = npi;
   size_t ncs = p->num_constants + p->num_routed_wires;
@@ -163,7 +174,7 @@ orc_circuit *orc_verifier_new(const orc_params *p, const uint64_t *k_is, uint32_
                               uint32_t num_gates, const uint32_t *code, size_t code_words, const uint64_t *imm, size_t num_imm,
                               uint32_t npi, const uint64_t digest[4], const uint64_t *cap) {
   if (p->num_challenges > 4 || p->num_query_rounds > 64 || p->num_fri_layers > ORC_MAX_FRI_LAYERS) return NULL;
-  if (p->quotient_degree_factor != (1u << p->rate_bits)) return NULL;
+  if (!quotient_shape_ok(p)) return NULL;
   orc_circuit *c = (orc_circuit *)xcalloc(1, sizeof *c);
   c->p = *p; c->n = (size_t)1 << p->degree_bits; c->num_selectors = num_selectors; c->num_gates = num_gates; c->npi = npi;
   c->gates = (orc_gate *)xmalloc(num_gates * sizeof(orc_gate)); memcpy(c->gates, gates, num_gates * sizeof(orc_gate));
@@ -452,28 +463,54 @@ static uint64_t *partial_products_and_zs(const orc_circuit *c, const uint64_t *w
   return out;
 }
 
-/* compute_quotient_polys: returns the CH*Q coefficient chunks, column-major [CH*Q][n] */
+/* Values of a batch on the quotient domain 7 <w_{2^q n}>, natural order, row-major [2^q n][ncols], computed from the COEFFICIENTS
+ * by a coset FFT of that size (not read out of the rate_bits LDE, which is how the device prover gets them).  Returns NULL if they
+ * are not the rows i << (rate_bits - q) of the committed LDE: get_lde_values(i, step) of plonky2. */
+static uint64_t *quotient_domain_rows(const orc_batch *b, unsigned q) {
+  size_t M = b->n << q, ncols = b->ncols;
+  uint64_t *cols = (uint64_t *)xmalloc(ncols * M * 8), *rows = (uint64_t *)xmalloc(ncols * M * 8);
+  orc_lde_batch(b->coeffs, ncols, b->n, q, GL_GENERATOR, cols);
+  int ok = 1;
+#pragma omp parallel for schedule(static) reduction(&& : ok)
+  for (size_t i = 0; i < M; i++) {
+    for (size_t c = 0; c < ncols; c++) rows[i * ncols + c] = cols[c * M + i];
+    ok = ok && memcmp(rows + i * ncols, batch_lde_row(b, i << (b->rate_bits - q)), ncols * 8) == 0;
+  }
+  free(cols);
+  if (!ok) { free(rows); return NULL; }
+  return rows;
+}
+
+/* compute_quotient_polys: the CH*Q coefficient chunks, column-major [CH*Q][n], on the 2^q n-point coset, q = quotient_degree_bits.
+ * *status: ORC_E_QUOTIENT_DEGREE if a coefficient in [Q n, 2^q n) is not zero (plonky2's trim_to_len(Q n) panics there),
+ * ORC_E_INTERNAL if the small-coset values disagree with the committed LDE; NULL is returned in both cases. */
 static uint64_t *quotient_chunks(const orc_circuit *c, const orc_batch *wires, const orc_batch *zs, const uint64_t *pis,
-                                 const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas) {
+                                 const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas, int *status) {
   const orc_params *p = &c->p;
-  size_t n = c->n, N = n << p->rate_bits, NR = p->num_routed_wires, NC = p->num_constants, CH = p->num_challenges, Q = p->quotient_degree_factor;
+  const unsigned q = quotient_degree_bits(p);
+  size_t n = c->n, M = n << q, NR = p->num_routed_wires, NC = p->num_constants, CH = p->num_challenges, Q = p->quotient_degree_factor;
   size_t nchunks = (NR + Q - 1) / Q, npp = nchunks - 1;
-  unsigned lgN = p->degree_bits + p->rate_bits;
-  uint64_t *pts = subgroup_table(lgN);
-  uint64_t *vals = (uint64_t *)xmalloc(CH * N * 8);
-  /* Z_H(7 w^i) takes 2^rate_bits values */
-  uint64_t zh_inv[256];
+  size_t W = wires->ncols, ncs = c->cs->ncols, nz = zs->ncols;
+  *status = 0;
+  uint64_t *cs_rows = quotient_domain_rows(c->cs, q), *w_rows = quotient_domain_rows(wires, q), *z_rows = quotient_domain_rows(zs, q);
+  if (!cs_rows || !w_rows || !z_rows) { free(cs_rows); free(w_rows); free(z_rows); *status = ORC_E_INTERNAL; return NULL; }
+  uint64_t *pts = subgroup_table(p->degree_bits + q);
+  uint64_t *vals = (uint64_t *)xmalloc(CH * M * 8);
+  /* Z_H(7 w^i) = 7^n root_of_unity(q)^(i mod 2^q) - 1 takes 2^q values */
+  uint64_t zh_tab[256], zh_inv[256];
   uint64_t shift_n = gl_pow(GL_GENERATOR, n);
-  for (size_t r = 0; r < ((size_t)1 << p->rate_bits); r++)
-    zh_inv[r] = gl_inv(gl_sub(gl_mul(shift_n, gl_pow(gl_root_of_unity(p->rate_bits), r)), 1));
+  size_t next_step = (size_t)1 << q; /* g = w^(2^q): the next row of H is +2^q in the quotient domain */
+  for (size_t r = 0; r < next_step; r++) {
+    zh_tab[r] = gl_sub(gl_mul(shift_n, gl_pow(gl_root_of_unity(q), r)), 1);
+    zh_inv[r] = gl_inv(zh_tab[r]);
+  }
   uint64_t ninv = gl_inv((uint64_t)n % GL_P);
-  size_t next_step = (size_t)1 << p->rate_bits; /* quotient domain = LDE domain, so step = 1 and next row = +2^rate_bits */
 #pragma omp parallel for schedule(dynamic, 64)
-  for (size_t i = 0; i < N; i++) {
+  for (size_t i = 0; i < M; i++) {
     uint64_t x = gl_mul(GL_GENERATOR, pts[i]);
-    const uint64_t *cs = batch_lde_row(c->cs, i), *w = batch_lde_row(wires, i), *zp = batch_lde_row(zs, i);
-    const uint64_t *zp_next = batch_lde_row(zs, (i + next_step) % N);
-    uint64_t zh = gl_sub(gl_mul(shift_n, gl_pow(gl_root_of_unity(p->rate_bits), i % next_step)), 1);
+    const uint64_t *cs = cs_rows + i * ncs, *w = w_rows + i * W, *zp = z_rows + i * nz;
+    const uint64_t *zp_next = z_rows + ((i + next_step) % M) * nz;
+    uint64_t zh = zh_tab[i % next_step];
     uint64_t l0 = gl_mul(gl_mul(zh, ninv), gl_inv(gl_sub(x, 1))); /* eval_l_0 ; x != 1 on the coset */
     uint64_t terms[4 + 4 * 16];
     size_t nt = 0;
@@ -496,16 +533,18 @@ static uint64_t *quotient_chunks(const orc_circuit *c, const orc_batch *wires, c
     for (size_t ch = 0; ch < CH; ch++) {
       uint64_t a = alphas[ch], acc = gates[ch];
       for (size_t t = nt; t-- > 0;) acc = gl_add(gl_mul(acc, a), terms[t]); /* reduce_with_powers over [terms, gate constraints] */
-      vals[ch * N + i] = gl_mul(acc, zh_inv[i % next_step]);
+      vals[ch * M + i] = gl_mul(acc, zh_inv[i % next_step]);
     }
   }
-  free(pts);
+  free(pts); free(cs_rows); free(w_rows); free(z_rows);
   uint64_t *chunks = (uint64_t *)xmalloc(CH * Q * n * 8);
   for (size_t ch = 0; ch < CH; ch++) {
-    orc_coset_ifft(vals + ch * N, N, GL_GENERATOR);
-    memcpy(chunks + ch * Q * n, vals + ch * N, N * 8); /* N = Q * n: chunk k = coefficients [k n, (k+1) n) */
+    orc_coset_ifft(vals + ch * M, M, GL_GENERATOR);
+    for (size_t i = Q * n; i < M; i++) if (vals[ch * M + i]) *status = ORC_E_QUOTIENT_DEGREE; /* trim_to_len(Q n) */
+    memcpy(chunks + ch * Q * n, vals + ch * M, Q * n * 8); /* chunk k = coefficients [k n, (k+1) n) */
   }
   free(vals);
+  if (*status) { free(chunks); return NULL; }
   return chunks;
 }
 
@@ -549,7 +588,7 @@ static uint64_t fri_proof_of_work(challenger *ch, unsigned pow_bits) {
 /* ------------------------------------------------------------------ prove */
 int orc_prove(const orc_circuit *cc, const uint64_t *wires_in, const uint64_t *pis_in, uint64_t *proof) {
   orc_circuit *c = (orc_circuit *)cc; /* only `last` is written */
-  if (!c->cs) return -1; /* verifier-only or unbuilt circuit */
+  if (!c->cs) return ORC_E_NOT_BUILT; /* verifier-only or unbuilt circuit */
   const orc_params *p = &c->p;
   size_t n = c->n, N = n << p->rate_bits, W = p->num_wires, NR = p->num_routed_wires, NC = p->num_constants, CH = p->num_challenges,
          Q = p->quotient_degree_factor;
@@ -584,7 +623,9 @@ int orc_prove(const orc_circuit *cc, const uint64_t *wires_in, const uint64_t *p
   ch_observe_n(&ch, zb->tree->cap, L.capw);
   for (size_t k = 0; k < CH; k++) alphas[k] = ch_get(&ch);
 
-  uint64_t *qchunks = quotient_chunks(c, wb, zb, pi_hash, betas, gammas, alphas);
+  int qstatus = 0;
+  uint64_t *qchunks = quotient_chunks(c, wb, zb, pi_hash, betas, gammas, alphas, &qstatus);
+  if (!qchunks) { free(pis); free(wires); batch_free(wb); batch_free(zb); return qstatus; }
   orc_batch *qb = batch_from_coeffs_owned(qchunks, CH * Q, p->degree_bits, p->rate_bits, p->cap_height);
   memcpy(proof + L.quot_cap, qb->tree->cap, L.capw * 8);
   ch_observe_n(&ch, qb->tree->cap, L.capw);

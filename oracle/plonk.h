@@ -58,7 +58,10 @@ orc_circuit *orc_verifier_new(const orc_params *p, const uint64_t *k_is, uint32_
 void orc_circuit_free(orc_circuit *c);
 void orc_circuit_digest(const orc_circuit *c, uint64_t digest[4], uint64_t *cap /* 2^cap_height*4, nullable */);
 size_t orc_proof_words(const orc_params *p);
-/* wires: column-major [num_wires][n] witness values.  0 on success. */
+/* wires: column-major [num_wires][n] witness values.  0 on success, otherwise one of: */
+#define ORC_E_NOT_BUILT (-1)        /* verifier-only or unbuilt circuit */
+#define ORC_E_QUOTIENT_DEGREE (-2)  /* the quotient has non-zero coefficients at or above quotient_degree_factor * n: plonky2's trim_to_len panics */
+#define ORC_E_INTERNAL (-3)         /* self-check: the quotient-domain values are not rows of the committed LDE */
 int orc_prove(const orc_circuit *c, const uint64_t *wires, const uint64_t *public_inputs, uint64_t *proof);
 /* 0 = accepted; otherwise a positive code naming the failed check */
 int orc_verify(const orc_circuit *c, const uint64_t *proof, const uint64_t *public_inputs);

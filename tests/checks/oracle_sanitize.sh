@@ -8,7 +8,7 @@ gcc -O1 -g -fPIC -shared -fopenmp -fsanitize=address,undefined -fno-omit-frame-p
 export LCP2_ORACLE_LIB=/tmp/liboracle_asan.so
 export LD_PRELOAD="$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so)"
 export ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 OMP_NUM_THREADS=4
-python -m pytest tests/test_oracle_golden.py tests/test_host_verifier.py tests/test_emu_kernels.py -x -q -m "not gpu" "$@"
+python -m pytest tests/test_oracle_golden.py tests/test_host_verifier.py tests/test_high_rate.py tests/test_emu_kernels.py -x -q -m "not gpu" "$@"
 # the C++ host layer (CircuitBuilder, gadgets, recursive verifier, BigUint) under the same sanitizers: the circuit-level tests in cpu mode
 unset LD_PRELOAD
 H=eth-lc-plonky2_amd/host

@@ -33,8 +33,17 @@ static bool g_skip_oracle_prove = false;  // set by the large test in cpu mode
 
 static std::array<uint8_t, 32> a32(const uint8_t *p) { std::array<uint8_t, 32> a; memcpy(a.data(), p, 32); return a; }
 
-// src/unit_tests.rs:29-35 prove_and_verify
-static void prove_and_verify(CircuitData &data, const PartialWitness &witness) {
+// an inner proof for the recursion tests: data.prove on the GPU in gpu mode, the oracle (the CPU prover of the tests) otherwise
+struct InnerProof {
+  std::unique_ptr<CircuitData> data;
+  ProofWithPublicInputs proof;
+  uint64_t digest[4];
+  std::vector<uint64_t> cap;
+};
+// src/unit_tests.rs:29-35 prove_and_verify.  `out` (nullable) receives the proof with its public inputs and the circuit's digest and
+// constants/sigmas cap: the oracle's in cpu mode, the GPU's (checked equal to the oracle's) in gpu mode
+static void prove_and_verify(CircuitData &data, const PartialWitness &witness, InnerProof *out = nullptr) {
+
   const CircuitDescription &D = data.description();
   std::vector<uint64_t> wires;
   std::vector<F> pis;
@@ -83,7 +92,8 @@ static void prove_and_verify(CircuitData &data, const PartialWitness &witness) {
   if (oracle_proves) {
     const auto tp = std::chrono::steady_clock::now();
     oproof.resize(orc_proof_words(&op));
-    orc_prove(oc, wires.data(), pis.data(), oproof.data());
+    const int prc = orc_prove(oc, wires.data(), pis.data(), oproof.data());
+    if (prc != 0) throw std::runtime_error("orc_prove failed with status " + std::to_string(prc));
     if (orc_verify(oc, oproof.data(), pis.data()) != 0) throw std::runtime_error("oracle verifier rejected the oracle proof");
     if (g_skip_oracle_prove) printf("oracle proved in %lld s (degree_bits %u)\n", (long long)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - tp).count(), data.degree_bits());
   }
@@ -104,7 +114,7 @@ static void prove_and_verify(CircuitData &data, const PartialWitness &witness) {
     printf("proved in %lldms (degree_bits %u)\n", (long long)ms, data.degree_bits());
     data.verify(proof);  // assert!(data.verify(proof).is_ok())
     if (!oproof.empty() && proof.proof != oproof) throw std::runtime_error("GPU proof differs from the oracle proof");
-    if (!oproof.empty() && g_skip_oracle_prove) printf("GPU proof equals the oracle proof word for word (%zu words, degree_bits %u)\n", oproof.size(), data.degree_bits());
+    if (!oproof.empty() && (g_skip_oracle_prove || out)) printf("GPU proof equals the oracle proof word for word (%zu words, degree_bits %u, rate_bits %u)\n", oproof.size(), data.degree_bits(), D.params.rate_bits);
     if (need_built && orc_verify(oc, proof.proof.data(), pis.data()) != 0) throw std::runtime_error("oracle verifier rejected the GPU proof");
     {
       // the independent verifier at ANY size: the oracle's verifier from digest + constants/sigmas cap alone (no oracle build()),
@@ -133,6 +143,7 @@ static void prove_and_verify(CircuitData &data, const PartialWitness &witness) {
       }
       orc_circuit_free(ov);
       printf("oracle verifier (digest + cap only) accepted the GPU proof and rejected two one-word changes (degree_bits %u)\n", data.degree_bits());
+      if (out) { out->proof = proof; memcpy(out->digest, digest, 32); out->cap = cap; }
     }
   } else if (oproof.empty()) {
     printf("witness generated (host, %lld ms) and every gate constraint checked (oracle), degree_bits %u\n", witness_ms, data.degree_bits());
@@ -148,18 +159,12 @@ static void prove_and_verify(CircuitData &data, const PartialWitness &witness) {
     int rc = lcp2_verify(vc, oproof.data(), oproof.size(), pis.data(), pis.size(), &failed);
     lcp2_circuit_destroy(vc);
     if (rc != LCP2_OK) throw std::runtime_error("product verifier rejected the oracle proof, check " + std::to_string(failed));
+    if (out) { out->proof.proof = oproof; out->proof.public_inputs = pis; memcpy(out->digest, digest, 32); out->cap = cap; }
     printf("proved (oracle) and verified, degree_bits %u (host witness generation %lld ms)\n", data.degree_bits(), witness_ms);
   }
   orc_circuit_free(oc);
 }
 
-// an inner proof for the recursion tests: data.prove on the GPU in gpu mode, the oracle (the CPU prover of the tests) otherwise
-struct InnerProof {
-  std::unique_ptr<CircuitData> data;
-  ProofWithPublicInputs proof;
-  uint64_t digest[4];
-  std::vector<uint64_t> cap;
-};
 static void prove_standalone(InnerProof &in, const PartialWitness &pw) {
   const CircuitDescription &D = in.data->description();
   if (g_gpu) {
@@ -734,6 +739,73 @@ static void test_recursive_verifier_tampered_sibling_panics() { recursive_verifi
 static void test_recursive_verifier_wrong_public_input_panics() { recursive_verifier(false, false, -1, true); }
 static void test_recursive_verifier_wrong_digest_panics() { recursive_verifier(false, false, -1, false, true); }
 
+// ---- shrinking a proof by recursion (plonky2's test_size_optimized_recursion, as examples/lc_prover --shrink and lch_wrap_create do
+// it): inner proof -> wrap under `first` -> wrap of that under `second`.  Every level goes through prove_and_verify, i.e. through
+// the oracle: its row-wise check of every gate, its prover at rate_bits 7 / 8 with quotient_degree_factor 8 (the quotient on the
+// first 8 n points of a 128 n / 256 n LDE) and its verifier.
+static CircuitConfig shrink_config(uint32_t rate_bits, uint32_t cap_height, uint32_t proof_of_work_bits, uint32_t num_query_rounds) {
+  CircuitConfig cfg = CircuitConfig::standard_recursion_config();
+  cfg.rate_bits = rate_bits; cfg.cap_height = cap_height; cfg.proof_of_work_bits = proof_of_work_bits; cfg.num_query_rounds = num_query_rounds;
+  return cfg;
+}
+// gpu mode: the product's build_wrap_circuit (verifier data from the attached inner circuit).  cpu mode: no device holds the inner
+// circuit, so the same circuit is put together from the same public pieces with the ORACLE's digest and cap as the constants.
+static WrapCircuit wrap_circuit_of(const CircuitConfig &cfg, const CircuitData &inner_data, const InnerProof &inner) {
+  if (g_gpu) return build_wrap_circuit(cfg, inner_data);
+  const CommonCircuitData common = CommonCircuitData::of(inner_data.description());
+  CircuitBuilder builder(cfg);
+  WrapCircuit w;
+  w.inner_proof = add_virtual_proof_with_pis(builder, common);
+  const VerifierCircuitTarget vd = constant_verifier_data(builder, inner.digest, inner.cap);
+  verify_proof(builder, w.inner_proof, vd, common);
+  for (Target t : w.inner_proof.public_inputs) builder.register_public_input(t);
+  w.num_gates = builder.num_gates();
+  w.data = builder.build();
+  return w;
+}
+static void wrap_chain(const CircuitConfig &first, const CircuitConfig &second, bool tamper_second_inner) {
+  InnerProof in = prove_inner(false, 123456789, 0xABCDE);
+  const std::vector<F> want_pis = in.proof.public_inputs;
+  const CircuitConfig cfgs[2] = {first, second};
+  std::unique_ptr<CircuitData> keep[2];
+  const CircuitData *inner_data = in.data.get();
+  InnerProof level;  // proof, digest and cap of the level below
+  level.proof = in.proof; memcpy(level.digest, in.digest, 32); level.cap = in.cap;
+  for (int k = 0; k < 2; k++) {
+    const auto t0 = std::chrono::steady_clock::now();
+    WrapCircuit w = wrap_circuit_of(cfgs[k], *inner_data, level);
+    const lcp2_params &P = w.data->description().params;
+    if (P.rate_bits != cfgs[k].rate_bits || P.cap_height != cfgs[k].cap_height || P.num_query_rounds != cfgs[k].num_query_rounds || P.quotient_degree_factor != 8)
+      throw std::runtime_error("wrap circuit: parameters are not the shrinking config's");
+    ProofWithPublicInputs fed = level.proof;
+    if (tamper_second_inner && k == 1) {  // a Merkle leaf word of the first query of the rate-7 proof: outside the transcript
+      lcp2_proof_layout L;
+      lcp2_proof_layout_of(&inner_data->description().params, &L);
+      const size_t at = L.queries + L.q_init_off[1] + 7;
+      fed.proof[at] = fed.proof[at] == 5 ? 6 : 5;
+    }
+    PartialWitness pw;
+    set_wrap_witness(pw, w, fed);
+    InnerProof next;
+    prove_and_verify(*w.data, pw, &next);
+    if (next.proof.public_inputs != want_pis) throw std::runtime_error("wrap " + std::to_string(k + 1) + ": public inputs differ from the inner proof's");
+    printf("wrap %d: rate_bits %u cap_height %u, %zu gates, 2^%u rows, %zu -> %zu proof words, %lld s\n", k + 1, P.rate_bits, P.cap_height, w.num_gates,
+           w.data->degree_bits(), level.proof.proof.size(), next.proof.proof.size(),
+           (long long)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count());
+    keep[k] = std::move(w.data);
+    inner_data = keep[k].get();
+    level.proof = next.proof; memcpy(level.digest, next.digest, 32); level.cap = next.cap;
+  }
+}
+// gpu mode: plonky2's two shrinking configs, rate_bits 7 and 8.  cpu mode: the same cap heights, PoW bits and query counts at the
+// lighter rates 4 and 5 (still quotient_degree_factor 8 = 2^3 below 2^rate_bits, the quotient on the first 8 n points of a 16 n /
+// 32 n LDE), because the oracle is the only CPU prover: measured on 8 threads, test_wrap_chain in cpu mode takes 375 s at rates 7
+// and 8 (168 s + 202 s for the two 2^13-row wraps) and 44 s at rates 4 and 5 (15 s + 27 s).
+static CircuitConfig wrap_first() { return shrink_config(g_gpu ? 7 : 4, 4, 16, 12); }
+static CircuitConfig wrap_second() { return shrink_config(g_gpu ? 8 : 5, 0, 20, 10); }
+static void test_wrap_chain() { wrap_chain(wrap_first(), wrap_second(), false); }
+static void test_wrap_chain_tampered_inner_panics() { wrap_chain(wrap_first(), wrap_second(), true); }
+
 // the outputs-only generator of a PoseidonGate row (what generate_witness_gpu runs on the host; the row itself is filled on the device)
 // against the full row generator and the oracle's permutation, swap included, non-canonical inputs included
 static void test_poseidon_gate_outputs_match_rows() {
@@ -810,6 +882,8 @@ static const TestCase TESTS[] = {
     {"test_recursive_verifier_tampered_sibling_panics", test_recursive_verifier_tampered_sibling_panics, true},
     {"test_recursive_verifier_wrong_public_input_panics", test_recursive_verifier_wrong_public_input_panics, true},
     {"test_recursive_verifier_wrong_digest_panics", test_recursive_verifier_wrong_digest_panics, true},
+    {"test_wrap_chain", test_wrap_chain, false},
+    {"test_wrap_chain_tampered_inner_panics", test_wrap_chain_tampered_inner_panics, true},
     {"test_real_gadget_circuit_2p22", test_real_gadget_circuit_2p22, false, true},
 };
 

@@ -8,6 +8,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ODIR = os.path.join(ROOT, "oracle")
 P = 0xFFFFFFFF00000001
+E_QUOTIENT_DEGREE = -2  # ORC_E_QUOTIENT_DEGREE (oracle/plonk.h): plonky2's trim_to_len(Q n) would panic
 c = ctypes
 u64p = c.POINTER(c.c_uint64)
 
@@ -182,10 +183,15 @@ class OracleCircuit:
         bad = np.zeros(2, dtype=np.uint64)
         return self.L.orc_check_witness(self.h, vp(np.ascontiguousarray(wires)), vp(np.ascontiguousarray(pis)), vp(bad)), bad
 
-    def prove(self, wires, pis):
+    def try_prove(self, wires, pis):
+        """(status of orc_prove, proof)"""
         proof = np.zeros(self.proof_words, dtype=np.uint64)
         rc = self.L.orc_prove(self.h, vp(np.ascontiguousarray(wires, dtype=np.uint64)), vp(np.ascontiguousarray(pis, dtype=np.uint64)), vp(proof))
-        assert rc == 0
+        return rc, proof
+
+    def prove(self, wires, pis):
+        rc, proof = self.try_prove(wires, pis)
+        assert rc == 0, f"orc_prove returned {rc}"
         return proof
 
     def verify(self, proof, pis):

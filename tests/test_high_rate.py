@@ -1,9 +1,11 @@
 """High-rate FRI configs and quotient degree factors below 2^rate_bits (plonky2's recursion-shrinking configs).
 
 plonky2 0.1.4 evaluates the quotient on the 2^q n-point coset, q = ceil(log2 Q), and only asserts q <= rate_bits; the library
-does the same on the first 2^q n leaves of every LDE.  The oracle refuses Q != 2^rate_bits, so a high-rate proof is checked
-against the oracle through its openings: with the challenges fixed, every opening is the value of a unique polynomial at zeta
-or g zeta, independent of rate_bits."""
+does the same on the first 2^q n leaves of every LDE.  The oracle takes the same values from the coefficients by a coset FFT of
+size 2^q n, so every config here is held to the standard of the rest of the suite: the oracle proves it and both verifiers agree
+on the proof and on every tampered section (CPU), and the GPU proof equals the oracle's in every word (GPU).  A separate
+argument stays next to that: with the challenges fixed, every opening is the value of a unique polynomial at zeta or g zeta,
+independent of rate_bits, so the openings at a high rate must be those of the proof at rate_bits = q."""
 import ctypes
 
 import numpy as np
@@ -209,6 +211,138 @@ def test_low_degree_circuit_satisfies_the_oracle(oracle):
     oc.close()
 
 
+# ------------------------------------------------------------------ CPU: the oracle proves every config, both verifiers agree
+
+def _whole(d, cfg):
+    return lambda m: m.params_config(d, 4, cfg[0], cfg[1], cfg[2], cfg[3], 4, 5)
+
+
+# name -> (params, circuit): Q = 8 under the two shrinking configs (shrink_2 also without any FRI layer: 2^5 rows) and under a
+# mixed-arity schedule; Q = 4 at q = rate_bits and below it; the non-powers of two 6, 5 and 3, where the coefficients in
+# [Q n, 2^q n) are trimmed
+ORACLE_CONFIGS = {
+    "shrink_1": (_whole(7, SHRINK_1), lambda m, p: m.circuit.synthetic_circuit(p, seed=910)),
+    "shrink_2": (_whole(6, SHRINK_2), lambda m, p: m.circuit.synthetic_circuit(p, seed=911)),
+    "shrink_2_no_fri_layers": (_whole(5, SHRINK_2), lambda m, p: m.circuit.synthetic_circuit(p, seed=912)),
+    "rate5_cap2_arities_321": (lambda m: _with(m.params_config(8, 4, 5, 2, 12, 16, 4, 5), fri_arity_bits=[3, 2, 1]),
+                               lambda m, p: m.circuit.synthetic_circuit(p, seed=913)),
+    "q4_rate2": (lambda m: _low_params(m, 7, 2, 4, 40), lambda m, p: low_degree_circuit(p, seed=914, max_degree=5)),
+    "q4_rate3": (lambda m: _low_params(m, 7, 3, 4, 40), lambda m, p: low_degree_circuit(p, seed=915, max_degree=5)),
+    "q4_rate6": (lambda m: _low_params(m, 6, 6, 4, 40), lambda m, p: low_degree_circuit(p, seed=916, max_degree=5)),
+    "q6_rate3": (lambda m: _low_params(m, 8, 3, 6, 60, cap_height=4, pow_bits=10, queries=20),
+                 lambda m, p: low_degree_circuit(p, seed=920, max_degree=7)),
+    "q5_rate3": (lambda m: _low_params(m, 6, 3, 5, 50), lambda m, p: low_degree_circuit(p, seed=917, max_degree=6)),
+    "q3_rate2": (lambda m: _low_params(m, 5, 2, 3, 30, cap_height=1), lambda m, p: low_degree_circuit(p, seed=918, max_degree=4)),
+}
+
+
+def oracle_config(m, name):
+    """(circuit, wires, public inputs) of ORACLE_CONFIGS[name]"""
+    make_params, make_circuit = ORACLE_CONFIGS[name]
+    return make_circuit(m, make_params(m))
+
+
+def tamper_spots(m, p):
+    """one word at the start of every section of the proof: the three caps, the openings, the quotient openings, the FRI caps (if
+    the schedule has a layer), the first query's first leaf word and first sibling word, the final polynomial, the PoW witness"""
+    L = m.proof_layout(p)
+    out = {"wires_cap": L.wires_cap, "zs_cap": L.zs_cap, "quotient_cap": L.quot_cap, "openings": L.op_constants,
+           "quotient_openings": L.op_quotient, "query_leaf": L.queries + L.q_init_off[0],
+           "query_sibling": L.queries + L.q_init_off[0] + L.q_init_cols[0], "final_poly": L.final_poly, "pow_witness": L.pow_witness}
+    if p.num_fri_layers:
+        out["fri_caps"] = L.fri_caps
+    assert L.q_init_sib > 0 and len(set(out.values())) == len(out)
+    return out
+
+
+@pytest.mark.parametrize("name", list(ORACLE_CONFIGS))
+def test_oracle_proves_and_both_verifiers_accept(oracle, name):
+    """the witness satisfies every gate row, the oracle proves (status 0) and verifies, the product's verifier-only handle accepts
+    the same proof, and the two sides agree on the proof's length"""
+    import eth_lc_plonky2_amd as m
+    circ, wires, pis = oracle_config(m, name)
+    p = circ.params
+    q = (p.quotient_degree_factor - 1).bit_length()
+    assert 2 <= p.quotient_degree_factor <= 1 << q <= 1 << p.rate_bits
+    lib = m.load_library()
+    assert oracle.orc_proof_words(ctypes.byref(p)) == lib.lcp2_proof_words(ctypes.byref(p)) > 0
+    oc = oracle_lib.OracleCircuit(oracle, circ)
+    bad, first = oc.check_witness(wires, pis)
+    assert bad == 0, first
+    rc, proof = oc.try_prove(wires, pis)
+    assert rc == 0
+    assert oc.verify(proof, pis) == 0
+    vd = m.CircuitData.verifier_only(circ, *oc.digest())
+    assert vd.proof_words == oc.proof_words == proof.size
+    vd.verify(proof, pis)
+    vd.close()
+    oc.close()
+
+
+def test_oracle_refuses_a_quotient_that_does_not_fit_q_chunks(oracle):
+    """the circuit of test_poseidon_rows_under_q6_are_invalid: PoseidonGate rows (degree 7, times the selector filter) under Q = 6
+    leave non-zero coefficients at or above 6 n, where plonky2's trim_to_len panics; orc_prove returns its own status for that
+    (the product: LCP2_E_INVALID) and does not abort"""
+    import eth_lc_plonky2_amd as m
+    params = _low_params(m, 7, 3, 6, 60, cap_height=4)
+    circ, wires, pis = low_degree_circuit(params, seed=930, max_degree=9, poseidon_row=True)
+    oc = oracle_lib.OracleCircuit(oracle, circ)
+    assert oc.check_witness(wires, pis)[0] == 0
+    rc, _ = oc.try_prove(wires, pis)
+    assert rc == oracle_lib.E_QUOTIENT_DEGREE != 0
+    # the same rows with room for them (Q = 8) prove
+    params8 = _low_params(m, 7, 3, 8, 80, cap_height=4)
+    circ8, wires8, pis8 = low_degree_circuit(params8, seed=930, max_degree=9, poseidon_row=True)
+    oc8 = oracle_lib.OracleCircuit(oracle, circ8)
+    rc, proof = oc8.try_prove(wires8, pis8)
+    assert rc == 0 and oc8.verify(proof, pis8) == 0
+    oc.close()
+    oc8.close()
+
+
+@pytest.mark.parametrize("Q,nr,ok", [(1, 20, False), (0, 80, False), (16, 80, False), (9, 80, False), (8, 80, True), (5, 50, True), (2, 20, True)])
+def test_oracle_constructors_refuse_only_q_below_2_or_above_2_pow_rate(oracle, Q, nr, ok):
+    """circuit_new and orc_verifier_new at rate_bits 3: 2 <= Q and ceil(log2 Q) <= rate_bits (plonky2's assertion), nothing else"""
+    import eth_lc_plonky2_amd as m
+    params = m.standard_params(5, 4)
+    circ, _, _ = m.circuit.synthetic_circuit(params, seed=3)
+    circ.params = _with(m.standard_params(5, 4), quotient_degree_factor=Q, num_routed_wires=nr)
+    gs, c = circ.gateset, ctypes
+    digest, cap = np.zeros(4, np.uint64), np.zeros(4 << params.cap_height, np.uint64)
+    hv = oracle.orc_verifier_new(c.byref(circ.params), oracle_lib.vp(circ.k_is), gs.num_selectors, c.cast(circ.gates_array, c.c_void_p), len(gs.gates),
+                                 oracle_lib.vp(gs.code), gs.code_len, oracle_lib.vp(gs.imm), gs.imm.size, circ.num_public_inputs,
+                                 oracle_lib.vp(digest), oracle_lib.vp(cap))
+    hc = oracle.orc_circuit_new(c.byref(circ.params), oracle_lib.vp(circ.constants_sigmas), oracle_lib.vp(circ.k_is), gs.num_selectors,
+                                c.cast(circ.gates_array, c.c_void_p), len(gs.gates), oracle_lib.vp(gs.code), gs.code_len, oracle_lib.vp(gs.imm),
+                                gs.imm.size, circ.num_public_inputs)
+    assert bool(hv) == bool(hc) == ok
+    for h in (hv, hc):
+        if h:
+            oracle.orc_circuit_free(h)
+
+
+def test_oracle_digest_depends_on_rate_only_through_the_cap(oracle):
+    """Proofs at rate_bits = q and at a higher rate have different challenges, so they cannot be compared word for word.  What can
+    be compared: circuit_digest = hash_no_pad(constants_sigmas_cap || hash_pad(empty domain separator) || degree_bits) at both
+    rates, i.e. rate_bits enters the digest through the cap alone (and the caps do differ)"""
+    import eth_lc_plonky2_amd as m
+    from eth_lc_plonky2_amd import poseidon_py as pos
+    sep = pos.hash_no_pad([1, 0, 0, 0, 0, 0, 0, 1])
+    for d, rates, Q, nr, deg in ((6, (3, 5, 7), 8, 80, None), (6, (2, 3, 6), 4, 40, 5), (6, (3, 4), 5, 50, 6)):
+        caps = []
+        for rate in rates:
+            if deg is None:
+                circ, _, _ = m.circuit.synthetic_circuit(m.params_config(d, 4, rate, 2, 8, 12, 2, 3), seed=940)
+            else:
+                circ, _, _ = low_degree_circuit(_low_params(m, d, rate, Q, nr), seed=940, max_degree=deg)
+            oc = oracle_lib.OracleCircuit(oracle, circ)
+            digest, cap = oc.digest()
+            oc.close()
+            assert [int(x) for x in digest] == pos.hash_no_pad([int(x) for x in cap.reshape(-1)] + sep + [d]), (Q, rate)
+            caps.append(cap.tobytes())
+        assert len(set(caps)) == len(caps), "two rates gave the same constants/sigmas cap"
+
+
 # ------------------------------------------------------------------ GPU: the openings do not depend on rate_bits
 
 def _openings_at(m, gpu_ctx, circ, wires, pis, ch):
@@ -278,7 +412,35 @@ def _sections(m, p):
     return out
 
 
-def _whole_proof_checks(m, gpu_ctx, circ, wires, pis):
+def _first_mismatch(m, params, got, want):
+    """None if the two proofs are equal, otherwise the section (of _sections) that holds the first differing word"""
+    bad = np.nonzero(got != want)[0]
+    if bad.size == 0:
+        return None
+    pos = int(bad[0])
+    name = max((at, n) for n, at in _sections(m, params).items() if at <= pos)[1]
+    return f"first mismatch at word {pos} of {want.size}, in section {name}; {bad.size} words differ"
+
+
+def _oracle_parity(m, oracle, data, circ, wires, pis, proof):
+    """the oracle builds and proves the same circuit: digest and constants/sigmas cap, every proof word and the oracle's verdict on
+    the GPU proof"""
+    oc = oracle_lib.OracleCircuit(oracle, circ)
+    bad, first = oc.check_witness(wires, pis)
+    assert bad == 0, first
+    d_gpu, cap_gpu = data.digest()
+    d_orc, cap_orc = oc.digest()
+    assert (np.asarray(cap_gpu).reshape(-1) == cap_orc.reshape(-1)).all(), "constants/sigmas cap differs from the oracle's"
+    assert (np.asarray(d_gpu) == d_orc).all(), "circuit digest differs from the oracle's"
+    want = oc.prove(wires, pis)
+    assert want.size == proof.size
+    diff = _first_mismatch(m, circ.params, proof, want)
+    assert diff is None, diff
+    assert oc.verify(proof, pis) == 0
+    oc.close()
+
+
+def _whole_proof_checks(m, gpu_ctx, oracle, circ, wires, pis):
     params = circ.params
     data = m.CircuitData.build(gpu_ctx, circ)
     proof = data.prove(wires, pis)
@@ -296,6 +458,7 @@ def _whole_proof_checks(m, gpu_ctx, circ, wires, pis):
     back, pis2 = m.proof_from_bytes(params, raw, len(pis))
     assert (np.asarray(back) == proof).all() and list(pis2) == list(pis)
     vo.close()
+    _oracle_parity(m, oracle, data, circ, wires, pis, proof)
     return data, proof
 
 
@@ -338,30 +501,59 @@ WHOLE = [
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,make", WHOLE, ids=[w[0] for w in WHOLE])
-def test_high_rate_proofs_verify(gpu_ctx, name, make):
+def test_high_rate_proofs_verify(gpu_ctx, oracle, name, make):
     """Q = 8 under high-rate configs: verifies (handle and verifier-only handle), every section is bound, bytes round-trip,
-    deterministic; a broken gate row or copy constraint is LCP2_E_UNSAT"""
+    deterministic, equal to the oracle's proof in every word (digest and cap too) and accepted by the oracle's verifier; a broken
+    gate row or copy constraint is LCP2_E_UNSAT"""
     import eth_lc_plonky2_amd as m
     params = make(m)
     circ, wires, pis = m.circuit.synthetic_circuit(params, seed=910)
-    data, _ = _whole_proof_checks(m, gpu_ctx, circ, wires, pis)
+    data, _ = _whole_proof_checks(m, gpu_ctx, oracle, circ, wires, pis)
     _broken_witnesses_are_unsat(m, data, circ, wires, pis)
     data.close()
 
 
 @pytest.mark.gpu
-def test_q6_at_rate_3(gpu_ctx):
-    """Q = 6 < 2^rate_bits = 8 (selector groups for degree 7, 60 routed wires: 10 chunks): whole proof checks, a broken gate
-    row and a broken copy constraint are LCP2_E_UNSAT, a sharded create is LCP2_E_UNSUPPORTED"""
+def test_q6_at_rate_3(gpu_ctx, oracle):
+    """Q = 6 < 2^rate_bits = 8 (selector groups for degree 7, 60 routed wires: 10 chunks): whole proof checks incl. equality with
+    the oracle's proof in every word, a broken gate row and a broken copy constraint are LCP2_E_UNSAT, a sharded create is
+    LCP2_E_UNSUPPORTED"""
     import eth_lc_plonky2_amd as m
     params = _low_params(m, 8, 3, 6, 60, cap_height=4, pow_bits=10, queries=20)
     circ, wires, pis = low_degree_circuit(params, seed=920, max_degree=7)
-    data, _ = _whole_proof_checks(m, gpu_ctx, circ, wires, pis)
+    data, _ = _whole_proof_checks(m, gpu_ctx, oracle, circ, wires, pis)
     _broken_witnesses_are_unsat(m, data, circ, wires, pis)
     data.close()
     with pytest.raises(m.Lcp2Error) as e:
         m.CircuitData.build_sharded(gpu_ctx, circ, 0, 4)
     assert e.value.status == E_UNSUPPORTED
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["q4_rate3", "q4_rate6", "q5_rate3", "q3_rate2"])
+def test_small_q_proofs_equal_the_oracle(gpu_ctx, oracle, name):
+    """Q = 4 above q = 2 (the first 4 n leaves of an 8 n and of a 64 n LDE) and the non-powers of two 5 (q = rate_bits = 3) and 3:
+    the GPU proof equals the oracle's in every word, which takes the same values from a coset FFT of size 2^q n"""
+    import eth_lc_plonky2_amd as m
+    circ, wires, pis = oracle_config(m, name)
+    data, _ = _whole_proof_checks(m, gpu_ctx, oracle, circ, wires, pis)
+    data.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,cfg", [("shrink_1", SHRINK_1), ("shrink_2", SHRINK_2)])
+def test_shrink_configs_equal_the_oracle_at_2p12_rows(gpu_ctx, oracle, name, cfg):
+    """2^12 rows under the shrinking configs: LDEs of 2^19 and 2^20 points through the multi-pass NTT / LDE and multi-block
+    paths, a four-layer cap and a cap of one digest, two FRI layers; every word equals the oracle's"""
+    import eth_lc_plonky2_amd as m
+    params = m.params_config(12, 4, cfg[0], cfg[1], cfg[2], cfg[3], 4, 5)
+    assert params.degree_bits + params.rate_bits == 12 + cfg[0] and params.num_fri_layers == 2
+    circ, wires, pis = m.circuit.synthetic_circuit(params, seed=950, small_values=(name == "shrink_2"))
+    data = m.CircuitData.build(gpu_ctx, circ)
+    proof = data.prove(wires, pis)
+    data.verify(proof, pis)
+    _oracle_parity(m, oracle, data, circ, wires, pis, proof)
+    data.close()
 
 
 @pytest.mark.gpu

@@ -1,6 +1,8 @@
 """Circuit-level tests of the C++ host layer (eth-lc-plonky2_amd/host): the reference's own #[test]s restated on the
 mirrored CircuitBuilder / gadget API (tests/cpp/test_gadgets.cpp).  CPU mode: witness generation, every gate
 constraint checked row-wise, oracle prove + verify, product host verifier.  GPU mode: data.prove on the MI355X."""
+import re
+
 import pytest
 
 import cpp_build
@@ -29,6 +31,9 @@ CPU_TESTS = [
     "test_recursive_verifier_tampered_final_poly_panics", "test_recursive_verifier_tampered_pow_panics",
     "test_recursive_verifier_tampered_sibling_panics", "test_recursive_verifier_wrong_public_input_panics",
     "test_recursive_verifier_wrong_digest_panics",
+    # shrinking by recursion (host/recursion.cpp build_wrap_circuit): wrap of a wrap, every level through the oracle's row check,
+    # prover and verifier (cpu mode at rates 4 and 5, gpu mode at plonky2's rates 7 and 8, see the comment at wrap_first())
+    "test_wrap_chain", "test_wrap_chain_tampered_inner_panics",
 ]
 
 
@@ -62,3 +67,6 @@ def test_gadgets_gpu_all():
     assert r.stdout.count("oracle verifier (digest + cap only) accepted the GPU proof") >= 20
     assert "rejected two one-word changes (degree_bits 22)" in r.stdout
     assert "rejected two one-word changes (degree_bits 19)" in r.stdout
+    # test_wrap_chain: both wraps (rate_bits 7 and 8) equal the oracle's proof in every word
+    for rate in (7, 8):
+        assert re.search(r"GPU proof equals the oracle proof word for word \(\d+ words, degree_bits \d+, rate_bits %d\)" % rate, r.stdout), rate

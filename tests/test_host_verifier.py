@@ -36,6 +36,46 @@ def test_product_verifier_accepts_oracle_proofs(oracle, degree_bits):
     vd.close()
 
 
+def _high_rate_names():
+    import test_high_rate
+    return list(test_high_rate.ORACLE_CONFIGS)
+
+
+@pytest.mark.parametrize("name", _high_rate_names())
+def test_both_verifiers_reject_every_section_of_high_rate_and_small_q_proofs(oracle, name):
+    """High-rate FRI configs and quotient degree factors below 2^rate_bits (test_high_rate.ORACLE_CONFIGS): the oracle's proof is
+    accepted by both verifiers; with one word changed at the start of any section (caps, openings, quotient openings, FRI caps,
+    a leaf and a sibling of the first query, final polynomial, PoW witness) both reject it, and they name the same check"""
+    import eth_lc_plonky2_amd as m
+    import test_high_rate
+    circ, wires, pis = test_high_rate.oracle_config(m, name)
+    oc = oracle_lib.OracleCircuit(oracle, circ)
+    proof = oc.prove(wires, pis)
+    assert oc.verify(proof, pis) == 0
+    digest, cap = oc.digest()
+    vd = m.CircuitData.verifier_only(circ, digest, cap)
+    ov = oracle_lib.OracleCircuit.verifier_only(oracle, circ, digest, cap)
+    vd.verify(proof, pis)
+    assert ov.verify(proof, pis) == 0
+    spots = test_high_rate.tamper_spots(m, circ.params)
+    assert ("fri_caps" in spots) == (circ.params.num_fri_layers > 0)
+    for section, pos in spots.items():
+        bad = proof.copy()
+        bad[pos] = np.uint64((int(bad[pos]) + 1) % m.GOLDILOCKS_P)
+        want = oc.verify(bad, pis)
+        assert want != 0 and ov.verify(bad, pis) == want, section
+        with pytest.raises(m.ProofRejected) as e:
+            vd.verify(bad, pis)
+        assert e.value.check == want, (section, e.value.check, want)
+    bad_pis = pis.copy()
+    bad_pis[1] ^= np.uint64(2)
+    assert oc.verify(proof, bad_pis) != 0
+    with pytest.raises(m.ProofRejected):
+        vd.verify(proof, bad_pis)
+    for x in (oc, ov, vd):
+        x.close()
+
+
 def test_oracle_verifier_only_circuit_agrees_with_the_built_one(oracle):
     """orc_verifier_new: the oracle's verifier from digest + cap alone (what the GPU tests use at 2^19 / 2^22 rows, where the
     oracle's build() would take minutes) gives the same verdict, check for check, as the oracle circuit that built the
