@@ -162,7 +162,7 @@ struct lcp2_oracle {
 namespace lcp2 {
 // internal commitment builders on device-resident input
 // shape checks shared by build(), the verifier-only constructor and every entry point that computes a proof layout: nullptr or
-// the reason; *unsupported tells LCP2_E_UNSUPPORTED from LCP2_E_INVALID (prover.hip)
+// the reason; *unsupported tells LCP2_E_UNSUPPORTED from LCP2_E_INVALID (prover_build.hip)
 const char *params_problem(const lcp2_params &p, bool *unsupported);
 int commit_values_dev(lcp2_ctx *ctx, const u64 *d_vals, size_t ncols, uint32_t log_n, uint32_t rate_bits,
                       uint32_t cap_height, lcp2_oracle *o, unsigned long long *noncanonical = nullptr /* device word, set to 1 if a value is >= p */);

@@ -585,7 +585,7 @@ void launch_quotient_setup(hipStream_t s, const QuotientSetupArgs &a) {
 // Coset-sharded proof: the quotient chunks out of the per-coset interpolants.  in[c][b * n + l] is coefficient l of the polynomial
 // of degree < n that agrees with challenge c's quotient on leaf block b (the coset of shift s_b); the quotient is
 // sum_k x^(k n) Q_k(x) and x^n = s_b^n on that coset, so the interpolants are a size-R transform of the chunks Q_k, coefficient by
-// coefficient, and out[c][k * n + l] = sum_b m[k][b] in[c][b * n + l] with the inverse matrix m (prover.hip).
+// coefficient, and out[c][k * n + l] = sum_b m[k][b] in[c][b * n + l] with the inverse matrix m (prover_stages.hip).
 __global__ __launch_bounds__(256) void k_quotient_combine(const u64 *__restrict__ in, u64 *__restrict__ out, const u64 *__restrict__ m, u64 n, u32 R, u64 plane) {
   const u64 l = (u64)blockIdx.x * 256 + threadIdx.x;
   if (l >= n) return;
