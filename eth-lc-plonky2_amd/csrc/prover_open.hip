@@ -45,6 +45,10 @@ int lcp2::fri_open_openings(lcp2_circuit *c, u64 *proof) {
   if (!c->cap_final) return ctx->fail(LCP2_E_INVALID, "sharded circuit: lcp2_circuit_set_constants_cap has not been called");
   FriOpenState &fo = c->fo;
   const gl2 zeta = fo.zeta, g_zeta = gl2_scale(zeta, gl_root_of_unity(p.degree_bits));
+  // k_divide_finalize divides by X - zeta and X - g zeta through the inverse powers of zeta and g zeta (k_compose_tables):
+  // zeta = 0, and with it g zeta = 0, has none.  Refused before anything is written; the handle keeps its state.
+  if ((zeta.c0 | zeta.c1) == 0 || (g_zeta.c0 | g_zeta.c1) == 0)
+    return ctx->fail(LCP2_E_INVALID, "lcp2_fri_open: zeta = 0 is not supported (the opening divides by powers of zeta and of g zeta)");
   const auto oracles = c->oracles();
   memset(proof + L.op_constants, 0, (L.total - L.op_constants) * 8);
   // the power tables of zeta and g zeta (device-made), every oracle's columns evaluated back to back, ONE copy back

@@ -379,7 +379,12 @@ typedef struct {
 } lcp2_challenger;
 /* ch: state after observing the quotient cap and drawing zeta; updated to the state after the query indices were
  * drawn.  proof: a buffer of lcp2_proof_words(); words from the openings to the end are written (the three caps in
- * front of them are the caller's). */
+ * front of them are the caller's).
+ * zeta: any two u64 (reduced mod p), except zeta = 0: the division by X - zeta and by X - g zeta is done with tables of the
+ * inverse powers of zeta and of g zeta, and g zeta = 0 is the same condition.  lcp2_fri_open and lcp2_fri_open_begin return
+ * LCP2_E_INVALID for it (lcp2_last_error says why), and so does lcp2_prove if the transcript ever draws it (probability 2^-128);
+ * the handle stays as it was, ready for the same call with another zeta.  Every other zeta is taken: a zero component, a point
+ * of the subgroup H or of the LDE coset, g zeta = 1. */
 int lcp2_fri_open(lcp2_circuit *c, const uint64_t zeta[2], lcp2_challenger *ch, uint64_t *proof);
 
 /* lcp2_fri_open in its three phases (lcp2_fri_open is their composition, one code path), for callers that need the points

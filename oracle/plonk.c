@@ -423,17 +423,20 @@ static uint64_t *subgroup_table(unsigned lg) {
 }
 
 /* wires_permutation_partial_products_and_zs for every challenge; output polys (values on H), column-major:
- * [Z_0 .. Z_{CH-1}, pp_{0,0..npp-1}, pp_{1,0..npp-1}, ...] */
-static uint64_t *partial_products_and_zs(const orc_circuit *c, const uint64_t *wires, const uint64_t *betas, const uint64_t *gammas) {
+ * [Z_0 .. Z_{CH-1}, pp_{0,0..npp-1}, pp_{1,0..npp-1}, ...].  *zero_den (nullable) is set when a denominator w + beta sigma + gamma
+ * is zero: plonky2 panics there (batch_multiplicative_inverse of a zero), gl_inv maps it to 0 without a word. */
+static uint64_t *partial_products_and_zs(const orc_circuit *c, const uint64_t *wires, const uint64_t *betas, const uint64_t *gammas,
+                                         int *zero_den) {
   const orc_params *p = &c->p;
   size_t n = c->n, NR = p->num_routed_wires, NC = p->num_constants, CH = p->num_challenges, Q = p->quotient_degree_factor;
   size_t nchunks = (NR + Q - 1) / Q, npp = nchunks - 1;
   uint64_t *out = (uint64_t *)xmalloc(CH * (1 + npp) * n * 8);
   uint64_t *sub = subgroup_table(p->degree_bits);
   uint64_t *qc = (uint64_t *)xmalloc(n * nchunks * 8); /* quotient chunk products per row */
+  int zd = 0;
   for (size_t ch = 0; ch < CH; ch++) {
     uint64_t beta = betas[ch], gamma = gammas[ch];
-#pragma omp parallel for schedule(static)
+#pragma omp parallel for schedule(static) reduction(| : zd)
     for (size_t i = 0; i < n; i++) {
       uint64_t x = sub[i];
       for (size_t k = 0; k < nchunks; k++) {
@@ -442,6 +445,7 @@ static uint64_t *partial_products_and_zs(const orc_circuit *c, const uint64_t *w
           uint64_t wv = gl_canon(wires[j * n + i]);
           uint64_t num = gl_add(gl_add(wv, gl_mul(beta, gl_mul(c->k_is[j], x))), gamma);
           uint64_t den = gl_add(gl_add(wv, gl_mul(beta, c->cs_values[(NC + j) * n + i])), gamma);
+          zd |= den == 0;
           prod = gl_mul(prod, gl_mul(num, gl_inv(den)));
         }
         qc[i * nchunks + k] = prod;
@@ -460,6 +464,7 @@ static uint64_t *partial_products_and_zs(const orc_circuit *c, const uint64_t *w
     }
   }
   free(sub); free(qc);
+  if (zero_den) *zero_den = zd;
   return out;
 }
 
@@ -586,7 +591,15 @@ static uint64_t fri_proof_of_work(challenger *ch, unsigned pow_bits) {
 }
 
 /* ------------------------------------------------------------------ prove */
-int orc_prove(const orc_circuit *cc, const uint64_t *wires_in, const uint64_t *pis_in, uint64_t *proof) {
+/* The value a challenge takes after its draw: the transcript's own, or the caller's (reduced mod p) when `bit` of mask is set.
+ * The draw itself always happens, so the transcript is the same sequence of observe / get either way. */
+static uint64_t challenge(uint64_t drawn, uint32_t mask, uint32_t bit, const uint64_t *forced, size_t k) {
+  return (mask & bit) ? gl_canon(forced[k]) : drawn;
+}
+
+/* orc_prove (mask 0, forced unused) and orc_prove_forced */
+static int prove_impl(const orc_circuit *cc, const uint64_t *wires_in, const uint64_t *pis_in, const orc_challenges *forced, uint32_t mask,
+                      uint64_t *proof) {
   orc_circuit *c = (orc_circuit *)cc; /* only `last` is written */
   if (!c->cs) return ORC_E_NOT_BUILT; /* verifier-only or unbuilt circuit */
   const orc_params *p = &c->p;
@@ -612,16 +625,18 @@ int orc_prove(const orc_circuit *cc, const uint64_t *wires_in, const uint64_t *p
   ch_observe_n(&ch, c->digest, 4);
   ch_observe_n(&ch, pi_hash, 4);
   ch_observe_n(&ch, wb->tree->cap, L.capw);
-  uint64_t betas[4], gammas[4], alphas[4];
-  for (size_t k = 0; k < CH; k++) betas[k] = ch_get(&ch);
-  for (size_t k = 0; k < CH; k++) gammas[k] = ch_get(&ch);
+  uint64_t betas[4] = {0, 0, 0, 0}, gammas[4] = {0, 0, 0, 0}, alphas[4] = {0, 0, 0, 0};
+  for (size_t k = 0; k < CH; k++) betas[k] = challenge(ch_get(&ch), mask, ORC_FORCE_BETAS, forced ? forced->betas : NULL, k);
+  for (size_t k = 0; k < CH; k++) gammas[k] = challenge(ch_get(&ch), mask, ORC_FORCE_GAMMAS, forced ? forced->gammas : NULL, k);
 
-  uint64_t *zs_vals = partial_products_and_zs(c, wires, betas, gammas);
+  int zero_den = 0;
+  uint64_t *zs_vals = partial_products_and_zs(c, wires, betas, gammas, mask ? &zero_den : NULL);
+  if (zero_den) { free(zs_vals); free(pis); free(wires); batch_free(wb); return ORC_E_ZERO_DENOMINATOR; }
   orc_batch *zb = batch_from_values(zs_vals, CH * (1 + npp), p->degree_bits, p->rate_bits, p->cap_height);
   free(zs_vals);
   memcpy(proof + L.zs_cap, zb->tree->cap, L.capw * 8);
   ch_observe_n(&ch, zb->tree->cap, L.capw);
-  for (size_t k = 0; k < CH; k++) alphas[k] = ch_get(&ch);
+  for (size_t k = 0; k < CH; k++) alphas[k] = challenge(ch_get(&ch), mask, ORC_FORCE_ALPHAS, forced ? forced->alphas : NULL, k);
 
   int qstatus = 0;
   uint64_t *qchunks = quotient_chunks(c, wb, zb, pi_hash, betas, gammas, alphas, &qstatus);
@@ -630,6 +645,7 @@ int orc_prove(const orc_circuit *cc, const uint64_t *wires_in, const uint64_t *p
   memcpy(proof + L.quot_cap, qb->tree->cap, L.capw * 8);
   ch_observe_n(&ch, qb->tree->cap, L.capw);
   gl2_t zeta = ch_get_ext(&ch);
+  if (mask & ORC_FORCE_ZETA) zeta = gl2_make(gl_canon(forced->zeta[0]), gl_canon(forced->zeta[1]));
   gl2_t g_zeta = gl2_scale(zeta, gl_root_of_unity(p->degree_bits));
 
   /* OpeningSet::new */
@@ -767,6 +783,15 @@ int orc_prove(const orc_circuit *cc, const uint64_t *wires_in, const uint64_t *p
   return 0;
 }
 
+int orc_prove(const orc_circuit *c, const uint64_t *wires, const uint64_t *pis, uint64_t *proof) {
+  return prove_impl(c, wires, pis, NULL, 0, proof);
+}
+int orc_prove_forced(const orc_circuit *c, const uint64_t *wires, const uint64_t *pis, const orc_challenges *forced, uint32_t mask,
+                     uint64_t *proof) {
+  if ((mask & ~ORC_FORCE_ALL) || (mask && !forced)) return ORC_E_INTERNAL;
+  return prove_impl(c, wires, pis, forced, mask, proof);
+}
+
 /* ------------------------------------------------------------------ verify */
 static gl2_t rd2(const uint64_t *p) { return gl2_make(p[0], p[1]); }
 
@@ -798,7 +823,7 @@ static gl2_t fri_compute_evaluation(uint64_t x, size_t x_index_within_coset, uns
 
 /* codes: 1 encoding, 2 proof of work, 3 vanishing identity, 4 initial Merkle proof, 5 FRI consistency,
  * 6 FRI layer Merkle proof, 7 final polynomial */
-int orc_verify(const orc_circuit *c, const uint64_t *proof, const uint64_t *pis_in) {
+static int verify_impl(const orc_circuit *c, const uint64_t *proof, const uint64_t *pis_in, const orc_challenges *forced, uint32_t mask) {
   const orc_params *p = &c->p;
   size_t n = c->n, N = n << p->rate_bits, W = p->num_wires, NR = p->num_routed_wires, NC = p->num_constants, CH = p->num_challenges,
          Q = p->quotient_degree_factor;
@@ -820,12 +845,13 @@ int orc_verify(const orc_circuit *c, const uint64_t *proof, const uint64_t *pis_
   ch_observe_n(&ch, pi_hash, 4);
   ch_observe_n(&ch, proof + L.wires_cap, L.capw);
   uint64_t betas[4], gammas[4], alphas[4];
-  for (size_t k = 0; k < CH; k++) betas[k] = ch_get(&ch);
-  for (size_t k = 0; k < CH; k++) gammas[k] = ch_get(&ch);
+  for (size_t k = 0; k < CH; k++) betas[k] = challenge(ch_get(&ch), mask, ORC_FORCE_BETAS, forced ? forced->betas : NULL, k);
+  for (size_t k = 0; k < CH; k++) gammas[k] = challenge(ch_get(&ch), mask, ORC_FORCE_GAMMAS, forced ? forced->gammas : NULL, k);
   ch_observe_n(&ch, proof + L.zs_cap, L.capw);
-  for (size_t k = 0; k < CH; k++) alphas[k] = ch_get(&ch);
+  for (size_t k = 0; k < CH; k++) alphas[k] = challenge(ch_get(&ch), mask, ORC_FORCE_ALPHAS, forced ? forced->alphas : NULL, k);
   ch_observe_n(&ch, proof + L.quot_cap, L.capw);
   gl2_t zeta = ch_get_ext(&ch);
+  if (mask & ORC_FORCE_ZETA) zeta = gl2_make(gl_canon(forced->zeta[0]), gl_canon(forced->zeta[1]));
   ch_observe_n(&ch, proof + L.op_constants, 2 * (NC + NR + W));
   ch_observe_n(&ch, proof + L.op_zs, 2 * CH);
   ch_observe_n(&ch, proof + L.op_pp, 2 * CH * npp);
@@ -940,4 +966,9 @@ int orc_verify(const orc_circuit *c, const uint64_t *proof, const uint64_t *pis_
 done:
   free(pis); free(ow); free(oc);
   return rc;
+}
+int orc_verify(const orc_circuit *c, const uint64_t *proof, const uint64_t *pis) { return verify_impl(c, proof, pis, NULL, 0); }
+int orc_verify_forced(const orc_circuit *c, const uint64_t *proof, const uint64_t *pis, const orc_challenges *forced, uint32_t mask) {
+  if ((mask & ~ORC_FORCE_ALL) || (mask && !forced)) return 1;
+  return verify_impl(c, proof, pis, forced, mask);
 }

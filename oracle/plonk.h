@@ -61,7 +61,8 @@ size_t orc_proof_words(const orc_params *p);
 /* wires: column-major [num_wires][n] witness values.  0 on success, otherwise one of: */
 #define ORC_E_NOT_BUILT (-1)        /* verifier-only or unbuilt circuit */
 #define ORC_E_QUOTIENT_DEGREE (-2)  /* the quotient has non-zero coefficients at or above quotient_degree_factor * n: plonky2's trim_to_len panics */
-#define ORC_E_INTERNAL (-3)         /* self-check: the quotient-domain values are not rows of the committed LDE */
+#define ORC_E_INTERNAL (-3)         /* self-check: the quotient-domain values are not rows of the committed LDE (or a bad mask) */
+#define ORC_E_ZERO_DENOMINATOR (-4) /* orc_prove_forced only: a denominator w + beta sigma + gamma of the permutation argument is zero (plonky2 panics) */
 int orc_prove(const orc_circuit *c, const uint64_t *wires, const uint64_t *public_inputs, uint64_t *proof);
 /* 0 = accepted; otherwise a positive code naming the failed check */
 int orc_verify(const orc_circuit *c, const uint64_t *proof, const uint64_t *public_inputs);
@@ -75,6 +76,23 @@ typedef struct {
   uint64_t query_indices[64];
 } orc_challenges;
 void orc_last_challenges(const orc_circuit *c, orc_challenges *out);
+
+/* The same prover and verifier with some plonk challenges chosen by the caller.  The transcript runs as in orc_prove / orc_verify
+ * (every challenge is still drawn); for each bit of `mask` the drawn values of that kind are then replaced by forced->betas /
+ * gammas / alphas [0, num_challenges) or forced->zeta, reduced mod p.  The FRI alpha and betas, the proof of work and the query
+ * indices stay transcript-derived; the other fields of `forced` are not read.  mask 0 is orc_prove / orc_verify.
+ * orc_last_challenges reports the values used.  orc_prove_forced returns ORC_E_ZERO_DENOMINATOR where plonky2 would panic on a
+ * zero denominator of the permutation argument.  orc_verify_forced divides by n (zeta - 1), x - zeta and x - g zeta like the verifier
+ * it is: its verdict means something only for zeta outside H and outside the LDE coset. */
+#define ORC_FORCE_BETAS 1u
+#define ORC_FORCE_GAMMAS 2u
+#define ORC_FORCE_ALPHAS 4u
+#define ORC_FORCE_ZETA 8u
+#define ORC_FORCE_ALL 15u
+int orc_prove_forced(const orc_circuit *c, const uint64_t *wires, const uint64_t *public_inputs, const orc_challenges *forced,
+                     uint32_t mask, uint64_t *proof);
+int orc_verify_forced(const orc_circuit *c, const uint64_t *proof, const uint64_t *public_inputs, const orc_challenges *forced,
+                      uint32_t mask);
 
 #ifdef __cplusplus
 }

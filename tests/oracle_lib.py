@@ -9,6 +9,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ODIR = os.path.join(ROOT, "oracle")
 P = 0xFFFFFFFF00000001
 E_QUOTIENT_DEGREE = -2  # ORC_E_QUOTIENT_DEGREE (oracle/plonk.h): plonky2's trim_to_len(Q n) would panic
+E_ZERO_DENOMINATOR = -4  # ORC_E_ZERO_DENOMINATOR: a zero denominator in the permutation argument under forced challenges
+FORCE_BETAS, FORCE_GAMMAS, FORCE_ALPHAS, FORCE_ZETA = 1, 2, 4, 8  # ORC_FORCE_*
 c = ctypes
 u64p = c.POINTER(c.c_uint64)
 
@@ -66,6 +68,8 @@ def load():
         "orc_proof_words": (c.c_size_t, [V]),
         "orc_prove": (c.c_int, [V, V, V, V]),
         "orc_verify": (c.c_int, [V, V, V]),
+        "orc_prove_forced": (c.c_int, [V, V, V, V, c.c_uint32, V]),
+        "orc_verify_forced": (c.c_int, [V, V, V, V, c.c_uint32]),
         "orc_check_witness": (c.c_size_t, [V, V, V, V]),
         "orc_last_challenges": (None, [V, V]),
         "orc_gl_mul": (c.c_uint64, [c.c_uint64, c.c_uint64]),
@@ -197,6 +201,31 @@ class OracleCircuit:
     def verify(self, proof, pis):
         return self.L.orc_verify(self.h, vp(np.ascontiguousarray(proof, dtype=np.uint64)), vp(np.ascontiguousarray(pis, dtype=np.uint64)))
 
+    @staticmethod
+    def _forced(betas, gammas, alphas, zeta):
+        """(orc_challenges, mask) of the kinds that are given; any u64 is taken (the oracle reduces mod p)"""
+        ch, mask = OracleChallenges(), 0
+        for bit, name, vals in ((FORCE_BETAS, "betas", betas), (FORCE_GAMMAS, "gammas", gammas), (FORCE_ALPHAS, "alphas", alphas),
+                                (FORCE_ZETA, "zeta", zeta)):
+            if vals is not None:
+                mask |= bit
+                for k, v in enumerate(vals):
+                    getattr(ch, name)[k] = int(v)
+        return ch, mask
+
+    def prove_forced(self, wires, pis, betas=None, gammas=None, alphas=None, zeta=None):
+        """(status of orc_prove_forced, proof): the challenges that are given replace the transcript's after their draw"""
+        ch, mask = self._forced(betas, gammas, alphas, zeta)
+        proof = np.zeros(self.proof_words, dtype=np.uint64)
+        rc = self.L.orc_prove_forced(self.h, vp(np.ascontiguousarray(wires, dtype=np.uint64)), vp(np.ascontiguousarray(pis, dtype=np.uint64)),
+                                     c.byref(ch), mask, vp(proof))
+        return rc, proof
+
+    def verify_forced(self, proof, pis, betas=None, gammas=None, alphas=None, zeta=None):
+        ch, mask = self._forced(betas, gammas, alphas, zeta)
+        return self.L.orc_verify_forced(self.h, vp(np.ascontiguousarray(proof, dtype=np.uint64)), vp(np.ascontiguousarray(pis, dtype=np.uint64)),
+                                        c.byref(ch), mask)
+
     def digest(self):
         d = np.zeros(4, dtype=np.uint64)
         cap = np.zeros((1 << self.params.cap_height, 4), dtype=np.uint64)
@@ -212,3 +241,64 @@ class OracleCircuit:
         if self.h:
             self.L.orc_circuit_free(self.h)
             self.h = None
+
+
+class Challenger:
+    """Challenger<F, PoseidonHash> on the oracle's permutation: the transcript a plonky2 fork keeps on its own side
+    when it binds the seams one by one."""
+    P = (1 << 64) - (1 << 32) + 1
+
+    def __init__(self, oracle):
+        self.o, self.s, self.inp, self.out = oracle, np.zeros(12, dtype=np.uint64), [], []
+
+    def observe(self, xs):
+        for x in np.asarray(xs, dtype=np.uint64).ravel():
+            self.out = []
+            self.inp.append(int(x) % self.P)
+            if len(self.inp) == 8:
+                self._duplex()
+
+    def _duplex(self):
+        for i, v in enumerate(self.inp):
+            self.s[i] = v
+        self.inp = []
+        self.o.orc_poseidon_permute(vp(self.s))
+        self.out = [int(v) for v in self.s[:8]]
+
+    def get(self, k=1):
+        r = []
+        for _ in range(k):
+            if self.inp or not self.out:
+                self._duplex()
+            r.append(self.out.pop())
+        return np.array(r, dtype=np.uint64)
+
+    def state(self, m):
+        st = m.binding.ChallengerState()
+        for i in range(12):
+            st.sponge[i] = int(self.s[i])
+        for i, v in enumerate(self.inp):
+            st.input[i] = v
+        for i, v in enumerate(self.out):
+            st.output[i] = v
+        st.input_len, st.output_len = len(self.inp), len(self.out)
+        return st
+
+
+def proof_sections(m, params):
+    """(name, start) pairs of the flat proof for readable mismatch reports"""
+    lib = m.load_library()
+    total = lib.lcp2_proof_words(c.byref(params))
+    capw = 4 << params.cap_height
+    names = [("wires_cap", 0), ("zs_cap", capw), ("quotient_cap", 2 * capw), ("openings", 3 * capw)]
+    return names, total
+
+
+def first_mismatch(m, params, a, b):
+    names, total = proof_sections(m, params)
+    bad = np.nonzero(a != b)[0]
+    if bad.size == 0:
+        return None
+    pos = int(bad[0])
+    sec = [n for n, s in names if s <= pos][-1]
+    return f"first mismatch at word {pos} of {total} (in or after section {sec}); {bad.size} words differ"

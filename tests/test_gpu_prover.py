@@ -6,28 +6,9 @@ import numpy as np
 import pytest
 
 import oracle_lib
+from oracle_lib import Challenger as _Challenger, first_mismatch as _first_mismatch
 
 pytestmark = pytest.mark.gpu
-
-
-def _sections(m, params):
-    """(name, start) pairs of the flat proof for readable mismatch reports"""
-    import ctypes
-    lib = m.load_library()
-    total = lib.lcp2_proof_words(ctypes.byref(params))
-    capw = 4 << params.cap_height
-    names = [("wires_cap", 0), ("zs_cap", capw), ("quotient_cap", 2 * capw), ("openings", 3 * capw)]
-    return names, total
-
-
-def _first_mismatch(m, params, a, b):
-    names, total = _sections(m, params)
-    bad = np.nonzero(a != b)[0]
-    if bad.size == 0:
-        return None
-    pos = int(bad[0])
-    sec = [n for n, s in names if s <= pos][-1]
-    return f"first mismatch at word {pos} of {total} (in or after section {sec}); {bad.size} words differ"
 
 
 # 14-16: the LDE (2^17 .. 2^19 points) and the quotient iNTT run as two passes (strided + contiguous), the FRI schedule has
@@ -405,48 +386,6 @@ def test_large_proof_verifies(gpu_ctx):
     with pytest.raises(m.ProofRejected):
         data.verify(proof, wrong)
     data.close()
-
-
-class _Challenger:
-    """Challenger<F, PoseidonHash> on the oracle's permutation: the transcript a plonky2 fork keeps on its own side
-    when it binds the seams one by one."""
-    P = (1 << 64) - (1 << 32) + 1
-
-    def __init__(self, oracle):
-        self.o, self.s, self.inp, self.out = oracle, np.zeros(12, dtype=np.uint64), [], []
-
-    def observe(self, xs):
-        for x in np.asarray(xs, dtype=np.uint64).ravel():
-            self.out = []
-            self.inp.append(int(x) % self.P)
-            if len(self.inp) == 8:
-                self._duplex()
-
-    def _duplex(self):
-        for i, v in enumerate(self.inp):
-            self.s[i] = v
-        self.inp = []
-        self.o.orc_poseidon_permute(oracle_lib.vp(self.s))
-        self.out = [int(v) for v in self.s[:8]]
-
-    def get(self, k=1):
-        r = []
-        for _ in range(k):
-            if self.inp or not self.out:
-                self._duplex()
-            r.append(self.out.pop())
-        return np.array(r, dtype=np.uint64)
-
-    def state(self, m):
-        st = m.binding.ChallengerState()
-        for i in range(12):
-            st.sponge[i] = int(self.s[i])
-        for i, v in enumerate(self.inp):
-            st.input[i] = v
-        for i, v in enumerate(self.out):
-            st.output[i] = v
-        st.input_len, st.output_len = len(self.inp), len(self.out)
-        return st
 
 
 def test_staged_seams_compose_to_prove(gpu_ctx, oracle):
