@@ -166,6 +166,8 @@ def load_library():
         "lcp2_quotient_commit": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_verify": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_int)]),
         "lcp2_last_challenges": (c.c_int, [c.c_void_p, c.c_void_p]),
+        "lcp2_gate_program_degree": (c.c_int, [c.c_void_p, c.c_size_t, c.c_uint32, c.POINTER(c.c_uint32)]),
+        "lcp2_circuit_gate_tiers": (c.c_int, [c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p]),
         "lcp2_proof_bytes": (c.c_size_t, [c.POINTER(Params), c.c_size_t, c.c_uint32]),
         "lcp2_proof_to_bytes": (c.c_int, [c.POINTER(Params), c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_uint32, c.c_void_p, c.c_size_t]),
         "lcp2_proof_from_bytes": (c.c_int, [c.POINTER(Params), c.c_void_p, c.c_size_t, c.c_uint32, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]),
@@ -762,6 +764,14 @@ class CircuitData:
         self._check(self.lib.lcp2_last_challenges(self.handle, _ptr(out)))
         return {"betas": out[0:4], "gammas": out[4:8], "alphas": out[8:12], "zeta": out[12:14], "fri_alpha": out[14:16],
                 "fri_betas": out[16:32].reshape(8, 2), "pow_witness": int(out[32]), "query_indices": out[33:97]}
+
+    def gate_tiers(self):
+        """(degrees, bundles) per gate: the degree bound derived from the gate's program, and the bundle with which K6 evaluates the
+        gate on half of the quotient coset (-1: on the whole coset)"""
+        ng = len(self.circ.gateset.gates)
+        deg, bun = np.zeros(ng, dtype=np.uint32), np.zeros(ng, dtype=np.int32)
+        self._check(self.lib.lcp2_circuit_gate_tiers(self.handle, ng, _ptr(deg), _ptr(bun)))
+        return deg, bun
 
     def close(self):
         if self.handle:

@@ -29,6 +29,9 @@ struct lcp2_circuit {
   uint32_t npi = 0, num_selectors = 0, num_regs = 1, dev_regs = 1;
   std::vector<lcp2::GateDev> dev_gates;  // the gate table as uploaded: offsets into the staged code
   std::vector<lcp2_gate> gates;
+  std::vector<uint32_t> gate_degree;     // per gate: the degree bound of its constraints, derived from its program (prover_build.hip)
+  lcp2::QuotientTiers tiers;             // K6: the bundles of low-degree gates evaluated on half of the quotient coset (none: all on the full tier)
+  DevBuf d_half_mask, tier_planes;       // [num_gates] bundle masks; [bundles][CH][2^q n] plane values, first half computed, second half extended
   std::vector<uint32_t> code;
   std::vector<u64> imm, k_is;
   u64 digest[4] = {0, 0, 0, 0};
@@ -192,6 +195,7 @@ int queue_perm_wrap(Download &d, lcp2_circuit *c);
 int perm_finish(lcp2_circuit *c, const u64 *prefix);
 int perm_commit(lcp2_circuit *c, u64 *cap_out, bool with_wrap = false);
 int stage_perm_zs(lcp2_circuit *c, const u64 *betas, const u64 *gammas, u64 *cap_out);
+int tier_extend(lcp2_circuit *c, NttHost<DeviceNttBackend> &ntt);
 int stage_quotient_values(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash, bool defer_check = false);
 int stage_quotient_commit(lcp2_circuit *c, u64 *cap_out);
 int stage_quotient(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash, u64 *cap_out);

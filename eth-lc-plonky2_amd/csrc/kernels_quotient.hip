@@ -6,6 +6,7 @@
 //
 // The LDE matrices are indexed in their storage (= Merkle leaf) order, so all column reads are coalesced 512-byte runs per wave;
 // the only gathers are the two Z(g x) values per point in k_q_perm.
+#include <algorithm>
 #include "kernels_gates.hpp"
 
 namespace lcp2 {
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(QUOTIENT_THREADS, 2) void k_q_perm(QuotientArgs a, 
 // ArithmeticGate and BaseSumGate<2> of one circuit in one walk over the wires (both read the routed wires from index 0 up: the
 // wires are loaded once, 16 at a time from the top, and feed both evaluators; same constraint order as q_arithmetic_native and
 // q_base_sum2_native, so the sums are the same field elements)
-__device__ __forceinline__ void q_arith_base_pair(const QuotientArgs &a, u64 i, const GateDev &GA, const GateDev &GB, u64 valA[QUOTIENT_MAX_CH], u64 valB[QUOTIENT_MAX_CH]) {
+__device__ __forceinline__ void q_arith_base_pair(const QuotientArgs &a, u64 i, u32 gA, u32 gB, const GateDev &GA, const GateDev &GB, u64 valA[QUOTIENT_MAX_CH], u64 valB[QUOTIENT_MAX_CH]) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const u32 CH = a.num_challenges;
   QEmit eA, eB;
@@ -418,7 +419,7 @@ __device__ __forceinline__ void q_arith_base_pair(const QuotientArgs &a, u64 i, 
   }
   eB.term(a, 0, gl_sub(sum, w0));
   eA.finish_terms(); eB.finish_terms();
-  const u64 fA = q_filter(a, GA, i), fB = q_filter(a, GB, i);
+  const u64 fA = q_filter(a, gA, GA, i), fB = q_filter(a, gB, GB, i);
 #pragma unroll
   for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
     if (c < CH) { valA[c] = gl_mul(fA, eA.acc[c]); valB[c] = gl_mul(fB, eB.acc[c]); }
@@ -457,7 +458,7 @@ __global__ __launch_bounds__(QUOTIENT_THREADS, 2) void k_q_light(QuotientArgs a,
     }
     if (run) {
       u64 va[QUOTIENT_MAX_CH], vb[QUOTIENT_MAX_CH];
-      q_arith_base_pair(a, i, GA, GB, va, vb);
+      q_arith_base_pair(a, i, L.g[ka], L.g[kb], GA, GB, va, vb);
 #pragma unroll
       for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
         if (c < a.num_challenges) sum[c] = gl_add(va[c], vb[c]);
@@ -506,8 +507,9 @@ bool is_light(const GateDev &G) {
   const u32 k = G.flags & LCP2_GATE_NATIVE_MASK;
   return k == 0 || k == LCP2_GATE_NATIVE_ARITHMETIC || k == LCP2_GATE_NATIVE_BASE_SUM2;
 }
+// tier (nullable): only the gates g with tier[g] == want (the full tier is -1, a bundle its index); nullptr: every gate
 template <bool CHECK>
-u32 launch_gates(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, unsigned long long *flag) {
+u32 launch_gates(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, unsigned long long *flag, const int *tier = nullptr, int want = -1) {
   u32 launched = 0;
   LightGates L{};
   auto flush = [&] {
@@ -517,7 +519,7 @@ u32 launch_gates(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev
     L.count = 0;
   };
   for (u32 g = 0; g < host_gates.size(); g++) {
-    if (host_gates[g].num_constraints == 0) continue;
+    if (host_gates[g].num_constraints == 0 || (tier && tier[g] != want)) continue;
     if (is_light(host_gates[g])) {
       L.g[L.count++] = g;
       if (L.count == 8) flush();
@@ -534,7 +536,63 @@ u32 launch_gates(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev
 // host_gates: the gate table as uploaded (staged code offsets); gates without constraints are skipped
 void launch_quotient(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates) {
   const u32 launched = launch_gates<false>(s, a, host_gates, nullptr);
-  hipLaunchKernelGGL(k_q_perm, q_grid(a), dim3(QUOTIENT_THREADS), 0, s, a, launched ? 1u : 0u);
+  launch_quotient_perm(s, a, launched ? 1u : 0u);
+}
+void launch_quotient_perm(hipStream_t s, const QuotientArgs &a, u32 have_gates) {
+  hipLaunchKernelGGL(k_q_perm, q_grid(a), dim3(QUOTIENT_THREADS), 0, s, a, have_gates);
+}
+u32 launch_quotient_full_tier(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, const QuotientTiers &t) {
+  return launch_gates<false>(s, a, host_gates, nullptr, t.bundle_of.data(), -1);
+}
+void launch_quotient_half_tier(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, const QuotientTiers &t, u64 *planes) {
+  for (size_t b = 0; b < t.bundles.size(); b++) {  // the first launch of a bundle stores its planes, the others accumulate
+    QuotientArgs ab = a;
+    ab.out = planes + (u64)b * a.num_challenges * a.N;
+    launch_gates<false>(s, ab, host_gates, nullptr, t.bundle_of.data(), (int)b);
+  }
+}
+
+// Half tier, last step: the planes of up to 8 bundles (extended to the whole coset) times what their gates' filters left out
+struct TierCombine { u32 count; u32 selector_index[8], group_start[8], group_end[8]; u64 mask[8]; };
+__global__ __launch_bounds__(256) void k_q_tier_combine(QuotientArgs a, const u64 *__restrict__ planes, TierCombine T, u32 accumulate) {
+  const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.count) return;
+  const u32 CH = a.num_challenges;
+  const u64 ig = a.leaf0 + i;
+  u64 acc[QUOTIENT_MAX_CH];
+#pragma unroll
+  for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) acc[c] = (c < CH && accumulate) ? a.out[(u64)c * a.N + ig] : 0;
+  for (u32 b = 0; b < T.count; b++) {
+    const u32 gs = T.group_start[b], ge = T.group_end[b];
+    const u64 mask = T.mask[b];
+    const u64 s = a.consts[(u64)T.selector_index[b] * a.stride + i];
+    u64 v[QUOTIENT_MAX_CH];
+#pragma unroll
+    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) v[c] = c < CH ? planes[((u64)b * CH + c) * a.N + ig] : 0;
+    u64 f = 1;
+    for (u32 j = gs; j < ge; j++) {
+      const bool in_bundle = (mask >> ((j - gs) & 63)) & 1;  // groups of <= 64 values (form_bundles)
+      if (!in_bundle) f = gl_mul(f, gl_sub((u64)j, s));
+    }
+    if (a.num_selectors > 1) f = gl_mul(f, gl_sub(0xFFFFFFFFull, s));
+#pragma unroll
+    for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
+      if (c < CH) acc[c] = gl_add(acc[c], gl_mul(f, v[c]));
+  }
+#pragma unroll
+  for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
+    if (c < CH) a.out[(u64)c * a.N + ig] = acc[c];
+}
+void launch_tier_combine(hipStream_t s, const QuotientArgs &a, const QuotientTiers &t, const u64 *planes, u32 accumulate) {
+  for (size_t b0 = 0; b0 < t.bundles.size(); b0 += 8) {
+    TierCombine T{};
+    T.count = (u32)std::min<size_t>(8, t.bundles.size() - b0);
+    for (u32 k = 0; k < T.count; k++) {
+      const QuotientBundle &B = t.bundles[b0 + k];
+      T.selector_index[k] = B.selector_index; T.group_start[k] = B.group_start; T.group_end[k] = B.group_end; T.mask[k] = B.mask;
+    }
+    hipLaunchKernelGGL(k_q_tier_combine, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, s, a, planes + (u64)b0 * a.num_challenges * a.N, T, b0 ? 1u : accumulate);
+  }
 }
 void launch_gate_check(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, unsigned long long *flag) {
   launch_gates<true>(s, a, host_gates, flag);

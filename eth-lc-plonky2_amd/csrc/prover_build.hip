@@ -1,5 +1,7 @@
 // build(): lcp2_circuit_create and the verifier-only constructor, with the checks both make of a circuit description, and the
 // accessors of what build() leaves in the handle (digest, cap, proof size, the verifier's view).
+#include <algorithm>
+#include <cstdlib>
 #include "circuit_state.hpp"
 
 using namespace lcp2;
@@ -88,6 +90,72 @@ const char *validate_programs(const lcp2_circuit_desc *d) {
   return nullptr;
 }
 
+// Degree bound of a gate's constraints in the wire and constant polynomials (each of degree < n), propagated through the
+// straight-line program: a WIRE / CONST operand is 1, IMM / PI 0, a register what was last written to it.  Saturates at DEGREE_CAP.
+constexpr u32 DEGREE_CAP = 1u << 20;
+u32 program_degree(const uint32_t *code, size_t first, size_t len, size_t nregs) {
+  std::vector<u32> reg(std::max<size_t>(nregs, 1), 0);
+  auto cap = [](u64 d) { return (u32)std::min<u64>(d, DEGREE_CAP); };
+  u32 deg = 0;
+  for (size_t pc = first; pc < first + len; pc++) {
+    const Insn in(code[2 * pc], code[2 * pc + 1]);
+    if (in.op == LCP2_OP_PMDS) {  // a linear map of the source window plus constants
+      u32 m = 0;
+      for (u32 r = 0; r < 12; r++) m = std::max(m, reg[in.idx[0] + r]);
+      for (u32 r = 0; r < 12; r++) reg[in.dst + r] = m;
+      continue;
+    }
+    auto of = [&](int k) { return in.kind[k] == 0 ? reg[in.idx[k]] : (in.kind[k] == 1 || in.kind[k] == 2) ? 1u : 0u; };
+    const u32 x = of(0);
+    switch (in.op) {
+      case LCP2_OP_EMIT: deg = std::max(deg, x); break;
+      case LCP2_OP_EMITBOOL: deg = std::max(deg, cap(2ull * x)); break;
+      case LCP2_OP_SBOX: reg[in.dst] = cap(7ull * x); break;
+      case LCP2_OP_MUL: case LCP2_OP_XOR: reg[in.dst] = cap((u64)x + of(1)); break;
+      case LCP2_OP_MULADD: reg[in.dst] = std::max(reg[in.dst], cap((u64)x + of(1))); break;
+      default: reg[in.dst] = std::max(x, of(1)); break;  // ADD, SUB, DBLADD
+    }
+  }
+  return deg;
+}
+
+// The half tier of K6 (prover_kernels.hpp QuotientTiers), from the derived degrees alone.  Per selector group the gates of degree
+// <= 2^(q-1) are taken by falling degree and put first-fit into bundles with max degree + size - 1 <= 2^(q-1).
+void form_bundles(lcp2_circuit *c) {
+  QuotientTiers &t = c->tiers;
+  t.bundles.clear();
+  t.bundle_of.assign(c->gates.size(), -1);
+  const u32 qb = c->qbits();
+  if (qb == 0) return;
+  const u32 half = 1u << (qb - 1);
+  std::vector<u32> order;
+  for (u32 g = 0; g < c->gates.size(); g++) {
+    const lcp2_gate &G = c->gates[g];
+    if (G.num_constraints == 0 || c->gate_degree[g] > half) continue;
+    if (G.selector_value < G.group_start || G.selector_value >= G.group_end || G.group_end - G.group_start > 64) continue;  // the masks hold 64 values
+    order.push_back(g);
+  }
+  std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return c->gate_degree[x] > c->gate_degree[y]; });
+  std::vector<u32> maxdeg;
+  for (u32 g : order) {
+    const lcp2_gate &G = c->gates[g];
+    size_t b = 0;
+    for (; b < t.bundles.size(); b++) {
+      const QuotientBundle &B = t.bundles[b];
+      if (B.selector_index == G.selector_index && B.group_start == G.group_start && B.group_end == G.group_end &&
+          maxdeg[b] + B.gates.size() <= half && !((B.mask >> (G.selector_value - G.group_start)) & 1))
+        break;
+    }
+    if (b == t.bundles.size()) {
+      t.bundles.push_back(QuotientBundle{G.selector_index, G.group_start, G.group_end, 0, {}});
+      maxdeg.push_back(c->gate_degree[g]);  // falling degrees: the first gate of a bundle has the largest
+    }
+    t.bundles[b].gates.push_back(g);
+    t.bundles[b].mask |= 1ull << (G.selector_value - G.group_start);
+    t.bundle_of[g] = (int)b;
+  }
+}
+
 // circuit_builder.rs::build: circuit_digest = hash_no_pad(constants_sigmas_cap || domain_separator_digest || degree_bits) with
 // domain_separator_digest = hash_pad(domain separator), the separator empty unless the builder sets one: pad10*1 = [1, 0 x 6, 1]
 void circuit_digest(const std::vector<u64> &cs_cap, u32 degree_bits, u64 digest[4]) {
@@ -155,6 +223,9 @@ void copy_description(lcp2_circuit *c, const lcp2_circuit_desc *d) {
   for (size_t i = 0; i < d->num_imm; i++) c->imm[i] = gl_canon(d->imm[i]);
   c->k_is.resize(p.num_routed_wires);
   for (u32 i = 0; i < p.num_routed_wires; i++) c->k_is[i] = gl_canon(d->k_is[i]);
+  c->gate_degree.resize(c->gates.size());
+  for (size_t g = 0; g < c->gates.size(); g++) c->gate_degree[g] = program_degree(c->code.data(), c->gates[g].code_offset, c->gates[g].code_len, c->num_regs);
+  c->tiers.bundle_of.assign(c->gates.size(), -1);
 }
 
 int circuit_create(lcp2_ctx *ctx, const lcp2_circuit_desc *d, uint32_t bf, uint32_t bc, lcp2_circuit **out) {
@@ -249,6 +320,26 @@ int circuit_create(lcp2_ctx *ctx, const lcp2_circuit_desc *d, uint32_t bf, uint3
   LCP2_HIP(ctx, c->row_tot.alloc((size_t)CH * n * 8));
   LCP2_HIP(ctx, c->scan_tmp.alloc(std::max(scan_scratch_words(n, 4), (u64)16) * 8));
   LCP2_HIP(ctx, c->qvals.alloc((size_t)CH * NQ * 8));
+  {  // K6's half tier; LCP2_QUOTIENT_TIERS=0 in the environment keeps every gate on the full tier.  A sharded circuit evaluates
+     // its own leaf blocks only and has no coset prefix to halve.
+    const char *sw = getenv("LCP2_QUOTIENT_TIERS");
+    if (!c->sharded() && !(sw && sw[0] == '0' && !sw[1])) form_bundles(c.get());
+    if (c->tiers.on()) {
+      std::vector<u64> masks(c->gates.size(), 0);
+      for (const QuotientBundle &B : c->tiers.bundles)
+        for (u32 g : B.gates) masks[g] = B.mask;
+      LCP2_TRY(upload(ctx, c->d_half_mask, masks.data(), masks.size() * 8));
+      LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `masks` goes out of scope
+      LCP2_HIP(ctx, c->tier_planes.alloc(c->tiers.bundles.size() * (size_t)CH * NQ * 8));
+      // one extension of zeroed planes: the transforms' twiddle and shift tables and the coefficient buffer exist before the first proof
+      LCP2_HIP(ctx, hipMemsetAsync(c->tier_planes.p, 0, c->tiers.bundles.size() * (size_t)CH * NQ * 8, ctx->stream));
+      DeviceNttBackend be{ctx};
+      NttHost<DeviceNttBackend> ntt(be);
+      LCP2_TRY(tier_extend(c.get(), ntt));
+      if (be.status) return be.status;
+      LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+  }
   LCP2_HIP(ctx, c->planes.alloc((size_t)4 * n * 8));
   LCP2_HIP(ctx, c->small.alloc((SMALL_GATE_SCALE + (size_t)QUOTIENT_MAX_CH * d->num_gates + 8) * 8));
   {
@@ -339,6 +430,31 @@ extern "C" size_t lcp2_proof_words(const lcp2_params *p) {
   bool unsupported;
   if (!p || params_problem(*p, &unsupported)) return 0;  // the layout arithmetic relies on a sane FRI schedule
   return ProofLayout(*p).total;
+}
+extern "C" int lcp2_gate_program_degree(const uint32_t *code, size_t num_instructions, uint32_t num_regs, uint32_t *degree) {
+  if (!code || !degree || num_regs > 64) return LCP2_E_INVALID;
+  const size_t nregs = std::max(num_regs, 1u);
+  for (size_t pc = 0; pc < num_instructions; pc++) {  // what validate_programs checks of the registers
+    const Insn in(code[2 * pc], code[2 * pc + 1]);
+    if (in.op > LCP2_OP_PMDS) return LCP2_E_INVALID;
+    if (in.op == LCP2_OP_PMDS) {
+      if ((size_t)in.dst + 12 > nregs || (size_t)in.idx[0] + 12 > nregs) return LCP2_E_INVALID;
+      continue;
+    }
+    if (!in.emits() && in.dst >= nregs) return LCP2_E_INVALID;
+    for (int k = 0; k < in.nsrc(); k++)
+      if (in.kind[k] > 4 || (in.kind[k] == 0 && in.idx[k] >= nregs)) return LCP2_E_INVALID;
+  }
+  *degree = program_degree(code, 0, num_instructions, nregs);
+  return LCP2_OK;
+}
+extern "C" int lcp2_circuit_gate_tiers(const lcp2_circuit *c, uint32_t num_gates, uint32_t *degrees, int32_t *bundles) {
+  if (!c || num_gates != c->gates.size()) return LCP2_E_INVALID;
+  for (uint32_t g = 0; g < num_gates; g++) {
+    if (degrees) degrees[g] = c->gate_degree[g];
+    if (bundles) bundles[g] = c->tiers.bundle_of[g];
+  }
+  return LCP2_OK;
 }
 extern "C" int lcp2_last_challenges(const lcp2_circuit *c, uint64_t out[97]) {
   if (!c || !out) return LCP2_E_INVALID;

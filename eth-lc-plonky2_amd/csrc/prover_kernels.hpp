@@ -68,7 +68,11 @@ struct QuotientArgs {
   const u64 *gate_scale;   // [num_gates][QUOTIENT_MAX_CH] alpha^(num_constraints - 1)
   const u32 *code;
   const GateDev *gates;
-  u64 *out;           // [CH][N] quotient values, leaf order (always the full domain)
+  // half tier (QuotientTiers below): [num_gates], bit j - group_start set for the selector values j of the gate's bundle.  The filter
+  // is then the product over those values alone, without the unused-selector factor: k_q_tier_combine multiplies by the rest.
+  // nullptr: the whole filter.
+  const u64 *half_mask;
+  u64 *out;           // [CH][N] quotient values, leaf order (always the full domain); a half-tier launch: the bundle's planes
   u64 N;              // size of the LDE domain
   // coset-sharded circuits hold only the leaf blocks [leaf0, leaf0 + count) of every LDE: `stride` is the column stride of
   // wires / consts / zs (= count), l0 / points / out are indexed with the global leaf index.  Unsharded: 0, N, N.
@@ -114,6 +118,29 @@ void launch_quotient_combine(hipStream_t s, const u64 *in, u64 *out, const u64 *
 void launch_perm_chunks(hipStream_t s, const PermArgs &a);
 void launch_perm_finalize(hipStream_t s, const PermArgs &a);
 void launch_quotient(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates);
+// Half tier of K6.  A bundle B is a set of gates of one selector group with max_g deg(C_g) + |B| - 1 <= 2^(q-1): the polynomial
+//   P_B = sum_{g in B} prod_{j in B, j != g} (j - s) C_g   has degree < 2^(q-1) n,
+// so it is evaluated on the first half of the quotient coset only (the coset 7 H_{2^(q-1) n}, in its own leaf order), extended to
+// the other half by an iNTT and a coset NTT of that size, and enters the quotient values as
+//   prod_{j in group, j not in B} (j - s) * (unused-selector factor) * P_B   (k_q_tier_combine).
+struct QuotientBundle {
+  u32 selector_index, group_start, group_end;
+  u64 mask;                 // bit j - group_start: selector value j belongs to the bundle
+  std::vector<u32> gates;
+};
+struct QuotientTiers {
+  std::vector<QuotientBundle> bundles;  // empty: every gate on the full tier
+  std::vector<int> bundle_of;           // per gate: index into bundles, -1: full tier
+  bool on() const { return !bundles.empty(); }
+};
+// the pieces of launch_quotient for a circuit with a half tier; each returns / takes the number of launches that have written a.out
+// the gates of the full tier (bundle_of[g] < 0)
+u32 launch_quotient_full_tier(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, const QuotientTiers &t);
+// the bundles: a.count = half of the coset, a.half_mask set; bundle b accumulates into planes[(b * CH + c) * a.N + i]
+void launch_quotient_half_tier(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, const QuotientTiers &t, u64 *planes);
+// a.out[c][i] (+)= outer filter_b(i) * planes[b][c][i] over the whole coset
+void launch_tier_combine(hipStream_t s, const QuotientArgs &a, const QuotientTiers &t, const u64 *planes, u32 accumulate);
+void launch_quotient_perm(hipStream_t s, const QuotientArgs &a, u32 have_gates);
 // host: rewrites validated gate programs into the staged device form (new code, per-gate offsets in `gates`, column lists)
 void stage_gate_programs(const std::vector<uint32_t> &code, std::vector<GateDev> &gates, u32 num_wires, u32 num_selectors,
                          std::vector<uint32_t> &staged_code, std::vector<uint32_t> &stage_list);

@@ -191,6 +191,24 @@ int stage_perm_zs(lcp2_circuit *c, const u64 *betas, const u64 *gammas, u64 *cap
   return LCP2_OK;
 }
 
+// Half tier of K6: every plane [bundles * CH][NQ] holds its values on the first NQ / 2 leaves; fill the second half.  The
+// coefficients in between go through the quotient oracle's coefficient buffer (CH * NQ words = 2 CH half planes per batch): it
+// is not written before stage_quotient_commit and nothing reads the previous proof's once a new proof has reached K6.
+int tier_extend(lcp2_circuit *c, NttHost<DeviceNttBackend> &ntt) {
+  lcp2_ctx *ctx = c->ctx; const lcp2_params &p = c->p;
+  const u32 CH = p.num_challenges, lgNQ = p.degree_bits + c->qbits(), ncols = (u32)c->tiers.bundles.size() * CH, batch = 2 * CH;
+  const u64 NQ = 1ull << lgNQ;
+  LCP2_HIP(ctx, c->quot.coeffs.ensure((size_t)CH * NQ * 8));
+  const u64 second = gl_mul(GL_GENERATOR, gl_root_of_unity(lgNQ));  // the odd points of 7 H_NQ are the coset 7 w_NQ H_{NQ/2}
+  for (u32 first = 0; first < ncols; first += batch) {
+    const u32 k = std::min(batch, ncols - first);
+    u64 *pl = c->tier_planes.u() + (u64)first * NQ;
+    ntt.inverse_bitrev_in(pl, NQ, c->quot.coeffs.u(), NQ / 2, lgNQ - 1, k, GL_GENERATOR);
+    ntt.forward(c->quot.coeffs.u(), NQ / 2, pl + NQ / 2, NQ, lgNQ - 1, k, second, 0);
+  }
+  return LCP2_OK;
+}
+
 // compute_quotient_polys + commitment (K6, K1-K4)
 // defer_check: leave the gate-check verdict on the device; stage_quotient_commit reads it together with the quotient cap
 int stage_quotient_values(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash, bool defer_check) {
@@ -241,7 +259,21 @@ int stage_quotient_values(lcp2_circuit *c, const u64 *alphas, const u64 *pi_hash
     QuotientArgs h = a;
     h.wires = c->d_wires_cur; h.consts = c->rows_mode ? c->cs_rows.u() : c->cs_values.u(); h.leaf0 = 0; h.count = c->rows(); h.stride = c->rows();
     launch_gate_check(s, h, c->dev_gates, (unsigned long long *)(d_small + SMALL_CHECK));
-    launch_quotient(s, a, c->dev_gates);
+    if (!c->tiers.on()) {
+      launch_quotient(s, a, c->dev_gates);
+    } else {
+      // Half tier: the bundles' polynomials have degree < NQ / 2, so their values on the first NQ / 2 leaves (the coset 7 H_{NQ/2} in
+      // its own leaf order) fix them; the second half of the prefix is the coset 7 w_NQ H_{NQ/2}, again in leaf order.
+      u64 *planes = c->tier_planes.u();
+      QuotientArgs hq = a;
+      hq.count = NQ / 2; hq.half_mask = c->d_half_mask.u();
+      launch_quotient_half_tier(s, hq, c->dev_gates, c->tiers, planes);
+      LCP2_TRY(tier_extend(c, ntt));
+      if (e.be.status) return e.be.status;
+      const u32 launched = launch_quotient_full_tier(s, a, c->dev_gates, c->tiers);
+      launch_tier_combine(s, a, c->tiers, planes, launched ? 1u : 0u);  // before k_q_perm: it divides by Z_H
+      launch_quotient_perm(s, a, 1u);
+    }
   }
   LCP2_HIP(ctx, hipGetLastError());
   if (c->local_quotient()) {  // block b is the coset of shift g w_N^bitrev(b), its values in bit-reversed order: interpolate in place

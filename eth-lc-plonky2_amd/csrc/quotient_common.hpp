@@ -257,19 +257,22 @@ __device__ __forceinline__ void q_interpret(const QuotientArgs &a, const GateDev
     lds[dst * T + tid] = r;
   }
 }
-// filter_g(point): the selector polynomial of gate g's group with the factor of g's own value left out
-__device__ __forceinline__ u64 q_filter(const QuotientArgs &a, const GateDev &G, u64 i) {
+// filter_g(point): the selector polynomial of gate g's group with the factor of g's own value left out.  Half tier (a.half_mask):
+// the factors of g's bundle alone; the others and the unused-selector factor are k_q_tier_combine's.
+__device__ __forceinline__ u64 q_filter(const QuotientArgs &a, u32 g, const GateDev &G, u64 i) {
   const u64 s = a.consts[(u64)G.selector_index * a.stride + i];
+  const bool half = a.half_mask != nullptr;  // wave-uniform, like the mask
+  const u64 keep = half ? konst(a.half_mask)[g] : ~0ull;
   u64 f = 1;
   for (u32 j = G.group_start; j < G.group_end; j++)
-    if (j != G.selector_value) f = gl_mul(f, gl_sub((u64)j, s));
-  if (a.num_selectors > 1) f = gl_mul(f, gl_sub(0xFFFFFFFFull, s));
+    if (j != G.selector_value && ((keep >> ((j - G.group_start) & 63)) & 1)) f = gl_mul(f, gl_sub((u64)j, s));  // a mask: groups of <= 64 values only (form_bundles)
+  if (a.num_selectors > 1 && !half) f = gl_mul(f, gl_sub(0xFFFFFFFFull, s));
   return f;
 }
 __device__ __forceinline__ void q_gate_finish(const QuotientArgs &a, u32 g, const GateDev &G, u64 i, const QEmit &emit, u64 val[QUOTIENT_MAX_CH]) {
   const u32 CH = a.num_challenges;
   const bool fwd = (G.flags & LCP2_GATE_EMIT_FORWARD) != 0;
-  const u64 f = q_filter(a, G, i);
+  const u64 f = q_filter(a, g, G, i);
 #pragma unroll
   for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
     if (c < CH) {

@@ -508,6 +508,17 @@ int lcp2_verifier_create(const lcp2_circuit_desc *desc, const uint64_t digest[4]
 /* challenges of the last lcp2_prove (for stage-wise parity tests): betas[4], gammas[4], alphas[4], zeta[2],
  * fri_alpha[2], fri_betas[8][2], pow_witness, query_indices[64] -- 4+4+4+2+2+16+1+64 = 97 words */
 int lcp2_last_challenges(const lcp2_circuit *c, uint64_t out[97]);
+/* The degree bound the library derives from a gate program (`num_instructions` two-word instructions, registers below num_regs), in
+ * the wire and constant polynomials: WIRE / CONST count 1, IMM / PI 0; ADD, SUB, DBLADD take the larger operand, MUL and XOR the
+ * sum, MULADD max(dst, sum), SBOX 7 times its operand, PMDS the largest of its window, EMITBOOL twice its operand; the result is
+ * the largest emitted degree.  Host only. */
+int lcp2_gate_program_degree(const uint32_t *code, size_t num_instructions, uint32_t num_regs, uint32_t *degree);
+/* What lcp2_circuit_create / lcp2_verifier_create derived for each of the handle's `num_gates` gates (read only; either array may be
+ * null): degrees[g] as above, and bundles[g], the bundle of low-degree gates with which the prover evaluates gate g on half of the
+ * quotient coset (gates of one bundle share one plane per challenge), or -1 where the gate is evaluated on the whole coset: every
+ * gate of a verifier-only or sharded handle, of a handle created with LCP2_QUOTIENT_TIERS=0 in the environment, and every gate whose
+ * degree exceeds half of the coset's 2^ceil(log2 quotient_degree_factor). */
+int lcp2_circuit_gate_tiers(const lcp2_circuit *c, uint32_t num_gates, uint32_t *degrees, int32_t *bundles);
 
 /* ------------------------------------------------------------------ timing
  * Per-kernel-family HIP-event timing on the context's stream.  Accumulates
