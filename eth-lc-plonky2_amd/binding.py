@@ -55,6 +55,15 @@ class ProofLayout(ctypes.Structure):
                 + [(n, ctypes.c_uint64) for n in ("final_poly", "final_len", "pow_witness", "total")])
 
 
+class U32Job(ctypes.Structure):
+    """lcp2_u32_job: one operation of a plonky2_u32 / comparison row (lcp2_u32_gate_rows)"""
+    _fields_ = [("row", ctypes.c_uint32), ("kind", ctypes.c_uint16), ("op", ctypes.c_uint16), ("inputs", ctypes.c_uint32 * 4)]
+
+
+U32_ARITHMETIC, U32_ADD_MANY, U32_SUBTRACTION, U32_RANGE_CHECK, U32_COMPARISON = range(5)
+U32_JOB_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u2"), ("op", "<u2"), ("in", "<u4", (4,))])   # U32Job as a numpy record
+assert U32_JOB_DTYPE.itemsize == ctypes.sizeof(U32Job) == 24
+
 _lib = None
 
 
@@ -115,6 +124,7 @@ def load_library():
         "lcp2_sha256_witness": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint32, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint64, c.c_void_p]),
         "lcp2_scatter_cells": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint64]),
         "lcp2_poseidon_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint64]),
+        "lcp2_u32_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.c_uint64]),
         "lcp2_commit_wires_rows_begin": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_commit_wires_chunk": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32]),
         "lcp2_commit_wires_rows_finish": (c.c_int, [c.c_void_p, c.c_void_p]),
@@ -383,6 +393,25 @@ class Context:
         return o
 
     # ---- device buffers
+    def buffer_zero(self, dev_ptr, words):
+        self._check(self.lib.lcp2_buffer_zero(self.handle, ctypes.c_void_p(dev_ptr), int(words) * 8))
+
+    def u32_gate_rows(self, jobs, wires_dev, n, njobs=None):
+        """lcp2_u32_gate_rows: writes the cells of every job into the device witness matrix `wires_dev` (a pointer, [>= 126][n]
+        column-major).  jobs: a numpy array of U32_JOB_DTYPE records (a host list: validated before anything runs), or a device
+        pointer to `njobs` lcp2_u32_job records (validated by the kernel).  Sorted by (kind, op, row) is the fast order
+        (u32_gates.witness_jobs returns it); any order is correct."""
+        if isinstance(jobs, np.ndarray):
+            if jobs.dtype != U32_JOB_DTYPE:
+                raise Lcp2Error(-1, "jobs must be an array of U32_JOB_DTYPE records")
+            j = np.ascontiguousarray(jobs).ravel()
+            count, p, mem = j.size, _ptr(j), MEM_HOST
+        else:
+            if njobs is None:
+                raise Lcp2Error(-1, "a device job list needs njobs")
+            count, p, mem = int(njobs), ctypes.c_void_p(jobs), MEM_DEVICE
+        self._check(self.lib.lcp2_u32_gate_rows(self.handle, p, count, mem, ctypes.c_void_p(wires_dev), n))
+
     def buffer_alloc(self, words):
         p = ctypes.c_void_p()
         self._check(self.lib.lcp2_buffer_alloc(self.handle, int(words) * 8, ctypes.byref(p)))

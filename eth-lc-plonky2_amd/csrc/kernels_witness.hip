@@ -12,6 +12,8 @@
 #include "internal.hpp"
 #include "sha_layout.hpp"
 #include "poseidon.hpp"
+#include "prover_kernels.hpp"
+#include "u32_rows.hpp"
 
 namespace lcp2 {
 
@@ -220,6 +222,24 @@ __global__ void k_poseidon_gate_rows(const PoseidonRowDev *__restrict__ rows, u6
 void launch_poseidon_gate_rows(hipStream_t s, const PoseidonRowDev *rows, u64 nrows, u64 *wires, u64 n, const u64 *rc) {
   if (!nrows) return;
   hipLaunchKernelGGL(k_poseidon_gate_rows, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, s, rows, nrows, wires, n, rc);
+}
+
+// One lane per job of lcp2_u32_gate_rows: one operation of a U32Arithmetic / U32AddMany / U32Subtraction / U32RangeCheck /
+// Comparison row, all of its cells (u32_rows.hpp u32_job_cells: the text tests/emu/emu_u32.cpp runs on the CPU).  Every cell is
+// one 8-byte store into a column of the column-major matrix, so a store instruction of a wave is contiguous - 512 bytes, four
+// whole 128-byte lines - exactly when its 64 jobs are 64 consecutive rows of one (kind, op): the order the header calls fast.
+// Jobs in any other order write the same cells, one 8-byte piece of a line per lane.  Nothing is read but the job (24 bytes per
+// lane, contiguous); blocks of 256 keep four waves' stores in flight per CU and a wave never mixes kinds in a sorted list, so the
+// switch does not diverge except at the few boundaries between kinds.
+constexpr u32 U32_ROWS_THREADS = 256;
+__global__ __launch_bounds__(U32_ROWS_THREADS) void k_u32_gate_rows(const U32JobDev *__restrict__ jobs, u64 njobs, u64 *__restrict__ wires,
+                                                                     u64 n, u64 *__restrict__ flag) {
+  u32_rows_lane(jobs, njobs, (u64)blockIdx.x * blockDim.x + threadIdx.x, wires, n, flag);
+}
+void launch_u32_gate_rows(hipStream_t s, const U32JobDev *jobs, u64 njobs, u64 *wires, u64 n, u64 *flag) {
+  if (!njobs) return;
+  hipLaunchKernelGGL(k_u32_gate_rows, dim3((unsigned)((njobs + U32_ROWS_THREADS - 1) / U32_ROWS_THREADS)), dim3(U32_ROWS_THREADS), 0, s,
+                     jobs, njobs, wires, n, flag);
 }
 
 void launch_sha_jobs_level(hipStream_t s, const ShaJobDev *jobs, u32 first, u32 count, const uint32_t *words_in, uint32_t *rec) {

@@ -5,6 +5,8 @@
 #include "ntt_host.hpp"
 #include "poseidon.hpp"
 #include "sha_layout.hpp"
+#include "prover_kernels.hpp"
+#include "u32_rows.hpp"
 
 using namespace lcp2;
 
@@ -632,6 +634,48 @@ extern "C" int lcp2_poseidon_gate_rows(lcp2_ctx *ctx, const lcp2_poseidon_row *r
   launch_poseidon_gate_rows(ctx->stream, (const PoseidonRowDev *)d, nrows, (u64 *)wires, n, ctx->d_rc);
   LCP2_HIP(ctx, hipGetLastError());
   LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the job list is freed on return
+  return LCP2_OK;
+}
+
+// plonky2_u32 / comparison rows: one job per operation of a row.  A host list is validated here, before anything is queued, and
+// goes up in pieces through scratch slot 0 (a 2^22-row circuit of the reference's mix has 13 M jobs, 315 MB: the piece bounds the
+// scratch, and the stream orders the kernel of one piece before the upload of the next).  A device list is validated by the
+// kernel, which is why the flag word is read back either way.
+extern "C" int lcp2_u32_gate_rows(lcp2_ctx *ctx, const lcp2_u32_job *jobs, size_t njobs, lcp2_mem jobs_mem, uint64_t *wires, uint64_t n) {
+  static_assert(sizeof(lcp2_u32_job) == 24 && sizeof(lcp2_u32_job) == sizeof(U32JobDev), "job layouts must agree");
+  static_assert(LCP2_U32_ARITHMETIC == U32_KIND_ARITHMETIC && LCP2_U32_ADD_MANY == U32_KIND_ADD_MANY && LCP2_U32_SUBTRACTION == U32_KIND_SUBTRACTION &&
+                LCP2_U32_RANGE_CHECK == U32_KIND_RANGE_CHECK && LCP2_U32_COMPARISON == U32_KIND_COMPARISON, "kind numbering must agree");
+  if (!ctx || !wires || (njobs && !jobs)) return LCP2_E_INVALID;
+  if (jobs_mem != LCP2_MEM_HOST && jobs_mem != LCP2_MEM_DEVICE) return ctx->fail(LCP2_E_INVALID, "u32 rows: bad lcp2_mem");
+  if (!njobs) return LCP2_OK;
+  const U32JobDev *list = (const U32JobDev *)jobs;
+  if (jobs_mem == LCP2_MEM_HOST)
+    for (size_t i = 0; i < njobs; i++)
+      if (u32 problem = u32_job_problem(list[i], n))
+        return ctx->fail(LCP2_E_INVALID, "u32 rows: job " + std::to_string(i) + ": " + u32_problem_str(problem));
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  void *d_flag;
+  LCP2_TRY(scratch_ensure(ctx, 1, sizeof(u64), &d_flag));
+  LCP2_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(u64), ctx->stream));
+  if (jobs_mem == LCP2_MEM_DEVICE) {
+    launch_u32_gate_rows(ctx->stream, list, njobs, (u64 *)wires, n, (u64 *)d_flag);
+  } else {
+    constexpr size_t PIECE = (size_t)1 << 20;  // jobs: 24 MiB
+    void *d;
+    LCP2_TRY(scratch_ensure(ctx, 0, std::min(njobs, PIECE) * sizeof(lcp2_u32_job), &d));
+    for (size_t at = 0; at < njobs; at += PIECE) {
+      const size_t count = std::min(PIECE, njobs - at);
+      size_t pin_used = 0;
+      if (njobs > PIECE) pin_used = lcp2_ctx::PIN_BYTES;  // (the staging buffer serves one transfer per call: a list in pieces goes up from the caller's memory)
+      LCP2_TRY(upload_small(ctx, d, list + at, count * sizeof(lcp2_u32_job), &pin_used));
+      launch_u32_gate_rows(ctx->stream, (const U32JobDev *)d, count, (u64 *)wires, n, (u64 *)d_flag);
+    }
+  }
+  LCP2_HIP(ctx, hipGetLastError());
+  u64 flag = 0;
+  LCP2_HIP(ctx, hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+  LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's list may go; every cell is written
+  if (flag) return ctx->fail(LCP2_E_INVALID, "u32 rows: job " + std::to_string(flag - 1) + " of the device list is invalid (row, kind, operation slot or borrow); the valid jobs are written");
   return LCP2_OK;
 }
 

@@ -158,6 +158,11 @@ void launch_fri_fold(hipStream_t s, const u64 *c0, const u64 *c1, u64 *o0, u64 *
 void launch_gather_ext_leaves(hipStream_t s, const u64 *p0, const u64 *p1, u32 arity, const u64 *leaf_idx, u32 k, u64 *out);
 void launch_pow_search(hipStream_t s, const PowArgs &a, u64 count);
 void launch_fill(hipStream_t s, u64 *p, u64 n, u64 v);
+// lcp2_u32_gate_rows (kernels_witness.hip k_u32_gate_rows, u32_rows.hpp): one lane per job writes the cells of one operation of a
+// plonky2_u32 / comparison row into wires [>= 126][n]; *flag (device, zeroed by the caller) receives 1 + the index of an invalid
+// job, which writes nothing
+struct U32JobDev;
+void launch_u32_gate_rows(hipStream_t s, const U32JobDev *jobs, u64 njobs, u64 *wires, u64 n, u64 *flag);
 // *flag = 1 if a word of p[r * pitch + i] (r < rows, i < width) is a non-zero field element (flag zeroed by the caller)
 void launch_any_nonzero(hipStream_t s, const u64 *p, u64 pitch, u64 width, u32 rows, unsigned long long *flag);
 

@@ -16,6 +16,7 @@ claim is checked against the program at build()), with `native=False` through th
 import numpy as np
 
 from . import gl_np as gl
+from .binding import U32_ADD_MANY, U32_ARITHMETIC, U32_COMPARISON, U32_JOB_DTYPE, U32_RANGE_CHECK, U32_SUBTRACTION
 from .circuit import (GATE_EMIT_FORWARD, K_REG, Circuit, GateSet, W, gate_noop, sigma_values)
 
 P = gl.P
@@ -654,3 +655,61 @@ def reference_mix_circuit(params, seed, native=True, small_values=False):
     """circuit.synthetic_circuit with the reference's gate mix (ReferenceMix): (Circuit, wires, public_inputs); params.num_constants = 5"""
     from .circuit import synthetic_circuit
     return synthetic_circuit(params, seed, small_values=small_values, extra=ReferenceMix(native))
+
+
+# ---------------------------------------------------------------- jobs of lcp2_u32_gate_rows: one operation of one row each
+# kind -> (gate name, operations per row, the wires of operation `op` that hold its inputs)
+U32_JOB_KINDS = {
+    U32_ARITHMETIC: ("U32ArithmeticGate", U32_ARITH_OPS, lambda op: [6 * op, 6 * op + 1, 6 * op + 2]),
+    U32_ADD_MANY: ("U32AddManyGate", ADD_MANY_OPS, lambda op: [6 * op + k for k in range(ADD_MANY_ADDENDS + 1)]),
+    U32_SUBTRACTION: ("U32SubtractionGate", SUB_OPS, lambda op: [5 * op, 5 * op + 1, 5 * op + 2]),
+    U32_RANGE_CHECK: ("U32RangeCheckGate", RANGE_INPUTS, lambda op: [op]),
+    U32_COMPARISON: ("ComparisonGate", 1, lambda op: [0, 1]),
+}
+
+
+def job_columns(kind, op):
+    """the columns (wires) one job of lcp2_u32_gate_rows owns: every cell of operation `op` of a row of gate `kind`"""
+    name, ops, _ = U32_JOB_KINDS[kind]
+    assert 0 <= op < ops, (name, op)
+    if kind == U32_ARITHMETIC:
+        return list(range(6 * op, 6 * op + 6)) + list(range(6 * U32_ARITH_OPS + U32_ARITH_LIMBS * op, 6 * U32_ARITH_OPS + U32_ARITH_LIMBS * (op + 1)))
+    if kind == U32_ADD_MANY:
+        per, nl = ADD_MANY_ADDENDS + 3, ADD_MANY_RESULT_LIMBS + ADD_MANY_CARRY_LIMBS
+        return list(range(per * op, per * op + per)) + list(range(per * ADD_MANY_OPS + nl * op, per * ADD_MANY_OPS + nl * (op + 1)))
+    if kind == U32_SUBTRACTION:
+        return list(range(5 * op, 5 * op + 5)) + list(range(5 * SUB_OPS + SUB_LIMBS * op, 5 * SUB_OPS + SUB_LIMBS * (op + 1)))
+    if kind == U32_RANGE_CHECK:
+        return [op] + list(range(RANGE_INPUTS + RANGE_AUX * op, RANGE_INPUTS + RANGE_AUX * (op + 1)))
+    return list(range(4 + 5 * CMP_CHUNKS + CMP_CHUNK_BITS + 1))
+
+
+def gate_rows(circ):
+    """(gate_of_row, G): the gate index of every row of a circuit, read back from its selector columns, and name -> index"""
+    gs = circ.gateset
+    gate_of_row = np.full(circ.n, -1, dtype=np.int64)
+    for k, g in enumerate(gs.gates):
+        gate_of_row[circ.constants_sigmas[g.selector_index] == np.uint64(k)] = k
+    assert (gate_of_row >= 0).all()
+    return gate_of_row, {name: k for k, name in enumerate(gs.names)}
+
+
+def witness_jobs(wires, gate_of_row, G):
+    """The jobs that regenerate every u32 / comparison row of a filled host witness: the inputs of each operation read out of
+    `wires` [num_wires][n].  Returns an array of U32_JOB_DTYPE records sorted by (kind, op, row), the order in which
+    lcp2_u32_gate_rows stores contiguously."""
+    parts = []
+    for kind in sorted(U32_JOB_KINDS):
+        name, ops, input_wires = U32_JOB_KINDS[kind]
+        if name not in G:
+            continue
+        rows = np.nonzero(gate_of_row == G[name])[0]
+        for op in range(ops):
+            jobs = np.zeros(rows.size, dtype=U32_JOB_DTYPE)
+            jobs["row"], jobs["kind"], jobs["op"] = rows, kind, op
+            for k, col in enumerate(input_wires(op)):
+                v = wires[col, rows]
+                assert (v <= _M32).all(), "%s input on wire %d is not a u32" % (name, col)
+                jobs["in"][:, k] = v
+            parts.append(jobs)
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=U32_JOB_DTYPE)

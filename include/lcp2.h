@@ -198,6 +198,42 @@ typedef struct {
   uint64_t in[12];   /* any u64 */
 } lcp2_poseidon_row;
 int lcp2_poseidon_gate_rows(lcp2_ctx *ctx, const lcp2_poseidon_row *rows, size_t nrows, uint64_t *wires, uint64_t n);
+/* plonky2_u32 and comparison rows generated on the device: U32ArithmeticGate { num_ops: 3 }, U32AddManyGate { num_addends: 3,
+ * num_ops: 5 }, U32SubtractionGate { num_ops: 6 }, U32RangeCheckGate { num_input_limbs: 7 } and ComparisonGate { num_bits: 32,
+ * num_chunks: 16 } - what plonky2_crypto's two_to_one_sha256, the BigUint gadgets, cmp_biguint and div_rem_biguint lower to
+ * (reference call sites src/merkle_tree_gadget.rs:37,57,77-79, src/targets.rs:184-235,304-332).  Most cells of such a row are
+ * two-bit limbs, chunk flags and inverses that only the gate's own constraints read; a fork's generator computes the outputs that
+ * other generators need on the host (one multiply-add, add or subtract), sets them, and queues a job.
+ * One job is ONE OPERATION of one row - a row holds 3, 5, 6, 7 or 1 independent operations whose inputs arrive at different
+ * times in a generator graph - and writes every cell of that operation, inputs, outputs and auxiliary cells, into the column-major
+ * witness matrix `wires` [>= 126][n] (wire layouts and values: eth-lc-plonky2_amd/u32_gates.py, parity unpinned like them):
+ *   kind          op <  in[]                               cells written
+ *   ARITHMETIC    3     m0, m1, addend                     wires 6 op .. 6 op + 5 (m0, m1, addend, output_low, output_high, inverse),
+ *                                                          32 limbs at 18 + 32 op.  inverse = 1 / (0xFFFFFFFF - output_high), and 0
+ *                                                          when output_high = 0xFFFFFFFF (output_low is 0 then)
+ *   ADD_MANY      5     addend0, addend1, addend2, carry   wires 6 op .. 6 op + 5 (.., output_result, output_carry), 18 limbs at 30 + 18 op
+ *   SUBTRACTION   6     x, y, borrow (0 or 1)              wires 5 op .. 5 op + 4 (.., output_result, output_borrow), 16 limbs at 30 + 16 op
+ *   RANGE_CHECK   7     input                              wire op, 16 limbs at 7 + 16 op
+ *   COMPARISON    1     first, second                      wires 0 .. 86 (result_bool = first <= second)
+ * Cells outside the operation are NOT touched: zero the matrix first (lcp2_buffer_zero).  A row of zeros satisfies every one of
+ * these gates except ComparisonGate, which needs a job for every row it occupies.  Two jobs for the same (row, op) leave one of
+ * the two values, unspecified which; jobs of different kinds on one row are the caller's error and are not detected.
+ * Order: any order is correct.  The FAST order is the list sorted by (kind, op, row): neighbouring lanes then store to
+ * neighbouring rows of the same columns and every store of a wave is contiguous.  The library does not sort.
+ * jobs_mem = LCP2_MEM_HOST: the list is validated before anything is launched, and a refused list writes nothing.
+ * LCP2_MEM_DEVICE: the kernel validates; an invalid job writes no cell, the valid ones are written, and the call still returns
+ * LCP2_E_INVALID.  Refused (LCP2_E_INVALID, the reason in lcp2_last_error): row >= n, an unknown kind, op out of range for the
+ * kind, a subtraction borrow above 1; also a null ctx or wires, or a null list with njobs > 0.  njobs = 0 is LCP2_OK.
+ * The context's stream is synchronised on return. */
+enum { LCP2_U32_ARITHMETIC = 0, LCP2_U32_ADD_MANY = 1, LCP2_U32_SUBTRACTION = 2, LCP2_U32_RANGE_CHECK = 3, LCP2_U32_COMPARISON = 4 };
+typedef struct {
+  uint32_t row;
+  uint16_t kind;   /* LCP2_U32_* */
+  uint16_t op;     /* operation slot inside the row */
+  uint32_t in[4];  /* the operation's inputs, each a u32; unused ones are ignored */
+} lcp2_u32_job;    /* 24 bytes */
+int lcp2_u32_gate_rows(lcp2_ctx *ctx, const lcp2_u32_job *jobs, size_t njobs, lcp2_mem jobs_mem,
+                       uint64_t *wires /* device, column-major [>= 126][n] */, uint64_t n);
 
 /* device buffers for callers that keep the witness resident in HBM */
 int lcp2_buffer_alloc(lcp2_ctx *ctx, size_t bytes, void **dev);
