@@ -97,7 +97,8 @@ def build_host(force=False, verbose=False):
     witness generation) behind the C entry points of host/lc_capi.h, linked against liblcp2.so.  g++ only (no device code)."""
     build_native(verbose=verbose)
     srcs = sorted(os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith(".cpp"))
-    deps = srcs + [os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith((".hpp", ".h"))] + [os.path.join(PKG_DIR, "..", "include", "lcp2.h")]
+    deps = srcs + [os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith((".hpp", ".h"))] + [
+        os.path.join(PKG_DIR, "..", "include", "lcp2.h"), os.path.join(CSRC, "gate_program.hpp")]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps):
         return HOST_LIB
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", HOST_LIB + ".tmp"] + srcs + ["-L", PKG_DIR, "-llcp2", "-Wl,-rpath,$ORIGIN"]

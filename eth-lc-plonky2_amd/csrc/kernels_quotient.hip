@@ -7,6 +7,7 @@
 // The LDE matrices are indexed in their storage (= Merkle leaf) order, so all column reads are coalesced 512-byte runs per wave;
 // the only gathers are the two Z(g x) values per point in k_q_perm.
 #include <algorithm>
+#include "gate_program.hpp"
 #include "kernels_gates.hpp"
 
 namespace lcp2 {
@@ -17,29 +18,25 @@ namespace lcp2 {
 void stage_gate_programs(const std::vector<uint32_t> &code, std::vector<GateDev> &gates, u32 num_wires, u32 num_selectors,
                          std::vector<uint32_t> &out, std::vector<uint32_t> &lists) {
   out.clear(); lists.clear();
-  auto column_of = [&](u32 kind, u32 idx) { return kind == 1 ? idx : num_wires + num_selectors + idx; };
-  auto nsrc_of = [](u32 op) { return (op == LCP2_OP_EMIT || op == LCP2_OP_EMITBOOL || op == LCP2_OP_SBOX) ? 1u : op == LCP2_OP_PMDS ? 0u : 2u; };
+  using gate_program::Insn;
+  auto column_of = [&](const Insn &in, int k) { return in.kind[k] == gate_program::KIND_WIRE ? in.idx[k] : num_wires + num_selectors + in.idx[k]; };
   for (GateDev &G : gates) {
     const u32 first = G.code_offset, last = G.code_offset + G.code_len, new_first = (u32)out.size() / 2;
     std::vector<u32> window;  // columns staged by the last LDG
     for (u32 pc = first; pc < last; pc++) {
-      u32 w0 = code[2 * pc], w1 = code[2 * pc + 1];
-      const u32 op = w0 & 0xF;
-      u32 kk[2] = {(w0 >> 16) & 0xF, (w0 >> 20) & 0xF}, ii[2] = {w1 & 0xFFFF, w1 >> 16};
-      const u32 nsrc = nsrc_of(op);
+      Insn in(code[2 * pc], code[2 * pc + 1]);
       auto slot_of = [&](u32 col) { for (u32 s = 0; s < window.size(); s++) if (window[s] == col) return (int)s; return -1; };
       bool missing = false;
-      for (u32 k = 0; k < nsrc; k++)
-        if ((kk[k] == 1 || kk[k] == 2) && slot_of(column_of(kk[k], ii[k])) < 0) missing = true;
+      for (int k = 0; k < in.nsrc(); k++)
+        if (gate_program::is_column(in.kind[k]) && slot_of(column_of(in, k)) < 0) missing = true;
       if (missing) {  // open a new window from here
         window.clear();
         for (u32 q = pc; q < last && window.size() < QUOTIENT_STAGE; q++) {
-          const u32 v0 = code[2 * q], v1 = code[2 * q + 1], o = v0 & 0xF;
-          const u32 k2[2] = {(v0 >> 16) & 0xF, (v0 >> 20) & 0xF}, i2[2] = {v1 & 0xFFFF, v1 >> 16};
+          const Insn ahead(code[2 * q], code[2 * q + 1]);
           std::vector<u32> need;
-          for (u32 k = 0; k < nsrc_of(o); k++)
-            if (k2[k] == 1 || k2[k] == 2) {
-              const u32 col = column_of(k2[k], i2[k]);
+          for (int k = 0; k < ahead.nsrc(); k++)
+            if (gate_program::is_column(ahead.kind[k])) {
+              const u32 col = column_of(ahead, k);
               bool have = false;
               for (u32 c : window) have = have || c == col;
               for (u32 c : need) have = have || c == col;
@@ -52,13 +49,11 @@ void stage_gate_programs(const std::vector<uint32_t> &code, std::vector<GateDev>
         out.push_back((u32)lists.size());
         lists.insert(lists.end(), window.begin(), window.end());
       }
-      for (u32 k = 0; k < nsrc; k++)
-        if (kk[k] == 1 || kk[k] == 2) { ii[k] = (u32)slot_of(column_of(kk[k], ii[k])); kk[k] = QKIND_STAGE; }
-      if (op != LCP2_OP_PMDS) {
-        w0 = (w0 & 0xFFFF) | kk[0] << 16 | kk[1] << 20;
-        w1 = (nsrc >= 1 ? ii[0] : (w1 & 0xFFFF)) | (nsrc >= 2 ? ii[1] : (w1 >> 16)) << 16;
-      }
-      out.push_back(w0); out.push_back(w1);
+      for (int k = 0; k < in.nsrc(); k++)
+        if (gate_program::is_column(in.kind[k])) { in.idx[k] = (u32)slot_of(column_of(in, k)); in.kind[k] = QKIND_STAGE; }
+      u32 w[2];
+      in.encode(w);
+      out.push_back(w[0]); out.push_back(w[1]);
     }
     G.code_offset = new_first;
     G.code_len = (u32)out.size() / 2 - new_first;

@@ -3,8 +3,10 @@
 #include <algorithm>
 #include <cstdlib>
 #include "circuit_state.hpp"
+#include "gate_program.hpp"
 
 using namespace lcp2;
+namespace gp = gate_program;
 
 namespace lcp2 {
 // shape checks shared by build() and the verifier-only constructor: everything the prover's workspaces and the verifier's
@@ -33,19 +35,11 @@ const char *params_problem(const lcp2_params &p, bool *unsupported) {
 }  // namespace lcp2
 
 namespace {
-// one instruction of a gate program (two words, include/lcp2.h): source k is of kind[k] (0: a register) at idx[k]
-struct Insn {
-  u32 op, dst, kind[2], idx[2];
-  Insn(u32 w0, u32 w1) : op(w0 & 0xF), dst((w0 >> 8) & 0xFF), kind{(w0 >> 16) & 0xF, (w0 >> 20) & 0xF}, idx{w1 & 0xFFFF, w1 >> 16} {}
-  bool emits() const { return op == LCP2_OP_EMIT || op == LCP2_OP_EMITBOOL; }
-  int nsrc() const { return (emits() || op == LCP2_OP_SBOX) ? 1 : 2; }
-};
-
 // validate the programs once so that neither the kernels nor the host verifier ever index out of range
 const char *validate_programs(const lcp2_circuit_desc *d) {
   const lcp2_params &p = d->params;
   if (d->num_regs > 64 || d->num_selectors > p.num_constants) return "bad gate set";
-  const size_t nregs = std::max(d->num_regs, 1u);
+  const gp::Limits limits{std::max(d->num_regs, 1u), p.num_wires, p.num_constants - d->num_selectors, d->num_imm, 4};
   for (u32 g = 0; g < d->num_gates; g++) {
     const lcp2_gate &G = d->gates[g];
     if (G.selector_index >= d->num_selectors || ((size_t)G.code_offset + (size_t)G.code_len) * 2 > d->code_words || G.group_end < G.group_start ||
@@ -70,52 +64,30 @@ const char *validate_programs(const lcp2_circuit_desc *d) {
     }
     size_t emits_seen = 0;
     for (size_t pc = G.code_offset; pc < (size_t)G.code_offset + G.code_len; pc++) {
-      const Insn in(d->code[2 * pc], d->code[2 * pc + 1]);
-      if (in.op > LCP2_OP_PMDS) return "bad instruction";
-      if (in.op == LCP2_OP_PMDS) {  // register windows of 12 and a block of 12 immediates
-        if (in.kind[0] != 0 || in.kind[1] != 3 || (size_t)in.dst + 12 > nregs || (size_t)in.idx[0] + 12 > nregs || (size_t)in.idx[1] + 12 > d->num_imm)
-          return "PMDS window out of range";
-        continue;
-      }
-      if (!in.emits() && in.dst >= nregs) return "bad instruction";
+      const gp::Insn in(d->code[2 * pc], d->code[2 * pc + 1]);
+      if (const char *why = gp::insn_problem(in, limits)) return why;
       emits_seen += in.emits();
-      for (int k = 0; k < in.nsrc(); k++) {
-        const u32 kind = in.kind[k];
-        size_t lim = kind == 0 ? nregs : kind == 1 ? p.num_wires : kind == 2 ? p.num_constants - d->num_selectors : kind == 3 ? d->num_imm : kind == 4 ? 4 : 0;
-        if (in.idx[k] >= lim) return "operand out of range";
-      }
     }
     if (emits_seen != G.num_constraints) return "num_constraints does not match the program";
   }
   return nullptr;
 }
 
-// Degree bound of a gate's constraints in the wire and constant polynomials (each of degree < n), propagated through the
-// straight-line program: a WIRE / CONST operand is 1, IMM / PI 0, a register what was last written to it.  Saturates at DEGREE_CAP.
+// Degree bound of a gate's constraints in the wire and constant polynomials (each of degree < n): the program walked over degree
+// bounds, where a sum has the larger degree of its terms and a product the sum of its factors', saturating at DEGREE_CAP.
 constexpr u32 DEGREE_CAP = 1u << 20;
+struct DegreeAlg {
+  using V = u32; using S = u32;
+  V wire(u32) { return 1; }    V gate_const(u32) { return 1; }    V imm(u64) { return 0; }    V pi(u32) { return 0; }    S scalar(u64) { return 0; }
+  V add(V a, V b) { return std::max(a, b); }    V sub(V a, V b) { return std::max(a, b); }    V mul(V a, V b) { return std::min(a + b, DEGREE_CAP); }
+  V mul_add(V a, V b, V acc) { return std::max(acc, mul(a, b)); }
+  V scale_add(V x, S, V acc) { return std::max(x, acc); }
+};
 u32 program_degree(const uint32_t *code, size_t first, size_t len, size_t nregs) {
   std::vector<u32> reg(std::max<size_t>(nregs, 1), 0);
-  auto cap = [](u64 d) { return (u32)std::min<u64>(d, DEGREE_CAP); };
+  DegreeAlg A;
   u32 deg = 0;
-  for (size_t pc = first; pc < first + len; pc++) {
-    const Insn in(code[2 * pc], code[2 * pc + 1]);
-    if (in.op == LCP2_OP_PMDS) {  // a linear map of the source window plus constants
-      u32 m = 0;
-      for (u32 r = 0; r < 12; r++) m = std::max(m, reg[in.idx[0] + r]);
-      for (u32 r = 0; r < 12; r++) reg[in.dst + r] = m;
-      continue;
-    }
-    auto of = [&](int k) { return in.kind[k] == 0 ? reg[in.idx[k]] : (in.kind[k] == 1 || in.kind[k] == 2) ? 1u : 0u; };
-    const u32 x = of(0);
-    switch (in.op) {
-      case LCP2_OP_EMIT: deg = std::max(deg, x); break;
-      case LCP2_OP_EMITBOOL: deg = std::max(deg, cap(2ull * x)); break;
-      case LCP2_OP_SBOX: reg[in.dst] = cap(7ull * x); break;
-      case LCP2_OP_MUL: case LCP2_OP_XOR: reg[in.dst] = cap((u64)x + of(1)); break;
-      case LCP2_OP_MULADD: reg[in.dst] = std::max(reg[in.dst], cap((u64)x + of(1))); break;
-      default: reg[in.dst] = std::max(x, of(1)); break;  // ADD, SUB, DBLADD
-    }
-  }
+  gp::walk_program(A, code, first, len, (const u64 *)nullptr, reg.data(), [&](u32 d) { deg = std::max(deg, d); });
   return deg;
 }
 
@@ -261,14 +233,8 @@ int circuit_create(lcp2_ctx *ctx, const lcp2_circuit_desc *d, uint32_t bf, uint3
     c->dev_regs = 1;
     for (const lcp2_gate &G : c->gates) {
       if (G.flags & LCP2_GATE_NATIVE_MASK) continue;
-      for (size_t pc = G.code_offset; pc < (size_t)G.code_offset + G.code_len; pc++) {
-        const Insn in(c->code[2 * pc], c->code[2 * pc + 1]);
-        const bool pmds = in.op == LCP2_OP_PMDS;  // reads and writes a window of 12 registers
-        u32 top = in.emits() ? 0 : in.dst + (pmds ? 12 : 1);
-        if (pmds) top = std::max(top, in.idx[0] + 12);
-        for (int k = 0; k < in.nsrc() && !pmds; k++) if (in.kind[k] == 0) top = std::max(top, in.idx[k] + 1);
-        c->dev_regs = std::max(c->dev_regs, top);
-      }
+      for (size_t pc = G.code_offset; pc < (size_t)G.code_offset + G.code_len; pc++)
+        c->dev_regs = std::max(c->dev_regs, gp::Insn(c->code[2 * pc], c->code[2 * pc + 1]).top_reg());
     }
     staged.resize(staged.size() + 4, 0);  // padded by two instructions: K6 fetches one instruction ahead of the one it executes
     LCP2_TRY(upload(ctx, c->d_gates, dev_gates.data(), dev_gates.size() * sizeof(GateDev)));
@@ -433,19 +399,10 @@ extern "C" size_t lcp2_proof_words(const lcp2_params *p) {
 }
 extern "C" int lcp2_gate_program_degree(const uint32_t *code, size_t num_instructions, uint32_t num_regs, uint32_t *degree) {
   if (!code || !degree || num_regs > 64) return LCP2_E_INVALID;
-  const size_t nregs = std::max(num_regs, 1u);
-  for (size_t pc = 0; pc < num_instructions; pc++) {  // what validate_programs checks of the registers
-    const Insn in(code[2 * pc], code[2 * pc + 1]);
-    if (in.op > LCP2_OP_PMDS) return LCP2_E_INVALID;
-    if (in.op == LCP2_OP_PMDS) {
-      if ((size_t)in.dst + 12 > nregs || (size_t)in.idx[0] + 12 > nregs) return LCP2_E_INVALID;
-      continue;
-    }
-    if (!in.emits() && in.dst >= nregs) return LCP2_E_INVALID;
-    for (int k = 0; k < in.nsrc(); k++)
-      if (in.kind[k] > 4 || (in.kind[k] == 0 && in.idx[k] >= nregs)) return LCP2_E_INVALID;
-  }
-  *degree = program_degree(code, 0, num_instructions, nregs);
+  const gp::Limits registers_only{std::max(num_regs, 1u)};  // the walk below indexes nothing else
+  for (size_t pc = 0; pc < num_instructions; pc++)
+    if (gp::insn_problem(gp::Insn(code[2 * pc], code[2 * pc + 1]), registers_only)) return LCP2_E_INVALID;
+  *degree = program_degree(code, 0, num_instructions, registers_only.regs);
   return LCP2_OK;
 }
 extern "C" int lcp2_circuit_gate_tiers(const lcp2_circuit *c, uint32_t num_gates, uint32_t *degrees, int32_t *bundles) {

@@ -4,6 +4,7 @@
 // (verify_fri_proof, fri_combine_initial, compute_evaluation).  Milliseconds of scalar work: it stays
 // on the host exactly as in the reference; no device call is made here.
 #include <vector>
+#include "gate_program.hpp"
 #include "host_protocol.hpp"
 #include "internal.hpp"
 
@@ -16,68 +17,18 @@ namespace {
 inline gl2 rd2(const u64 *p) { return gl2_make(p[0], p[1]); }
 inline gl2 base2(u64 x) { return gl2_make(x, 0); }
 
-// gate programs over the extension field (evaluation at zeta)
-inline gl2 sbox7_ext(gl2 x) { gl2 x2 = gl2_mul(x, x), x4 = gl2_mul(x2, x2), x3 = gl2_mul(x2, x); return gl2_mul(x3, x4); }
-void eval_gates_ext(const VerifierView &v, const gl2 *wires, const gl2 *consts, const u64 *pis, const u64 *alphas, gl2 *out) {
-  static const u64 CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-  const u32 CH = v.p->num_challenges;
-  for (u32 k = 0; k < CH; k++) out[k] = base2(0);
-  gl2 regs[64];
-  for (u32 g = 0; g < v.num_gates; g++) {
-    const lcp2_gate &G = v.gates[g];
-    const bool fwd = (G.flags & LCP2_GATE_EMIT_FORWARD) != 0;
-    gl2 acc[4] = {base2(0), base2(0), base2(0), base2(0)};
-    u64 apow[4] = {1, 1, 1, 1};  // forward gates: running powers of alpha (the prover kernel uses the 1 / alpha Horner form)
-    for (u32 pc = G.code_offset; pc < G.code_offset + G.code_len; pc++) {
-      const u32 w0 = v.code[2 * pc], w1 = v.code[2 * pc + 1];
-      const u32 op = w0 & 0xF, dst = (w0 >> 8) & 0xFF, ka = (w0 >> 16) & 0xF, kb = (w0 >> 20) & 0xF, ia = w1 & 0xFFFF, ib = w1 >> 16;
-      auto fetch = [&](u32 k, u32 i) -> gl2 {
-        switch (k) {
-          case 0: return regs[i];
-          case 1: return wires[i];
-          case 2: return consts[v.num_selectors + i];
-          case 3: return base2(v.imm[i]);
-          default: return base2(pis[i]);
-        }
-      };
-      if (op == LCP2_OP_PMDS) {
-        gl2 in[12];
-        for (int i = 0; i < 12; i++) in[i] = regs[ia + i];
-        for (int r = 0; r < 12; r++) {
-          gl2 t = base2(v.imm[ib + r]);
-          if (r == 0) t = gl2_add(t, gl2_scale(in[0], 8));
-          for (int i = 0; i < 12; i++) t = gl2_add(t, gl2_scale(in[(i + r) % 12], CIRC[i]));
-          regs[dst + r] = t;
-        }
-        continue;
-      }
-      gl2 a = fetch(ka, ia);
-      if (op == LCP2_OP_EMIT || op == LCP2_OP_EMITBOOL) {
-        if (op == LCP2_OP_EMITBOOL) a = gl2_sub(gl2_mul(a, a), a);
-        for (u32 k = 0; k < CH; k++) {
-          if (fwd) { acc[k] = gl2_add(acc[k], gl2_scale(a, apow[k])); apow[k] = gl_mul(apow[k], alphas[k]); }
-          else acc[k] = gl2_add(gl2_scale(acc[k], alphas[k]), a);
-        }
-        continue;
-      }
-      if (op == LCP2_OP_SBOX) { regs[dst] = sbox7_ext(a); continue; }
-      gl2 b = fetch(kb, ib);
-      switch (op) {
-        case LCP2_OP_ADD: regs[dst] = gl2_add(a, b); break;
-        case LCP2_OP_SUB: regs[dst] = gl2_sub(a, b); break;
-        case LCP2_OP_MUL: regs[dst] = gl2_mul(a, b); break;
-        case LCP2_OP_XOR: { gl2 ab = gl2_mul(a, b); regs[dst] = gl2_sub(gl2_sub(gl2_add(a, b), ab), ab); break; }
-        case LCP2_OP_DBLADD: regs[dst] = gl2_add(gl2_add(a, a), b); break;
-        default: regs[dst] = gl2_add(regs[dst], gl2_mul(a, b)); break;  // LCP2_OP_MULADD
-      }
-    }
-    gl2 s = consts[G.selector_index], f = base2(1);
-    for (u32 j = G.group_start; j < G.group_end; j++)
-      if (j != G.selector_value) f = gl2_mul(f, gl2_sub(base2(j), s));
-    if (v.num_selectors > 1) f = gl2_mul(f, gl2_sub(base2(0xFFFFFFFFull), s));
-    for (u32 k = 0; k < CH; k++) out[k] = gl2_add(out[k], gl2_mul(f, acc[k]));
-  }
-}
+// gate programs over the extension field (evaluation at zeta): the algebra gate_program.hpp walks them with.  mul_add and scale_add
+// are a multiplication and an addition here (the field element is the same either way; over targets they are one gate)
+struct ZetaAlg {
+  using V = gl2; using S = u64;
+  const gl2 *wires, *consts; const u64 *pis; u32 num_selectors;
+  V wire(u32 i) { return wires[i]; }    V selector(u32 i) { return consts[i]; }    V gate_const(u32 i) { return consts[num_selectors + i]; }
+  V imm(u64 x) { return base2(x); }     V pi(u32 i) { return base2(pis[i]); }
+  S scalar(u64 x) { return x; }         S scalar_mul(S a, S b) { return gl_mul(a, b); }
+  V add(V a, V b) { return gl2_add(a, b); }    V sub(V a, V b) { return gl2_sub(a, b); }    V mul(V a, V b) { return gl2_mul(a, b); }
+  V mul_add(V a, V b, V acc) { return gl2_add(acc, gl2_mul(a, b)); }
+  V scale_add(V x, S s, V acc) { return gl2_add(acc, gl2_scale(x, s)); }
+};
 
 // compute_evaluation: value at beta of the degree < arity interpolant through the coset of x
 gl2 fri_compute_evaluation(u64 x, u64 within, u32 arity_bits, const gl2 *evals_bitrev, gl2 beta) {
@@ -166,7 +117,8 @@ int verify_impl(const VerifierView &v, const u64 *proof, const u64 *pis_in) {
       }
     }
     gl2 gates[4];
-    eval_gates_ext(v, ow.data(), oc.data(), pi_hash, alphas, gates);
+    ZetaAlg at_zeta{ow.data(), oc.data(), pi_hash, v.num_selectors};
+    gate_program::eval_gates_filtered(at_zeta, v.gates, v.num_gates, v.code, v.imm, v.num_selectors, alphas, CH, gates);
     for (u32 k = 0; k < CH; k++) {
       gl2 acc = gates[k];
       for (size_t t = terms.size(); t-- > 0;) acc = gl2_add(gl2_scale(acc, alphas[k]), terms[t]);

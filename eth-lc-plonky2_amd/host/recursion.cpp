@@ -1,8 +1,9 @@
 // Recursive verifier gadget (recursion.hpp).  Every function restates, over targets, the step of csrc/verifier.hip::verify_impl
-// named beside it; the two must stay in lockstep (tests/cpp/test_gadgets.cpp proves an inner circuit, verifies the proof natively
+// named beside it (the gate programs are walked by the verifier's own code, csrc/gate_program.hpp); the two must stay in lockstep (tests/cpp/test_gadgets.cpp proves an inner circuit, verifies the proof natively
 // and in-circuit, and checks that a tampered proof makes the outer witness generation fail).
 #include "recursion.hpp"
 #include "host_internal.hpp"
+#include "../csrc/gate_program.hpp"
 
 namespace lc {
 
@@ -206,68 +207,18 @@ void set_verifier_data_target(PartialWitness &pw, const VerifierCircuitTarget &t
 
 // ------------------------------------------------------------------ verify_proof
 namespace {
-// csrc/verifier.hip eval_gates_ext: the inner circuit's gate programs over extension targets at zeta
-void eval_gates_ext(Ar &A, const CommonCircuitData &c, const std::vector<EV> &wires, const std::vector<EV> &consts, const SV pis[4], const std::vector<SV> &alphas,
-                    std::vector<EV> &out) {
-  static const uint64_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-  const uint32_t CH = c.params.num_challenges;
-  const EV ezero{K(0), K(0)};
-  out.assign(CH, ezero);
-  std::vector<EV> regs(64, ezero);
-  for (const lcp2_gate &G : c.gates) {
-    const bool fwd = (G.flags & LCP2_GATE_EMIT_FORWARD) != 0;
-    std::vector<EV> acc(CH, ezero);
-    std::vector<SV> apow(CH, K(1));
-    for (uint32_t pc = G.code_offset; pc < G.code_offset + G.code_len; pc++) {
-      const uint32_t w0 = c.code[2 * pc], w1 = c.code[2 * pc + 1];
-      const uint32_t op = w0 & 0xF, dst = (w0 >> 8) & 0xFF, ka = (w0 >> 16) & 0xF, kb = (w0 >> 20) & 0xF, ia = w1 & 0xFFFF, ib = w1 >> 16;
-      auto fetch = [&](uint32_t k, uint32_t i) -> EV {
-        switch (k) {
-          case 0: return regs[i];
-          case 1: return wires[i];
-          case 2: return consts[c.num_selectors + i];
-          case 3: return EV{K(c.imm[i]), K(0)};
-          default: return EV{pis[i], K(0)};
-        }
-      };
-      if (op == LCP2_OP_PMDS) {
-        EV in[12];
-        for (int i = 0; i < 12; i++) in[i] = regs[ia + i];
-        for (int r = 0; r < 12; r++) {
-          EV t{K(c.imm[ib + r]), K(0)};
-          if (r == 0) t = A.escale_add(in[0], K(8), t);
-          for (int i = 0; i < 12; i++) t = A.escale_add(in[(i + r) % 12], K(CIRC[i]), t);
-          regs[dst + r] = t;
-        }
-        continue;
-      }
-      EV a = fetch(ka, ia);
-      if (op == LCP2_OP_EMIT || op == LCP2_OP_EMITBOOL) {
-        if (op == LCP2_OP_EMITBOOL) a = A.esub(A.emul(a, a), a);
-        for (uint32_t k = 0; k < CH; k++) {
-          if (fwd) { acc[k] = A.escale_add(a, apow[k], acc[k]); apow[k] = A.mul(apow[k], alphas[k]); }
-          else acc[k] = A.escale_add(acc[k], alphas[k], a);
-        }
-        continue;
-      }
-      if (op == LCP2_OP_SBOX) { EV x2 = A.emul(a, a), x4 = A.emul(x2, x2), x3 = A.emul(x2, a); regs[dst] = A.emul(x3, x4); continue; }
-      EV b = fetch(kb, ib);
-      switch (op) {
-        case LCP2_OP_ADD: regs[dst] = A.eadd(a, b); break;
-        case LCP2_OP_SUB: regs[dst] = A.esub(a, b); break;
-        case LCP2_OP_MUL: regs[dst] = A.emul(a, b); break;
-        case LCP2_OP_XOR: { EV ab = A.emul(a, b); regs[dst] = A.esub(A.esub(A.eadd(a, b), ab), ab); break; }
-        case LCP2_OP_DBLADD: regs[dst] = A.eadd(A.eadd(a, a), b); break;
-        default: regs[dst] = A.emul_add(a, b, regs[dst]); break;  // LCP2_OP_MULADD
-      }
-    }
-    EV s = consts[G.selector_index], f{K(1), K(0)};
-    for (uint32_t j = G.group_start; j < G.group_end; j++)
-      if (j != G.selector_value) f = A.emul(f, A.esub(EV{K(j), K(0)}, s));
-    if (c.num_selectors > 1) f = A.emul(f, A.esub(EV{K(0xFFFFFFFFull), K(0)}, s));
-    for (uint32_t k = 0; k < CH; k++) out[k] = A.emul_add(f, acc[k], out[k]);
-  }
-}
+// the inner circuit's gate programs over extension targets at zeta: the algebra csrc/gate_program.hpp walks them with (the same
+// walk as csrc/verifier.hip's ZetaAlg, here one ArithmeticGate operation per call)
+struct ZetaTargets {
+  using V = EV; using S = SV;
+  Ar &A; const std::vector<EV> &wires, &consts; const SV *pis; uint32_t num_selectors;
+  V wire(uint32_t i) { return wires[i]; }    V selector(uint32_t i) { return consts[i]; }    V gate_const(uint32_t i) { return consts[num_selectors + i]; }
+  V imm(uint64_t x) { return EV{K(x), K(0)}; }    V pi(uint32_t i) { return EV{pis[i], K(0)}; }
+  S scalar(uint64_t x) { return K(x); }           S scalar_mul(S a, S b) { return A.mul(a, b); }
+  V add(V a, V b) { return A.eadd(a, b); }    V sub(V a, V b) { return A.esub(a, b); }    V mul(V a, V b) { return A.emul(a, b); }
+  V mul_add(V a, V b, V acc) { return A.emul_add(a, b, acc); }
+  V scale_add(V x, S s, V acc) { return A.escale_add(x, s, acc); }
+};
 
 // fri/verifier.rs compute_evaluation: the value at beta of the interpolant through the coset of x.  The points are
 // p_i = s g^i (s = the coset's first point), so with Z(X) = X^arity - s^arity the barycentric form is
@@ -372,8 +323,9 @@ void verify_proof(CircuitBuilder &B, const ProofWithPublicInputsTarget &pt, cons
       }
     }
     const SV pis[4] = {T(pi_hash[0]), T(pi_hash[1]), T(pi_hash[2]), T(pi_hash[3])};
-    std::vector<EV> gates;
-    eval_gates_ext(A, c, ow, oc, pis, alphas, gates);
+    ZetaTargets at_zeta{A, ow, oc, pis, c.num_selectors};
+    EV gates[gate_program::MAX_CHALLENGES];
+    gate_program::eval_gates_filtered(at_zeta, c.gates.data(), c.gates.size(), c.code.data(), c.imm.data(), c.num_selectors, alphas.data(), CH, gates);
     for (uint32_t k = 0; k < CH; k++) {
       EV acc = gates[k];
       for (size_t t = terms.size(); t-- > 0;) acc = A.escale_add(acc, alphas[k], terms[t]);

@@ -165,6 +165,17 @@ static void prove_and_verify(CircuitData &data, const PartialWitness &witness, I
   orc_circuit_free(oc);
 }
 
+// A circuit that verify_proof builds, pinned: the in-circuit verifier adds one gate per call of its target algebra, so walking the
+// inner gate programs in another order, or with a multiplication and an addition where one fused operation stood, builds another
+// circuit.  The oracle parity cannot see that (the oracle proves whatever circuit it is handed); the digest can.
+struct CircuitPin { uint64_t digest[4]; uint32_t degree_bits; size_t num_gates; };
+static void expect_circuit(const std::string &what, const CircuitPin &want, const uint64_t digest[4], uint32_t degree_bits, size_t num_gates) {
+  printf("%s: digest 0x%llx 0x%llx 0x%llx 0x%llx, 2^%u rows, %zu gates\n", what.c_str(), (unsigned long long)digest[0], (unsigned long long)digest[1],
+         (unsigned long long)digest[2], (unsigned long long)digest[3], degree_bits, num_gates);
+  if (memcmp(digest, want.digest, 32) != 0 || degree_bits != want.degree_bits || num_gates != want.num_gates)
+    throw std::runtime_error(what + ": verify_proof built another circuit than the pinned one");
+}
+
 static void prove_standalone(InnerProof &in, const PartialWitness &pw) {
   const CircuitDescription &D = in.data->description();
   if (g_gpu) {
@@ -719,13 +730,18 @@ static void recursive_verifier(bool with_sha, bool constant_vd, long tamper, boo
   PartialWitness pw;
   set_proof_with_pis_target(pw, pt, p);
   if (!constant_vd) set_verifier_data_target(pw, vd, dg, in.cap);
+  InnerProof outer;
   try {
-    prove_and_verify(*data, pw);
+    prove_and_verify(*data, pw, &outer);
   } catch (const UnsatisfiedError &e) {
     const bool pow_failed = std::string(e.what()).find("split_le: value does not fit in 16 bits") != std::string::npos;
     if (pow_failed != (tamper == 5)) throw std::runtime_error(std::string("the wrong check failed: ") + e.what());
     throw;
   }
+  // test_recursive_verifier's outer circuit, read at commit b984159 (before csrc/gate_program.hpp walked the programs); the
+  // standard config in both modes, so one circuit
+  static const CircuitPin pin = {{0x6fc2806b7e9f54a2ull, 0xf35328caee2a9c7aull, 0x3011123612b5f45aull, 0xc5ba53fe48a16283ull}, 13, 5403};
+  if (!with_sha && !constant_vd) expect_circuit("recursive verifier", pin, outer.digest, data->degree_bits(), rows);
 }
 static void test_recursive_verifier() { recursive_verifier(false, false, -1); }
 static void test_recursive_verifier_constant_verifier_data_sha_inner() { recursive_verifier(true, true, -1); }
@@ -789,6 +805,11 @@ static void wrap_chain(const CircuitConfig &first, const CircuitConfig &second, 
     InnerProof next;
     prove_and_verify(*w.data, pw, &next);
     if (next.proof.public_inputs != want_pis) throw std::runtime_error("wrap " + std::to_string(k + 1) + ": public inputs differ from the inner proof's");
+    // the two wrap circuits of cpu mode (rate_bits 4 and 5), read at commit b984159 like the pin in recursive_verifier; gpu mode
+    // wraps at rates 7 and 8, other circuits, which only the GPU can commit to
+    static const CircuitPin pins[2] = {{{0xd58e2c971bcdd9a4ull, 0x8131fd401571619cull, 0x0fc6b335df883911ull, 0x85e796ce0a435694ull}, 13, 5437},
+                                       {{0xfe3f76810bd61bb3ull, 0xa91ddb60224bfacbull, 0x08c07c487c36f660ull, 0x004b4ea9e4b7d990ull}, 13, 4474}};
+    if (!g_gpu) expect_circuit("wrap " + std::to_string(k + 1), pins[k], next.digest, w.data->degree_bits(), w.num_gates);
     printf("wrap %d: rate_bits %u cap_height %u, %zu gates, 2^%u rows, %zu -> %zu proof words, %lld s\n", k + 1, P.rate_bits, P.cap_height, w.num_gates,
            w.data->degree_bits(), level.proof.proof.size(), next.proof.proof.size(),
            (long long)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count());

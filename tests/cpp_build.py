@@ -7,6 +7,7 @@ CPP = os.path.join(ROOT, "tests", "cpp")
 HOST = os.path.join(ROOT, "eth-lc-plonky2_amd", "host")
 BIN = os.path.join(CPP, "test_gadgets")
 HOST_SOURCES = ("gates.cpp", "builder.cpp", "gadgets.cpp", "light_client_update.cpp", "poseidon_host.cpp", "recursion.cpp", "biguint.cpp")
+SHARED_HEADERS = [os.path.join(ROOT, "include", "lcp2.h"), os.path.join(ROOT, "eth-lc-plonky2_amd", "csrc", "gate_program.hpp")]  # what host/ includes from outside
 EXAMPLE_SRC = os.path.join(ROOT, "examples", "lc_prover.cpp")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "lc_prover")
 
@@ -23,8 +24,7 @@ def build():
     if not os.path.exists(hdr) or os.path.getmtime(hdr) < max(os.path.getmtime(gen), os.path.getmtime(kat), os.path.getmtime(lcu)):
         subprocess.run(["python3", gen, hdr], check=True)
     srcs = [os.path.join(CPP, "test_gadgets.cpp")] + [os.path.join(HOST, f) for f in HOST_SOURCES]
-    deps = srcs + [hdr] + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".hpp")] + [
-        os.path.join(ROOT, "include", "lcp2.h"), os.path.join(ROOT, "oracle", "plonk.h")]
+    deps = srcs + [hdr] + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".hpp")] + SHARED_HEADERS + [os.path.join(ROOT, "oracle", "plonk.h")]
     if not os.path.exists(BIN) or any(os.path.getmtime(d) > os.path.getmtime(BIN) for d in deps):
         pkg, orc = os.path.join(ROOT, "eth-lc-plonky2_amd"), os.path.join(ROOT, "oracle")
         subprocess.run(["g++", "-O2", "-std=c++17", "-o", BIN] + srcs + ["-L", pkg, "-llcp2", "-L", orc, "-loracle",
@@ -43,7 +43,7 @@ def build_example():
     import eth_lc_plonky2_amd as m
     m.build_native()
     srcs = [EXAMPLE_SRC] + [os.path.join(HOST, f) for f in HOST_SOURCES]
-    deps = srcs + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "lcp2.h")]
+    deps = srcs + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".hpp")] + SHARED_HEADERS
     if not os.path.exists(EXAMPLE_BIN) or any(os.path.getmtime(d) > os.path.getmtime(EXAMPLE_BIN) for d in deps):
         pkg = os.path.join(ROOT, "eth-lc-plonky2_amd")
         subprocess.run(["g++", "-O2", "-std=c++17", "-o", EXAMPLE_BIN] + srcs + ["-L", pkg, "-llcp2", "-Wl,-rpath," + pkg], check=True)

@@ -89,6 +89,33 @@ def test_hand_written_rules():
     for t in (sbox_of_product, emitbool_doubles, muladd_keeps_the_larger):
         assert tier_lib.program_degree(prog(t)) == _degree(m, prog(t))[1]
 
+    # saturation: degrees stop at 2^20.  7^7 = 823543 is the last power of 7 below it; the expected numbers are tier_lib's
+    def sbox_chain(n, then):
+        def build(a):
+            x = W(0)
+            for _ in range(n):
+                x = a.sbox(x, 5)
+            then(a, x)
+        return build
+
+    def muladd_into_saturated(a, x):   # dst at the cap, product of degree 2: the cap stays
+        a.muladd(x, W(1), W(2))
+        a.emit(x)
+
+    def product_of_saturated(a, x):    # cap + cap, and the XOR of the result with a wire
+        a.emit(a.xor(a.mul(x, x), W(1)))
+    cap = 1 << 20
+    for build, want in [(sbox_chain(7, lambda a, x: a.emit(x)), 7 ** 7),                   # below the cap: exact
+                        (sbox_chain(7, lambda a, x: a.emit_bool(x)), cap),                 # 2 * 7^7 is past it
+                        (sbox_chain(8, lambda a, x: a.emit(x)), cap),                      # 7^8 is past it
+                        (sbox_chain(8, lambda a, x: a.emit_bool(x)), cap),                 # twice the cap is the cap
+                        (sbox_chain(12, lambda a, x: a.emit_bool(x)), cap),                # and stays there (7^12 would pass 2^32)
+                        (sbox_chain(8, muladd_into_saturated), cap),
+                        (sbox_chain(8, product_of_saturated), cap),
+                        (sbox_chain(2, muladd_into_saturated), 49)]:                       # MULADD into a register of a higher degree
+        assert tier_lib.program_degree(prog(build)) == want
+        assert _degree(m, prog(build)) == (0, want)
+
 
 def test_host_layer_gate_set_against_gate_degree():
     """host/gates.cpp: the derived degree of every program of build_gate_set equals GATE_DEGREE, the four SHA-256 gates (XOR, EMITBOOL

@@ -12,6 +12,8 @@ import tempfile
 
 import numpy as np
 
+import gate_program_ref
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "eth-lc-plonky2_amd", "csrc")
 DUMP = os.path.join(ROOT, "tools", "gen", "reference_gate_programs.txt")
@@ -84,33 +86,7 @@ def test_generated_schedules_fit_their_register_budget():
 # ---------------------------------------------------------------- generated evaluators on the CPU against the programs
 def _interpret(code, imm, wires, consts, pis, forward, alpha):
     """include/lcp2.h semantics over Python integers -> sum_j alpha^j constraint_j"""
-    reg = [0] * 256
-    emitted = []
-
-    def operand(kind, idx):  # 0 REG, 1 WIRE, 2 CONST (gate constant, after the selector columns), 3 IMM, 4 PI
-        return (reg, wires, consts, imm, pis)[kind][idx]
-
-    MDS_CIRC = [17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20]
-    for pc in range(len(code) // 2):
-        w0, w1 = int(code[2 * pc]), int(code[2 * pc + 1])
-        op, dst, ka, kb, ia, ib = w0 & 0xF, (w0 >> 8) & 0xFF, (w0 >> 16) & 0xF, (w0 >> 20) & 0xF, w1 & 0xFFFF, w1 >> 16
-        if op == 9:
-            src = [reg[ia + j] for j in range(12)]
-            for r in range(12):
-                reg[dst + r] = (sum(src[(i + r) % 12] * MDS_CIRC[i] for i in range(12)) + (8 * src[0] if r == 0 else 0) + imm[ib + r]) % P
-            continue
-        x = operand(ka, ia)
-        if op == 3:
-            emitted.append(x)
-            continue
-        if op == 6:
-            emitted.append((x * x - x) % P)
-            continue
-        if op == 8:
-            reg[dst] = pow(x, 7, P)
-            continue
-        y = operand(kb, ib)
-        reg[dst] = {0: x + y, 1: x - y, 2: x * y, 4: x + y - 2 * x * y, 5: 2 * x + y, 7: reg[dst] + x * y}[op] % P
+    emitted = gate_program_ref.emitted_constraints(code, imm, wires, consts, pis)
     if not forward:
         emitted.reverse()
     return sum(c * pow(alpha, j, P) for j, c in enumerate(emitted)) % P

@@ -1,5 +1,7 @@
 """Host logic without a GPU: the product's verifier (lcp2_verify, host-only C++) must accept proofs
 made by the oracle prover and reject tampered ones; the proof layout of both sides must agree."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -141,17 +143,41 @@ def test_verifier_create_validates_gate_programs(oracle):
     circ, wires, pis = m.circuit.synthetic_circuit(params, seed=3)
     oc = oracle_lib.OracleCircuit(oracle, circ)
     digest, cap = oc.digest()
-    code = circ.gateset.code
-    first = next(g for g in circ.gateset.gates if g.code_len).code_offset
+    gs, cm = circ.gateset, m.circuit
+    code = gs.code
+    gate = next(g for g in gs.gates if g.code_len)
+    first = gate.code_offset
     saved = (int(code[2 * first]), int(code[2 * first + 1]))
+    assert saved[0] & 0xF not in (cm.OP_EMIT, cm.OP_EMITBOOL)   # the replacements emit nothing either: num_constraints still matches
+    lib = m.load_library()
+
+    def degree_status():
+        """the same program through lcp2_gate_program_degree, which knows the register count and no other table"""
+        w = np.ascontiguousarray(code[2 * first:2 * (first + gate.code_len)], dtype=np.uint32)
+        out = ctypes.c_uint32(0)
+        return lib.lcp2_gate_program_degree(w.ctypes.data_as(ctypes.c_void_p), w.size // 2, gs.max_regs, ctypes.byref(out))
+
+    def add(kind, idx):
+        return (cm.OP_ADD | kind << 16 | cm.K_REG << 20, idx)
+    assert degree_status() == 0
+    # (instruction, whether a check of the registers alone can see it): both entry points go through the one validation and must
+    # refuse the first four; the rest name a table that only a circuit description has, so the degree entry point accepts them
+    table = [(((saved[0] & ~0xF) | 15, saved[1]), True),                                            # unknown opcode
+             (((saved[0] & ~0xFF00) | (200 << 8), saved[1]), True),                                 # destination register out of range
+             ((cm.OP_PMDS | 60 << 8 | cm.K_REG << 16 | cm.K_IMM << 20, 0), True),                   # PMDS window past the registers
+             (add(7, 0), True),                                                                     # no such operand kind
+             (add(cm.K_WIRE, 0xFFFF), False),                                                       # wire operand out of range
+             (add(cm.K_CONST, 0xFFFF), False),                                                      # gate constant out of range
+             (add(cm.K_IMM, 0xFFFF), False),                                                        # immediate out of range
+             (add(cm.K_PI, 4), False)]                                                              # public_inputs_hash has 4 words
+    assert gs.max_regs <= 64 and len(gs.imm) < 0xFFFF
     try:
-        for w0, w1 in [((saved[0] & ~0xF) | 15, saved[1]),                   # unknown opcode
-                       ((saved[0] & ~0xFF00) | (200 << 8), saved[1]),         # destination register out of range
-                       ((saved[0] & ~0xF0000) | (1 << 16), 0xFFFF)]:          # wire operand out of range
+        for (w0, w1), registers_only in table:
             code[2 * first], code[2 * first + 1] = w0, w1
             with pytest.raises(m.Lcp2Error) as e:
                 m.CircuitData.verifier_only(circ, digest, cap)
             assert e.value.status == -1
+            assert (degree_status() != 0) == registers_only, (hex(w0), hex(w1))
     finally:
         code[2 * first], code[2 * first + 1] = saved
     m.CircuitData.verifier_only(circ, digest, cap).close()

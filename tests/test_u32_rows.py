@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import gate_program_ref as ref
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "emu", "emu_u32.cpp")
 LIB = os.path.join(HERE, "emu", "libemu_u32.so")
@@ -157,22 +159,10 @@ def constraints(gs, name, row):
     """the constraints a gate's program (include/lcp2.h instruction set, the arithmetic subset these gates use) emits on one row"""
     g = gs.gates[gs.index(name)]
     code, imm = gs.code[2 * g.code_offset:2 * (g.code_offset + g.code_len)], gs.imm
-    reg, emitted = [0] * 256, []
-    for pc in range(len(code) // 2):
-        w0, w1 = int(code[2 * pc]), int(code[2 * pc + 1])
-        op, dst, ka, kb, ia, ib = w0 & 0xF, (w0 >> 8) & 0xFF, (w0 >> 16) & 0xF, (w0 >> 20) & 0xF, w1 & 0xFFFF, w1 >> 16
-
-        def operand(kind, idx):
-            assert kind in (0, 1, 3), kind   # REG, WIRE, IMM
-            return int((reg, row, None, imm)[kind][idx])
-
-        x = operand(ka, ia)
-        if op == 3:
-            emitted.append(x % P)
-            continue
-        y = operand(kb, ib)
-        assert op in (0, 1, 2), op
-        reg[dst] = {0: x + y, 1: x - y, 2: x * y}[op] % P
+    for op, _, kinds, _ in ref.decode(code):
+        assert op in (ref.OP_ADD, ref.OP_SUB, ref.OP_MUL, ref.OP_EMIT), op
+        assert all(k in (ref.KIND_REG, ref.KIND_WIRE, ref.KIND_IMM) for k in kinds[:ref.num_sources(op)]), kinds
+    emitted = ref.emitted_constraints(code, imm, row, None, None)
     assert len(emitted) == g.num_constraints
     return emitted
 

@@ -3,34 +3,7 @@ lcp2_gate_program_degree, lcp2_circuit_gate_tiers), for the tests that hold the 
 import os
 import subprocess
 
-OP_ADD, OP_SUB, OP_MUL, OP_EMIT, OP_XOR, OP_DBLADD, OP_EMITBOOL, OP_MULADD, OP_SBOX, OP_PMDS = range(10)
-
-
-def program_degree(words, num_regs=64):
-    """degree bound of a program (a flat list of two-word instructions): WIRE / CONST 1, IMM / PI 0, ADD / SUB / DBLADD max,
-    MUL / XOR sum, MULADD max(dst, sum), SBOX 7 x, PMDS max of its window, EMIT the operand, EMITBOOL twice; max over the emits"""
-    reg, deg = [0] * max(num_regs, 1), 0
-    for pc in range(0, len(words), 2):
-        w0, w1 = int(words[pc]), int(words[pc + 1])
-        op, dst, kinds, idx = w0 & 0xF, (w0 >> 8) & 0xFF, ((w0 >> 16) & 0xF, (w0 >> 20) & 0xF), (w1 & 0xFFFF, w1 >> 16)
-
-        def of(k):
-            return reg[idx[k]] if kinds[k] == 0 else 1 if kinds[k] in (1, 2) else 0
-        if op == OP_PMDS:
-            reg[dst:dst + 12] = [max(reg[idx[0]:idx[0] + 12])] * 12
-        elif op == OP_EMIT:
-            deg = max(deg, of(0))
-        elif op == OP_EMITBOOL:
-            deg = max(deg, 2 * of(0))
-        elif op == OP_SBOX:
-            reg[dst] = 7 * of(0)
-        elif op in (OP_MUL, OP_XOR):
-            reg[dst] = of(0) + of(1)
-        elif op == OP_MULADD:
-            reg[dst] = max(reg[dst], of(0) + of(1))
-        else:
-            reg[dst] = max(of(0), of(1))
-    return deg
+from gate_program_ref import program_degree  # noqa: F401  (the rule itself; the bundle logic below builds on it)
 
 
 def gateset_degrees(gs):
@@ -74,8 +47,8 @@ def build_tiers_binary():
     cpp_build.build()   # liblcp2.so, liboracle.so, golden_data.hpp
     src = os.path.join(cpp_build.CPP, "test_tiers.cpp")
     srcs = [src] + [os.path.join(cpp_build.HOST, f) for f in cpp_build.HOST_SOURCES]
-    deps = srcs + [os.path.join(cpp_build.HOST, f) for f in os.listdir(cpp_build.HOST) if f.endswith(".hpp")] + [
-        os.path.join(ROOT, "include", "lcp2.h"), os.path.join(ROOT, "oracle", "plonk.h"), os.path.join(cpp_build.CPP, "golden_data.hpp")]
+    deps = srcs + [os.path.join(cpp_build.HOST, f) for f in os.listdir(cpp_build.HOST) if f.endswith(".hpp")] + cpp_build.SHARED_HEADERS + [
+        os.path.join(ROOT, "oracle", "plonk.h"), os.path.join(cpp_build.CPP, "golden_data.hpp")]
     if not os.path.exists(TIERS_BIN) or any(os.path.getmtime(d) > os.path.getmtime(TIERS_BIN) for d in deps):
         pkg, orc = os.path.join(ROOT, "eth-lc-plonky2_amd"), os.path.join(ROOT, "oracle")
         subprocess.run(["g++", "-O2", "-std=c++17", "-o", TIERS_BIN] + srcs + ["-L", pkg, "-llcp2", "-L", orc, "-loracle",

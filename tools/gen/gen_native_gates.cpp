@@ -27,6 +27,7 @@
 #include <set>
 #include <string>
 #include <vector>
+#include "../../eth-lc-plonky2_amd/csrc/gate_program.hpp"
 #include "../../eth-lc-plonky2_amd/host/host_internal.hpp"
 
 using namespace lc;
@@ -92,10 +93,10 @@ static bool build_nodes(const Program &P, std::vector<Node> &nodes, std::set<std
   const bool fwd = (P.flags & LCP2_GATE_EMIT_FORWARD) != 0;
   uint32_t emitted = 0;
   for (size_t pc = 0; pc < P.code.size() / 2; pc++) {
-    const uint32_t w0 = P.code[2 * pc], w1 = P.code[2 * pc + 1], op = w0 & 0xF, dst = (w0 >> 8) & 0xFF;
-    const uint32_t kk[2] = {(w0 >> 16) & 0xF, (w0 >> 20) & 0xF}, ii[2] = {w1 & 0xFFFF, w1 >> 16};
-    const bool emits = op == LCP2_OP_EMIT || op == LCP2_OP_EMITBOOL;
-    if (op == LCP2_OP_PMDS) {
+    const gate_program::Insn in(P.code[2 * pc], P.code[2 * pc + 1]);
+    const uint32_t op = in.op, dst = in.dst, *kk = in.kind, *ii = in.idx;
+    const bool emits = in.emits();
+    if (in.pmds()) {
       if (!P.rewrite) { fprintf(stderr, "generator: PMDS in a program without rewriting\n"); return false; }
       std::vector<int> window(12);
       for (int j = 0; j < 12; j++) window[j] = cur[ii[0] + j];
@@ -118,16 +119,16 @@ static bool build_nodes(const Program &P, std::vector<Node> &nodes, std::set<std
     n.op = op;
     std::string *out[2] = {&n.a, &n.b};
     int *outn[2] = {&n.na, &n.nb};
-    for (int s = 0; s < (emits ? 1 : 2); s++) {
+    for (int s = 0; s < in.nsrc(); s++) {
       char buf[64];
       switch (kk[s]) {
-        case 0:
+        case gate_program::KIND_REG:
           if (cur[ii[s]] < 0) { snprintf(buf, sizeof buf, "0ull"); (s ? n.imm_b : n.imm_a) = true; }
           else { snprintf(buf, sizeof buf, "v%d", cur[ii[s]]); n.deps.push_back(cur[ii[s]]); *outn[s] = cur[ii[s]]; }
           break;
-        case 1: snprintf(buf, sizeof buf, "w%u", ii[s]); n.loads.push_back(buf); break;
-        case 2: snprintf(buf, sizeof buf, "k%u", ii[s]); n.loads.push_back(buf); break;
-        case 3:
+        case gate_program::KIND_WIRE: snprintf(buf, sizeof buf, "w%u", ii[s]); n.loads.push_back(buf); break;
+        case gate_program::KIND_CONST: snprintf(buf, sizeof buf, "k%u", ii[s]); n.loads.push_back(buf); break;
+        case gate_program::KIND_IMM:
           snprintf(buf, sizeof buf, "0x%llxull", (unsigned long long)(*P.imm)[ii[s]]);
           (s ? n.imm_b : n.imm_a) = true;
           (s ? n.vb : n.va) = (*P.imm)[ii[s]];
