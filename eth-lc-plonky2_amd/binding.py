@@ -64,6 +64,24 @@ U32_ARITHMETIC, U32_ADD_MANY, U32_SUBTRACTION, U32_RANGE_CHECK, U32_COMPARISON =
 U32_JOB_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u2"), ("op", "<u2"), ("in", "<u4", (4,))])   # U32Job as a numpy record
 assert U32_JOB_DTYPE.itemsize == ctypes.sizeof(U32Job) == 24
 
+class RecOperand(ctypes.Structure):
+    """lcp2_rec_operand: an immediate value, or a cell (row v, column col) of the witness matrix (lcp2_rec_gate_rows)"""
+    _fields_ = [("v", ctypes.c_uint64), ("col", ctypes.c_uint32), ("src", ctypes.c_uint32)]
+
+
+class RecJob(ctypes.Structure):
+    """lcp2_rec_job: one operation of a recursion-gate row; its operands start at operands[first_operand]"""
+    _fields_ = [("row", ctypes.c_uint32), ("kind", ctypes.c_uint16), ("op", ctypes.c_uint16), ("first_operand", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+(REC_ARITHMETIC, REC_BASE_SUM, REC_ARITHMETIC_EXT, REC_MUL_EXT, REC_REDUCING, REC_REDUCING_EXT, REC_POSEIDON_MDS, REC_RANDOM_ACCESS,
+ REC_EXPONENTIATION, REC_COSET_INTERPOLATION, REC_KINDS) = range(11)
+REC_IMM, REC_CELL = 0, 1
+REC_OPERAND_DTYPE = np.dtype([("v", "<u8"), ("col", "<u4"), ("src", "<u4")])   # RecOperand as a numpy record
+REC_JOB_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u2"), ("op", "<u2"), ("first_operand", "<u4"), ("reserved", "<u4")])
+assert REC_OPERAND_DTYPE.itemsize == ctypes.sizeof(RecOperand) == 16 and REC_JOB_DTYPE.itemsize == ctypes.sizeof(RecJob) == 16
+
 _lib = None
 
 
@@ -125,6 +143,8 @@ def load_library():
         "lcp2_scatter_cells": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint64]),
         "lcp2_poseidon_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint64]),
         "lcp2_u32_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.c_uint64]),
+        "lcp2_rec_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p,
+                                         c.c_uint32, c.c_uint64]),
         "lcp2_commit_wires_rows_begin": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_commit_wires_chunk": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32]),
         "lcp2_commit_wires_rows_finish": (c.c_int, [c.c_void_p, c.c_void_p]),
@@ -411,6 +431,27 @@ class Context:
                 raise Lcp2Error(-1, "a device job list needs njobs")
             count, p, mem = int(njobs), ctypes.c_void_p(jobs), MEM_DEVICE
         self._check(self.lib.lcp2_u32_gate_rows(self.handle, p, count, mem, ctypes.c_void_p(wires_dev), n))
+
+    def rec_gate_rows(self, jobs, operands, level_ends, wires_dev, ncols, n, njobs=None, noperands=None):
+        """lcp2_rec_gate_rows: runs the recorded plan level by level on the device witness matrix `wires_dev` (a pointer,
+        [ncols >= 135][n] column-major).  jobs / operands: numpy arrays of REC_JOB_DTYPE / REC_OPERAND_DTYPE records (host lists:
+        validated before anything runs), or two device pointers with `njobs` and `noperands` (validated by the kernel).
+        level_ends: the index after the last job of every level, always on the host.  recursion_gates.witness_jobs and
+        chain_plan return such lists in the fast order (kind, op, row) inside each level."""
+        ends = np.ascontiguousarray(level_ends, dtype=np.uint32).ravel()
+        if isinstance(jobs, np.ndarray) != isinstance(operands, np.ndarray):
+            raise Lcp2Error(-1, "jobs and operands must both be host arrays or both be device pointers")
+        if isinstance(jobs, np.ndarray):
+            if jobs.dtype != REC_JOB_DTYPE or operands.dtype != REC_OPERAND_DTYPE:
+                raise Lcp2Error(-1, "jobs / operands must be arrays of REC_JOB_DTYPE / REC_OPERAND_DTYPE records")
+            j, o = np.ascontiguousarray(jobs).ravel(), np.ascontiguousarray(operands).ravel()
+            nj, no, pj, po, mem = j.size, o.size, _ptr(j), _ptr(o), MEM_HOST
+        else:
+            if njobs is None or noperands is None:
+                raise Lcp2Error(-1, "device lists need njobs and noperands")
+            nj, no, pj, po, mem = int(njobs), int(noperands), ctypes.c_void_p(jobs), ctypes.c_void_p(operands), MEM_DEVICE
+        self._check(self.lib.lcp2_rec_gate_rows(self.handle, pj, nj, po, no, _ptr(ends) if ends.size else None, ends.size, mem,
+                                                ctypes.c_void_p(wires_dev), int(ncols), int(n)))
 
     def buffer_alloc(self, words):
         p = ctypes.c_void_p()

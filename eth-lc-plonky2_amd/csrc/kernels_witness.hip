@@ -14,6 +14,7 @@
 #include "poseidon.hpp"
 #include "prover_kernels.hpp"
 #include "u32_rows.hpp"
+#include "rec_rows.hpp"
 
 namespace lcp2 {
 
@@ -240,6 +241,31 @@ void launch_u32_gate_rows(hipStream_t s, const U32JobDev *jobs, u64 njobs, u64 *
   if (!njobs) return;
   hipLaunchKernelGGL(k_u32_gate_rows, dim3((unsigned)((njobs + U32_ROWS_THREADS - 1) / U32_ROWS_THREADS)), dim3(U32_ROWS_THREADS), 0, s,
                      jobs, njobs, wires, n, flag);
+}
+
+// One lane per job of one LEVEL of lcp2_rec_gate_rows: one operation of a recursion-gate row (rec_rows.hpp rec_job_cells: the text
+// tests/emu/emu_rec.cpp runs on the CPU).  A lane reads its 16-byte job, then its operands one after the other as the per-kind
+// function asks for them - an IMM operand is the 16-byte record itself, a CELL operand one more 8-byte load from the matrix - and
+// writes each cell with one 8-byte store into its column; as in k_u32_gate_rows a store of a wave is contiguous when its 64 jobs
+// are consecutive rows of one (kind, op).  The operands do NOT go through LDS: a lane's operand records are read once, by that
+// lane alone, in order (no reuse across lanes or waves to stage for), the long kinds hold at most two extension elements between
+// operands, and the records of one lane are consecutive, so the 16-byte loads of a lane walk whole cache lines; a round trip
+// through LDS would add instructions and a barrier to a kernel whose long kinds are bound by 43 / 66 / 16 DEPENDENT extension
+// multiplies per lane, which LDS cannot shorten.  The long kinds stay one lane per job; a sorted list keeps a wave on one kind.
+// The flag word is folded with a minimum, so it names the first refused job; lanes of a level after that job's return at once.
+constexpr u32 REC_ROWS_THREADS = 256;
+__global__ __launch_bounds__(REC_ROWS_THREADS) void k_rec_gate_rows(const RecJobDev *__restrict__ jobs, u64 base, u64 begin, u64 end,
+                                                                     const RecOperandDev *__restrict__ operands, u64 noperands, u64 *wires,
+                                                                     u32 ncols, u64 n, u64 *flag, int check_structure) {
+  const u64 i = begin + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 problem = rec_rows_lane(jobs, base, begin, end, i, operands, noperands, wires, ncols, n, flag, check_structure != 0);
+  if (problem) atomicMin((unsigned long long *)flag, (unsigned long long)(i << 8 | problem));
+}
+void launch_rec_gate_rows(hipStream_t s, const RecJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
+                          u64 *wires, u32 ncols, u64 n, u64 *flag, bool check_structure) {
+  if (begin >= end) return;
+  hipLaunchKernelGGL(k_rec_gate_rows, dim3((unsigned)((end - begin + REC_ROWS_THREADS - 1) / REC_ROWS_THREADS)), dim3(REC_ROWS_THREADS), 0, s,
+                     jobs, base, begin, end, operands, noperands, wires, ncols, n, flag, check_structure ? 1 : 0);
 }
 
 void launch_sha_jobs_level(hipStream_t s, const ShaJobDev *jobs, u32 first, u32 count, const uint32_t *words_in, uint32_t *rec) {

@@ -7,6 +7,7 @@
 #include "sha_layout.hpp"
 #include "prover_kernels.hpp"
 #include "u32_rows.hpp"
+#include "rec_rows.hpp"
 
 using namespace lcp2;
 
@@ -676,6 +677,90 @@ extern "C" int lcp2_u32_gate_rows(lcp2_ctx *ctx, const lcp2_u32_job *jobs, size_
   LCP2_HIP(ctx, hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
   LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's list may go; every cell is written
   if (flag) return ctx->fail(LCP2_E_INVALID, "u32 rows: job " + std::to_string(flag - 1) + " of the device list is invalid (row, kind, operation slot or borrow); the valid jobs are written");
+  return LCP2_OK;
+}
+
+// Recursion-gate rows, level by level.  A host list is validated here before anything is queued (structure of every job, and the
+// value conditions of the operands that are IMM); its operands go up whole, before any job, and its jobs in pieces of the pinned
+// staging buffer's size.  A piece may end inside a level: the jobs of a level do not depend on one another, so the level is then two
+// launches, and a piece that holds the end of one level and the start of the next launches them apart, in order.  A device list is
+// validated by the kernel.  Either way the value conditions of CELL operands can only be seen on the device: the flag word is
+// read once, after the last level, because a level that begins after a refused job writes nothing (rec_rows_lane).
+static int rec_stage(lcp2_ctx *ctx, void *dst, const void *src, size_t bytes) {  // host -> device through the pinned buffer, reusable on return
+  if (!ctx->pin) {
+    LCP2_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LCP2_OK;
+  }
+  for (size_t at = 0; at < bytes; at += lcp2_ctx::PIN_BYTES) {
+    const size_t piece = std::min(lcp2_ctx::PIN_BYTES, bytes - at);
+    LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the copy out of the staging buffer that may still be in flight
+    memcpy(ctx->pin, (const char *)src + at, piece);
+    LCP2_HIP(ctx, hipMemcpyAsync((char *)dst + at, ctx->pin, piece, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return LCP2_OK;
+}
+
+extern "C" int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_t njobs, const lcp2_rec_operand *operands, size_t noperands,
+                                  const uint32_t *level_ends, size_t nlevels, lcp2_mem lists_mem, uint64_t *wires, uint32_t ncols, uint64_t n) {
+  static_assert(sizeof(lcp2_rec_job) == 16 && sizeof(lcp2_rec_job) == sizeof(RecJobDev) && sizeof(lcp2_rec_operand) == 16 &&
+                sizeof(lcp2_rec_operand) == sizeof(RecOperandDev), "record layouts must agree");
+  static_assert(LCP2_REC_ARITHMETIC == REC_ARITHMETIC && LCP2_REC_BASE_SUM == REC_BASE_SUM && LCP2_REC_ARITHMETIC_EXT == REC_ARITHMETIC_EXT &&
+                LCP2_REC_MUL_EXT == REC_MUL_EXT && LCP2_REC_REDUCING == REC_REDUCING && LCP2_REC_REDUCING_EXT == REC_REDUCING_EXT &&
+                LCP2_REC_POSEIDON_MDS == REC_POSEIDON_MDS && LCP2_REC_RANDOM_ACCESS == REC_RANDOM_ACCESS &&
+                LCP2_REC_EXPONENTIATION == REC_EXPONENTIATION && LCP2_REC_COSET_INTERPOLATION == REC_COSET_INTERPOLATION &&
+                LCP2_REC_KINDS == REC_KINDS && LCP2_REC_IMM == REC_IMM && LCP2_REC_CELL == REC_CELL, "numbering must agree");
+  if (!ctx || !wires || (njobs && (!jobs || !level_ends || !nlevels)) || (noperands && !operands)) return LCP2_E_INVALID;
+  if (lists_mem != LCP2_MEM_HOST && lists_mem != LCP2_MEM_DEVICE) return ctx->fail(LCP2_E_INVALID, "rec rows: bad lcp2_mem");
+  if (!njobs) return LCP2_OK;
+  if (ncols < REC_ROW_COLUMNS) return ctx->fail(LCP2_E_INVALID, "rec rows: the matrix needs at least 135 columns");
+  for (size_t l = 0; l < nlevels; l++)
+    if (level_ends[l] < (l ? level_ends[l - 1] : 0) || level_ends[l] > njobs)
+      return ctx->fail(LCP2_E_INVALID, "rec rows: level_ends is not ascending at level " + std::to_string(l));
+  if (level_ends[nlevels - 1] != njobs) return ctx->fail(LCP2_E_INVALID, "rec rows: level_ends does not end at njobs");
+  const RecJobDev *list = (const RecJobDev *)jobs;
+  const RecOperandDev *ops = (const RecOperandDev *)operands;
+  const bool host = lists_mem == LCP2_MEM_HOST;
+  if (host)
+    for (size_t i = 0; i < njobs; i++) {
+      u32 problem = rec_job_problem(list[i], ops, noperands, ncols, n);
+      const int checked = problem ? -1 : rec_value_operand(list[i].kind, list[i].op);
+      if (checked >= 0 && ops[(size_t)list[i].first_operand + checked].src == REC_IMM)
+        problem = rec_value_problem(list[i].kind, gl_canon(ops[(size_t)list[i].first_operand + checked].v));
+      if (problem) return ctx->fail(LCP2_E_INVALID, "rec rows: job " + std::to_string(i) + ": " + rec_problem_str(problem));
+    }
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  void *d_flag;
+  LCP2_TRY(scratch_ensure(ctx, 1, sizeof(u64), &d_flag));
+  LCP2_HIP(ctx, hipMemsetAsync(d_flag, 0xFF, sizeof(u64), ctx->stream));  // REC_NO_PROBLEM
+  if (!host) {
+    for (size_t l = 0; l < nlevels; l++)
+      launch_rec_gate_rows(ctx->stream, list, 0, l ? level_ends[l - 1] : 0, level_ends[l], ops, noperands, (u64 *)wires, ncols, n, (u64 *)d_flag, true);
+  } else {
+    constexpr size_t PIECE = lcp2_ctx::PIN_BYTES / sizeof(lcp2_rec_job);  // jobs
+    void *d_jobs, *d_ops;
+    LCP2_TRY(scratch_ensure(ctx, 0, std::min(njobs, PIECE) * sizeof(lcp2_rec_job), &d_jobs));
+    LCP2_TRY(scratch_ensure(ctx, 2, std::max<size_t>(noperands, 1) * sizeof(lcp2_rec_operand), &d_ops));
+    if (noperands) LCP2_TRY(rec_stage(ctx, d_ops, ops, noperands * sizeof(lcp2_rec_operand)));  // before the jobs that use them
+    size_t level = 0;
+    for (size_t at = 0; at < njobs; at += PIECE) {
+      const size_t stop = std::min(njobs, at + PIECE);
+      LCP2_TRY(rec_stage(ctx, d_jobs, list + at, (stop - at) * sizeof(lcp2_rec_job)));  // (waits for the launches of the piece before)
+      for (; level < nlevels; level++) {  // the part of every level that lies in [at, stop)
+        const size_t begin = std::max<size_t>(level ? level_ends[level - 1] : 0, at), end = std::min<size_t>(level_ends[level], stop);
+        launch_rec_gate_rows(ctx->stream, (const RecJobDev *)d_jobs, at, begin, end, (const RecOperandDev *)d_ops, noperands, (u64 *)wires, ncols, n,
+                             (u64 *)d_flag, false);
+        if (level_ends[level] > stop) break;  // the level goes on in the next piece
+      }
+    }
+  }
+  LCP2_HIP(ctx, hipGetLastError());
+  u64 flag = 0;
+  LCP2_HIP(ctx, hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+  LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's lists may go; every cell is written
+  if (flag != REC_NO_PROBLEM)
+    return ctx->fail(LCP2_E_INVALID, "rec rows: job " + std::to_string(flag >> 8) + ": " + rec_problem_str(flag & 0xFF) +
+                                         " (found on the device: the valid jobs of its level and of the levels before are written, later levels are not)");
   return LCP2_OK;
 }
 

@@ -163,6 +163,14 @@ void launch_fill(hipStream_t s, u64 *p, u64 n, u64 v);
 // job, which writes nothing
 struct U32JobDev;
 void launch_u32_gate_rows(hipStream_t s, const U32JobDev *jobs, u64 njobs, u64 *wires, u64 n, u64 *flag);
+// lcp2_rec_gate_rows (kernels_witness.hip k_rec_gate_rows, rec_rows.hpp): the jobs [begin, end) of one level, one lane each; jobs[0]
+// is job `base` of the list (begin >= base); operands: the WHOLE operand list; wires [ncols >= 135][n].  *flag (device, set to
+// REC_NO_PROBLEM = ~0 by the caller) receives the minimum of (index << 8 | problem) over the refused jobs, which write nothing; a
+// launch whose level begins after the job the flag names writes nothing at all
+struct RecJobDev;
+struct RecOperandDev;
+void launch_rec_gate_rows(hipStream_t s, const RecJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
+                          u64 *wires, u32 ncols, u64 n, u64 *flag, bool check_structure);
 // *flag = 1 if a word of p[r * pitch + i] (r < rows, i < width) is a non-zero field element (flag zeroed by the caller)
 void launch_any_nonzero(hipStream_t s, const u64 *p, u64 pitch, u64 width, u32 rows, unsigned long long *flag);
 

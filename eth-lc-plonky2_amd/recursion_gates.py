@@ -331,3 +331,360 @@ def recursion_gates_circuit(params, seed, native=True):
     sig = sigma_values(np.tile(rows, (NR, 1)), np.tile(np.arange(NR)[:, None], (1, n)), k_is, params.degree_bits)
     cs = np.concatenate([gs.selector_columns(gate_of_row), c0[None, :], c1[None, :], sig])
     return Circuit(params, gs, cs, k_is, 0), wires, np.zeros(0, dtype=np.uint64)
+
+
+# ---------------------------------------------------------------- jobs of lcp2_rec_gate_rows: one operation of one row each
+from types import SimpleNamespace  # noqa: E402
+
+from .binding import (REC_ARITHMETIC, REC_ARITHMETIC_EXT, REC_BASE_SUM, REC_CELL, REC_COSET_INTERPOLATION, REC_EXPONENTIATION,  # noqa: E402
+                      REC_IMM, REC_JOB_DTYPE, REC_MUL_EXT, REC_OPERAND_DTYPE, REC_POSEIDON_MDS, REC_RANDOM_ACCESS, REC_REDUCING,
+                      REC_REDUCING_EXT)
+from .circuit import ARITH_OPS, BASE_SUM_LIMBS, gate_arithmetic, gate_base_sum  # noqa: E402
+
+RA_VEC = 1 << RANDOM_ACCESS_BITS
+RA_ROUTED = (2 + RA_VEC) * RANDOM_ACCESS_COPIES + RANDOM_ACCESS_EXTRA
+REC_ROW_COLUMNS = 135
+# kind -> (gate name, operations per row, operands of operation `op`)
+REC_JOB_KINDS = {
+    REC_ARITHMETIC: ("ArithmeticGate", ARITH_OPS, lambda op: 5),
+    REC_BASE_SUM: ("BaseSumGate", 1, lambda op: 1),
+    REC_ARITHMETIC_EXT: ("ArithmeticExtensionGate", ARITH_EXT_OPS, lambda op: 8),
+    REC_MUL_EXT: ("MulExtensionGate", MUL_EXT_OPS, lambda op: 5),
+    REC_REDUCING: ("ReducingGate", 1, lambda op: 4 + REDUCING_COEFFS),
+    REC_REDUCING_EXT: ("ReducingExtensionGate", 1, lambda op: 4 + 2 * REDUCING_EXT_COEFFS),
+    REC_POSEIDON_MDS: ("PoseidonMdsGate", 1, lambda op: 24),
+    REC_RANDOM_ACCESS: ("RandomAccessGate", RANDOM_ACCESS_COPIES + 1, lambda op: 1 + RA_VEC if op < RANDOM_ACCESS_COPIES else RANDOM_ACCESS_EXTRA),
+    REC_EXPONENTIATION: ("ExponentiationGate", 1, lambda op: 3),
+    REC_COSET_INTERPOLATION: ("CosetInterpolationGate", 1, lambda op: 35),
+}
+
+
+def job_columns(kind, op):
+    """the columns (wires) one job of lcp2_rec_gate_rows owns: every cell of operation `op` of a row of gate `kind`"""
+    name, ops, _ = REC_JOB_KINDS[kind]
+    assert 0 <= op < ops, (name, op)
+    if kind == REC_ARITHMETIC:
+        return list(range(4 * op, 4 * op + 4))
+    if kind == REC_BASE_SUM:
+        return list(range(1 + BASE_SUM_LIMBS))
+    if kind == REC_ARITHMETIC_EXT:
+        return list(range(8 * op, 8 * op + 8))
+    if kind == REC_MUL_EXT:
+        return list(range(6 * op, 6 * op + 6))
+    if kind == REC_REDUCING:
+        return list(range(6 + REDUCING_COEFFS + 2 * (REDUCING_COEFFS - 1)))
+    if kind == REC_REDUCING_EXT:
+        return list(range(6 + 2 * REDUCING_EXT_COEFFS + 2 * (REDUCING_EXT_COEFFS - 1)))
+    if kind == REC_POSEIDON_MDS:
+        return list(range(48))
+    if kind == REC_RANDOM_ACCESS:
+        if op == RANDOM_ACCESS_COPIES:
+            return [RA_ROUTED - 2, RA_ROUTED - 1]
+        return list(range((2 + RA_VEC) * op, (2 + RA_VEC) * (op + 1))) + list(range(RA_ROUTED + RANDOM_ACCESS_BITS * op, RA_ROUTED + RANDOM_ACCESS_BITS * (op + 1)))
+    if kind == REC_EXPONENTIATION:
+        return list(range(2 + 2 * EXP_POWER_BITS))
+    return list(range(1 + 2 * 16 + 4 + 4 * 2 + 2))   # CosetInterpolationGate: shift, 16 values, point, value, 2 x (eval, prod), shifted point
+
+
+def job_cells(kind, op, vals):
+    """{column: value} of one job in Python integers: run_once of operation `op` of gate `kind` on the operand values `vals` (any
+    u64 each, reduced here; the two power words of EXPONENTIATION are bit strings and are not)"""
+    from . import u32_gates as ug
+    raw, v, out = [int(x) for x in vals], [int(x) % P for x in vals], {}
+    assert len(v) == REC_JOB_KINDS[kind][2](op)
+
+    def pair(k):
+        return (v[k], v[k + 1])
+
+    def put2(col, x):
+        out[col], out[col + 1] = x
+
+    if kind == REC_ARITHMETIC:
+        c0, c1, m0, m1, ad = v
+        out.update({4 * op: m0, 4 * op + 1: m1, 4 * op + 2: ad, 4 * op + 3: (c0 * m0 * m1 + c1 * ad) % P})
+    elif kind == REC_BASE_SUM:
+        assert v[0] < 1 << BASE_SUM_LIMBS
+        out[0] = v[0]
+        for i in range(BASE_SUM_LIMBS):
+            out[1 + i] = (v[0] >> i) & 1
+    elif kind == REC_ARITHMETIC_EXT:
+        c0, c1, m0, m1, ad = v[0], v[1], pair(2), pair(4), pair(6)
+        pr = _emul(m0, m1)
+        for k, x in enumerate((m0, m1, ad, ((c0 * pr[0] + c1 * ad[0]) % P, (c0 * pr[1] + c1 * ad[1]) % P))):
+            put2(8 * op + 2 * k, x)
+    elif kind == REC_MUL_EXT:
+        pr = _emul(pair(1), pair(3))
+        for k, x in enumerate((pair(1), pair(3), (v[0] * pr[0] % P, v[0] * pr[1] % P))):
+            put2(6 * op + 2 * k, x)
+    elif kind in (REC_REDUCING, REC_REDUCING_EXT):
+        ext = kind == REC_REDUCING_EXT
+        count = REDUCING_EXT_COEFFS if ext else REDUCING_COEFFS
+        alpha, acc = pair(0), pair(2)
+        put2(2, alpha)
+        put2(4, acc)
+        start = 6 + (2 if ext else 1) * count
+        for i in range(count):
+            c = pair(4 + 2 * i) if ext else (v[4 + i], 0)
+            if ext:
+                put2(6 + 2 * i, c)
+            else:
+                out[6 + i] = c[0]
+            t = _emul(acc, alpha)
+            acc = ((t[0] + c[0]) % P, (t[1] + c[1]) % P)
+            put2(start + 2 * i if i < count - 1 else 0, acc)
+    elif kind == REC_POSEIDON_MDS:
+        for k in range(2):
+            s = [v[2 * i + k] for i in range(12)]
+            for r in range(12):
+                out[2 * r + k] = s[r]
+                out[24 + 2 * r + k] = (sum(s[(i + r) % 12] * MDS_CIRC[i] for i in range(12)) + s[r] * MDS_DIAG[r]) % P
+    elif kind == REC_RANDOM_ACCESS:
+        if op == RANDOM_ACCESS_COPIES:
+            out[RA_ROUTED - 2], out[RA_ROUTED - 1] = v
+        else:
+            base, idx = (2 + RA_VEC) * op, v[0]
+            assert idx < RA_VEC
+            out[base], out[base + 1] = idx, v[1 + idx]
+            for i in range(RA_VEC):
+                out[base + 2 + i] = v[1 + i]
+            for i in range(RANDOM_ACCESS_BITS):
+                out[RA_ROUTED + RANDOM_ACCESS_BITS * op + i] = (idx >> i) & 1
+    elif kind == REC_EXPONENTIATION:
+        n = EXP_POWER_BITS
+        assert v[2] <= 3
+        base, power = v[0], raw[1] | (v[2] << 64)
+        out[0] = base
+        cur = 1
+        for i in range(n):
+            out[1 + i] = (power >> i) & 1
+        for i in range(n):
+            bit = (power >> (n - 1 - i)) & 1
+            cur = (cur * cur if i else 1) % P * (base if bit else 1) % P
+            out[2 + n + i] = cur
+        out[1 + n] = cur
+    else:
+        domain = ug._coset_domain()
+        weights = ug._barycentric_weights(domain)
+        shift, values, point = v[0], [pair(1 + 2 * i) for i in range(ug.COSET_POINTS)], pair(33)
+        assert shift
+        inv_shift = pow(shift, P - 2, P)
+        x = (point[0] * inv_shift % P, point[1] * inv_shift % P)
+        out[0] = shift
+        for i, val in enumerate(values):
+            put2(1 + 2 * i, val)
+        put2(33, point)
+        ev, pr, pinned = (0, 0), (1, 0), 0
+        for i in range(ug.COSET_POINTS):
+            term = ((x[0] - domain[i]) % P, x[1])
+            wv = (values[i][0] * weights[i] % P, values[i][1] * weights[i] % P)
+            e1, e2 = _emul(ev, term), _emul(wv, pr)
+            ev, pr = ((e1[0] + e2[0]) % P, (e1[1] + e2[1]) % P), _emul(pr, term)
+            if i + 1 in (ug.COSET_DEGREE, 2 * ug.COSET_DEGREE - 1):
+                put2(37 + 2 * pinned, ev)
+                put2(41 + 2 * pinned, pr)
+                pinned += 1
+        put2(35, ev)
+        put2(45, x)
+    return out
+
+
+def job_inputs(kind, op, w, c0=0, c1=0):
+    """the operand values of operation `op` read back from a filled row `w` (a sequence of wire values) and the row's gate constants"""
+    w = [int(x) for x in w[:REC_ROW_COLUMNS]]
+    if kind == REC_ARITHMETIC:
+        return [c0, c1] + w[4 * op:4 * op + 3]
+    if kind == REC_BASE_SUM:
+        return [w[0]]
+    if kind == REC_ARITHMETIC_EXT:
+        return [c0, c1] + w[8 * op:8 * op + 6]
+    if kind == REC_MUL_EXT:
+        return [c0] + w[6 * op:6 * op + 4]
+    if kind == REC_REDUCING:
+        return w[2:6 + REDUCING_COEFFS]
+    if kind == REC_REDUCING_EXT:
+        return w[2:6 + 2 * REDUCING_EXT_COEFFS]
+    if kind == REC_POSEIDON_MDS:
+        return w[:24]
+    if kind == REC_RANDOM_ACCESS:
+        base = (2 + RA_VEC) * op
+        return [c0, c1] if op == RANDOM_ACCESS_COPIES else [w[base]] + w[base + 2:base + 2 + RA_VEC]
+    if kind == REC_EXPONENTIATION:
+        return [w[0], sum(w[1 + i] << i for i in range(64)), w[65] | (w[66] << 1)]
+    return w[:35]
+
+
+IMM = lambda v: (int(v), 0, REC_IMM)          # noqa: E731
+CELL = lambda row, col: (int(row), int(col), REC_CELL)   # noqa: E731
+
+
+def pack_plan(levels):
+    """levels: [[(row, kind, op, [IMM(..) / CELL(..), ..]), ..], ..] -> (jobs, operands, level_ends) as record arrays, every level
+    sorted by (kind, op, row): the order in which lcp2_rec_gate_rows stores contiguously"""
+    items = [sorted(level, key=lambda it: (it[1], it[2], it[0])) for level in levels]
+    jobs = np.zeros(sum(len(level) for level in items), dtype=REC_JOB_DTYPE)
+    ops = np.zeros(sum(len(it[3]) for level in items for it in level), dtype=REC_OPERAND_DTYPE)
+    at = k = 0
+    ends = []
+    for level in items:
+        for row, kind, op, operands in level:
+            assert len(operands) == REC_JOB_KINDS[kind][2](op), (kind, op, len(operands))
+            jobs[k] = (row, kind, op, at, 0)
+            for v, col, src in operands:
+                ops[at] = (v % (1 << 64), col, src)
+                at += 1
+            k += 1
+        ends.append(k)
+    return jobs, ops, np.array(ends, dtype=np.uint32)
+
+
+def run_plan(jobs, operands, level_ends, ncols, n, start=None):
+    """lcp2_rec_gate_rows in Python integers: the matrix [ncols][n] after the plan ran on `start` (zeros by default)"""
+    out = np.zeros((ncols, n), dtype=np.uint64) if start is None else start.copy()
+    for j in jobs[:int(level_ends[-1]) if len(level_ends) else 0]:
+        kind, op, first = int(j["kind"]), int(j["op"]), int(j["first_operand"])
+        vals = []
+        for o in operands[first:first + REC_JOB_KINDS[kind][2](op)]:
+            vals.append(int(out[int(o["col"]), int(o["v"])]) % P if o["src"] == REC_CELL else int(o["v"]))
+        for col, v in job_cells(kind, op, vals).items():
+            out[col, int(j["row"])] = v
+    return out
+
+
+def witness_jobs(wires, gate_of_row, G, consts=None):
+    """The IMM jobs that regenerate every owned cell of the recursion-gate rows of a filled host witness, in ONE level: the operands
+    of each operation read out of `wires` [num_wires][n] and the rows' gate constants consts = (c0 [n], c1 [n]).  Operation slots
+    whose cells are all zero get no job (a zero slot satisfies its gate, as a slot no generator ran on does).
+    Returns (jobs, operands, level_ends)."""
+    level = []
+    for kind, (name, ops, _) in REC_JOB_KINDS.items():
+        if name not in G:
+            continue
+        for r in np.nonzero(gate_of_row == G[name])[0]:
+            w = wires[:, r]
+            c0, c1 = (int(consts[0][r]), int(consts[1][r])) if consts is not None else (0, 0)
+            for op in range(ops):
+                if ops > 1 and not w[job_columns(kind, op)].any():
+                    continue
+                level.append((int(r), kind, op, [IMM(v) for v in job_inputs(kind, op, w, c0, c1)]))
+    return pack_plan([level])
+
+
+# ---------------------------------------------------------------- a chained plan over all ten gates
+CHAIN_ORDER = [REC_ARITHMETIC, REC_BASE_SUM, REC_ARITHMETIC_EXT, REC_MUL_EXT, REC_REDUCING, REC_REDUCING_EXT, REC_POSEIDON_MDS,
+               REC_RANDOM_ACCESS, REC_EXPONENTIATION, REC_COSET_INTERPOLATION]
+
+
+def chain_gateset(native=True):
+    """all ten gates and NoopGate, sorted by (degree, name) as plonky2 sorts a gate set: three selector groups under max_degree 9"""
+    from . import u32_gates as ug
+    return GateSet([
+        ("NoopGate", 0, gate_noop),
+        ("PoseidonMdsGate", 1, gate_poseidon_mds),
+        ("BaseSumGate", 2, gate_base_sum(BASE_SUM_LIMBS)),
+        ("ReducingExtensionGate", 2, gate_reducing_extension),
+        ("ReducingGate", 2, gate_reducing),
+        ("ArithmeticExtensionGate", 3, gate_arithmetic_extension),
+        ("ArithmeticGate", 3, gate_arithmetic),
+        ("MulExtensionGate", 3, gate_mul_extension),
+        ("ExponentiationGate", 4, gate_exponentiation),
+        ("RandomAccessGate", 5, gate_random_access),
+        ("CosetInterpolationGate", 8, ug.gate_coset_interpolation),
+    ], native=native)
+
+
+def chain_plan(n, seed, levels=None):
+    """A deterministic plan over n rows in which every level feeds the next.  Every level holds `width` groups of ten rows, one row of
+    each gate; level 0 is IMM only (values drawn from `seed`), and every operand of a later level that is not a gate constant is a
+    CELL of a row of the level before:
+      ARITHMETIC        row constants (2, 1).  op 0, 1: lo = 2 b1 + b0 and hi = 2 b3 + b2 from the bit wires of the BASE_SUM row;
+                        op 2: 4 hi + lo (as 2 hi 2 + lo) from the ARITHMETIC row - the low 4 bits of a BASE_SUM value, two levels on;
+                        op 3: 2 index r + s (index: op 2 of the level before, r < 2^40 and s < 2^50 immediates), below 2^63
+      BASE_SUM          the value is op 3 of the ARITHMETIC row
+      ARITHMETIC_EXT    m0 = MUL_EXT output, m1 = REDUCING output, addend = a POSEIDON_MDS output
+      MUL_EXT           m0 = ARITHMETIC_EXT output, m1 = COSET_INTERPOLATION evaluation_value
+      REDUCING          alpha = MUL_EXT output, old_acc = ARITHMETIC_EXT output, coefficients = POSEIDON_MDS cells
+      REDUCING_EXT      alpha = REDUCING output, old_acc = ARITHMETIC_EXT output, coefficients = REDUCING accumulators
+      POSEIDON_MDS      inputs = REDUCING_EXT accumulators
+      RANDOM_ACCESS     copy 0: index = op 2 of the ARITHMETIC row, items = POSEIDON_MDS outputs; op 4: the row's constants
+      EXPONENTIATION    base = REDUCING output c0, power = (BASE_SUM value, a RANDOM_ACCESS bit)
+      COSET_INTERPOLATION  shift = EXPONENTIATION output, values = REDUCING_EXT coefficients, point = MUL_EXT output
+    levels = None: width 1 and as many levels as fit (at least 6 from n = 64); else that many levels, as wide as fit.  The gate
+    constants and the immediates of the later levels depend on n only, so two seeds give the same plan but for level 0's values.
+    Returns a namespace: jobs, operands, level_ends, expected (the matrix [135][n] in Python integers, from a zero matrix),
+    gate_of_row (indices into chain_gateset()), c0, c1 (the gate constants of every row).  Level 0's operands come first in the
+    operand list: they end where the first job of level 1 has its first_operand."""
+    rng, fixed = np.random.default_rng(seed), np.random.default_rng(0xC4A1 + n)
+    usable = n - min(4, n // 4)
+    nk = len(CHAIN_ORDER)
+    if levels is None:
+        levels, width = usable // nk, 1
+    else:
+        width = usable // (nk * levels)
+    assert levels >= 1 and width >= 1
+    gs = chain_gateset()
+    gate_of_row = np.zeros(n, dtype=np.int64)
+    c0, c1 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+
+    def row_of(level, kind, j):
+        return (level * nk + CHAIN_ORDER.index(kind)) * width + j
+
+    def f(r=None):
+        return int((r or fixed).integers(0, P, dtype=np.uint64))
+
+    plan = []
+    for lv in range(levels):
+        jobs = []
+        for j in range(width):
+            R = {kind: row_of(lv, kind, j) for kind in CHAIN_ORDER}
+            Q = {kind: row_of(lv - 1, kind, j) for kind in CHAIN_ORDER}
+            for kind, r in R.items():
+                gate_of_row[r] = gs.index(REC_JOB_KINDS[kind][0])
+                c0[r], c1[r] = (2, 1) if kind == REC_ARITHMETIC else (f(), f())
+            k = {kind: (IMM(c0[r]), IMM(c1[r])) for kind, r in R.items()}
+
+            def cells(kind, cols):
+                return [CELL(Q[kind], c) for c in cols]
+
+            def leaf(count, hi=P):
+                return [IMM(rng.integers(0, hi, dtype=np.uint64)) for _ in range(count)]
+
+            first = lv == 0
+            A, B = R[REC_ARITHMETIC], Q[REC_ARITHMETIC]
+            bit = (lambda i: leaf(1, 2)[0]) if first else (lambda i: CELL(Q[REC_BASE_SUM], 1 + i))
+            jobs.append((A, REC_ARITHMETIC, 0, [*k[REC_ARITHMETIC], bit(1), IMM(1), bit(0)]))
+            jobs.append((A, REC_ARITHMETIC, 1, [*k[REC_ARITHMETIC], bit(3), IMM(1), bit(2)]))
+            jobs.append((A, REC_ARITHMETIC, 2, [*k[REC_ARITHMETIC], *(leaf(1, 4) if first else [CELL(B, 7)]), IMM(2), *(leaf(1, 4) if first else [CELL(B, 3)])]))
+            jobs.append((A, REC_ARITHMETIC, 3, [*k[REC_ARITHMETIC], *(leaf(1, 16) if first else [CELL(B, 11)]), IMM(fixed.integers(0, 1 << 40)), IMM(fixed.integers(0, 1 << 50))]))
+            jobs.append((R[REC_BASE_SUM], REC_BASE_SUM, 0, leaf(1, 1 << 63) if first else [CELL(B, 15)]))
+            jobs.append((R[REC_ARITHMETIC_EXT], REC_ARITHMETIC_EXT, 0, [*k[REC_ARITHMETIC_EXT], *(leaf(6) if first else
+                         cells(REC_MUL_EXT, (4, 5)) + cells(REC_REDUCING, (0, 1)) + cells(REC_POSEIDON_MDS, (24, 25)))]))
+            jobs.append((R[REC_MUL_EXT], REC_MUL_EXT, 0, [k[REC_MUL_EXT][0], *(leaf(4) if first else
+                         cells(REC_ARITHMETIC_EXT, (6, 7)) + cells(REC_COSET_INTERPOLATION, (35, 36)))]))
+            jobs.append((R[REC_REDUCING], REC_REDUCING, 0, leaf(47) if first else
+                         cells(REC_MUL_EXT, (4, 5)) + cells(REC_ARITHMETIC_EXT, (6, 7)) + cells(REC_POSEIDON_MDS, range(REDUCING_COEFFS))))
+            jobs.append((R[REC_REDUCING_EXT], REC_REDUCING_EXT, 0, leaf(68) if first else
+                         cells(REC_REDUCING, (0, 1)) + cells(REC_ARITHMETIC_EXT, (6, 7)) + cells(REC_REDUCING, range(49, 49 + 2 * REDUCING_EXT_COEFFS))))
+            jobs.append((R[REC_POSEIDON_MDS], REC_POSEIDON_MDS, 0, leaf(24) if first else cells(REC_REDUCING_EXT, range(70, 94))))
+            jobs.append((R[REC_RANDOM_ACCESS], REC_RANDOM_ACCESS, 0, leaf(1, 16) + leaf(16) if first else
+                         [CELL(B, 11)] + cells(REC_POSEIDON_MDS, range(24, 40))))
+            jobs.append((R[REC_RANDOM_ACCESS], REC_RANDOM_ACCESS, RANDOM_ACCESS_COPIES, list(k[REC_RANDOM_ACCESS])))
+            jobs.append((R[REC_EXPONENTIATION], REC_EXPONENTIATION, 0, leaf(1) + leaf(1, 1 << 64) + leaf(1, 4) if first else
+                         cells(REC_REDUCING, (0,)) + cells(REC_BASE_SUM, (0,)) + cells(REC_RANDOM_ACCESS, (RA_ROUTED,))))
+            jobs.append((R[REC_COSET_INTERPOLATION], REC_COSET_INTERPOLATION, 0, leaf(1, P - 1) + leaf(34) if first else
+                         cells(REC_EXPONENTIATION, (1 + EXP_POWER_BITS,)) + cells(REC_REDUCING_EXT, range(6, 38)) + cells(REC_MUL_EXT, (4, 5))))
+        plan.append(jobs)
+    jobs, operands, level_ends = pack_plan(plan)
+    expected = run_plan(jobs, operands, level_ends, REC_ROW_COLUMNS, n)
+    return SimpleNamespace(jobs=jobs, operands=operands, level_ends=level_ends, expected=expected, gate_of_row=gate_of_row, c0=c0, c1=c1)
+
+
+def chain_circuit(params, plan, native=True):
+    """the circuit a chain_plan fills: its rows' gates and constants, no copy constraints (identity permutation), no public inputs"""
+    gs = chain_gateset(native)
+    n, NR = 1 << params.degree_bits, params.num_routed_wires
+    assert n == plan.gate_of_row.size and params.num_constants == gs.num_selectors + 2 and params.num_wires >= REC_ROW_COLUMNS and NR >= 80
+    rows = np.arange(n)
+    k_is = gl.powers(7, NR)
+    sig = sigma_values(np.tile(rows, (NR, 1)), np.tile(np.arange(NR)[:, None], (1, n)), k_is, params.degree_bits)
+    cs = np.concatenate([gs.selector_columns(plan.gate_of_row), plan.c0[None, :], plan.c1[None, :], sig])
+    return Circuit(params, gs, cs, k_is, 0), np.zeros(0, dtype=np.uint64)

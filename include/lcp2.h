@@ -235,6 +235,71 @@ typedef struct {
 int lcp2_u32_gate_rows(lcp2_ctx *ctx, const lcp2_u32_job *jobs, size_t njobs, lcp2_mem jobs_mem,
                        uint64_t *wires /* device, column-major [>= 126][n] */, uint64_t n);
 
+/* Recursion-gate rows generated on the device, LEVEL BY LEVEL: SimpleGenerator::run_once of ArithmeticGate { num_ops: 20 },
+ * BaseSumGate<2> { 63 limbs }, ArithmeticExtensionGate { 10 }, MulExtensionGate { 13 }, ReducingGate { 43 coefficients },
+ * ReducingExtensionGate { 32 }, PoseidonMdsGate, RandomAccessGate { bits 4, copies 4, 2 extra constants }, ExponentiationGate
+ * { 66 power bits } and CosetInterpolationGate { subgroup_bits 4, degree 8 }, D = 2 - the gates builder.verify_proof is made of
+ * (reference call site src/targets.rs:468-470).  Most cells of such a row ARE the operation's inputs and outputs, and the output
+ * of one operation is the input of the next through a copy constraint, so a job does not carry values: each operand is either an
+ * immediate or a CELL of the witness matrix, and the list runs in levels.  A caller records jobs, operands and level_ends once per
+ * circuit (they may stay in HBM); per proof it rewrites only the IMM values of the leaves and replays the plan.
+ * One job is ONE OPERATION of one row and writes every cell of that operation - inputs, outputs, intermediates - into the
+ * column-major matrix `wires` [ncols >= 135][n].  It takes a fixed number of operands from operands[first_operand] on; extension
+ * elements are two operands, (c0, c1).  The gate constants c0, c1 are operands too: the witness matrix does not hold them.
+ * Layouts and values: eth-lc-plonky2_amd/recursion_gates.py, u32_gates.py (coset interpolation), circuit.py (arithmetic, base
+ * sum); like those programs [RECALL] of plonky2, parity unpinned.
+ *   kind                 op <  operands (count)                                          cells written
+ *   ARITHMETIC           20    c0, c1, m0, m1, addend (5)                                wires 4 op .. 4 op + 3 (output = c0 m0 m1 + c1 addend)
+ *   BASE_SUM             1     value (1)                                                 wire 0 and the 63 bits on wires 1 .. 63
+ *   ARITHMETIC_EXT       10    c0, c1, m0, m1, addend (8)                                wires 8 op .. 8 op + 7
+ *   MUL_EXT              13    c0, m0, m1 (5)                                            wires 6 op .. 6 op + 5
+ *   REDUCING             1     alpha, old_acc, 43 coefficients (47)                      wires 2 .. 48 (inputs), 49 .. 132 (42 accumulators), 0, 1 (output)
+ *   REDUCING_EXT         1     alpha, old_acc, 32 extension coefficients (68)            wires 2 .. 69, 70 .. 131, 0, 1
+ *   POSEIDON_MDS         1     12 extension inputs (24)                                  wires 0 .. 47
+ *   RANDOM_ACCESS        5     op 0..3, one copy: access_index, 16 items (17)            wires 18 op .. 18 op + 17 (index, claimed element, items), 4 bits at 74 + 4 op
+ *                              op 4: the two extra constants (2)                         wires 72, 73
+ *   EXPONENTIATION       1     base, power bits 0..63, power bits 64..65 (3)             wire 0, bits 1 .. 66, output 67, intermediates 68 .. 133
+ *   COSET_INTERPOLATION  1     shift, 16 extension values, evaluation point (35)         wires 0 .. 46 (.., evaluation_value 35, 36, intermediates, shifted point)
+ * Operand values are canonicalised when read (an IMM may be any u64, a cell is reduced after the load) and every value written is
+ * canonical.  The two power words of EXPONENTIATION are bit strings, not field elements: an IMM word is used as it stands.
+ * Cells outside the operation are NOT touched.
+ * Levels: level l is the jobs [level_ends[l-1], level_ends[l]); each level is one launch (a host list: one per staged piece) on
+ * the context's stream, in order.  A CELL operand may name any cell the matrix held before the call or that a job of an EARLIER
+ * level writes.  A reference to a cell written in the SAME level is the caller's error and is NOT detected, like two jobs for one
+ * slot or two kinds on one row.  Inside a level any order is correct; the FAST order is (kind, op, row).
+ * lists_mem says where jobs AND operands live; level_ends is always host memory.  LCP2_MEM_HOST: the lists are validated before
+ * anything is launched - a refused list writes nothing - the operands go up before the jobs, the jobs in pieces.
+ * LCP2_MEM_DEVICE: the kernel validates.
+ * Refused (LCP2_E_INVALID; lcp2_last_error names "job <index>" and the reason): row >= n, an unknown kind, op out of range,
+ * first_operand + count > noperands, an operand src above 1, a CELL operand with col >= ncols or v >= n; also ncols < 135,
+ * level_ends not ascending or not ending at njobs, a lists_mem above 1, a null ctx, wires, or (njobs > 0) jobs / level_ends, or
+ * (noperands > 0) operands.  njobs = 0 is LCP2_OK.  Refusable by VALUE: BASE_SUM value >= 2^63, RANDOM_ACCESS index >= 16,
+ * EXPONENTIATION high word > 3, COSET_INTERPOLATION shift = 0 (mod p).  A host list is checked for these on the host where the
+ * operand is IMM.  Everything else (CELL operands, device lists) is checked in the kernel: the refused job writes nothing, the
+ * valid jobs of its level and of earlier levels are written, the launches of later levels write nothing (their lanes return at
+ * once: the call does not wait for the host between levels), and the call returns LCP2_E_INVALID naming the first refused job.
+ * The context's stream is synchronised on return. */
+enum { LCP2_REC_ARITHMETIC = 0, LCP2_REC_BASE_SUM, LCP2_REC_ARITHMETIC_EXT, LCP2_REC_MUL_EXT, LCP2_REC_REDUCING,
+       LCP2_REC_REDUCING_EXT, LCP2_REC_POSEIDON_MDS, LCP2_REC_RANDOM_ACCESS, LCP2_REC_EXPONENTIATION,
+       LCP2_REC_COSET_INTERPOLATION, LCP2_REC_KINDS };
+enum { LCP2_REC_IMM = 0, LCP2_REC_CELL = 1 };
+typedef struct {
+  uint64_t v;    /* IMM: the value (any u64, canonicalised); CELL: the row */
+  uint32_t col;  /* CELL: the column */
+  uint32_t src;  /* LCP2_REC_IMM or LCP2_REC_CELL */
+} lcp2_rec_operand;  /* 16 bytes */
+typedef struct {
+  uint32_t row;
+  uint16_t kind;  /* LCP2_REC_* */
+  uint16_t op;    /* operation slot inside the row */
+  uint32_t first_operand, reserved;
+} lcp2_rec_job;  /* 16 bytes */
+int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_t njobs,
+                       const lcp2_rec_operand *operands, size_t noperands,
+                       const uint32_t *level_ends /* host, [nlevels], ascending, last == njobs */, size_t nlevels,
+                       lcp2_mem lists_mem /* where jobs AND operands live */,
+                       uint64_t *wires /* device, column-major [ncols][n] */, uint32_t ncols, uint64_t n);
+
 /* device buffers for callers that keep the witness resident in HBM */
 int lcp2_buffer_alloc(lcp2_ctx *ctx, size_t bytes, void **dev);
 int lcp2_buffer_free(lcp2_ctx *ctx, void *dev);
