@@ -63,6 +63,8 @@ class U32Job(ctypes.Structure):
 U32_ARITHMETIC, U32_ADD_MANY, U32_SUBTRACTION, U32_RANGE_CHECK, U32_COMPARISON = range(5)
 U32_JOB_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u2"), ("op", "<u2"), ("in", "<u4", (4,))])   # U32Job as a numpy record
 assert U32_JOB_DTYPE.itemsize == ctypes.sizeof(U32Job) == 24
+POSEIDON_ROW_DTYPE = np.dtype([("row", "<u4"), ("swap", "<u4"), ("in", "<u8", (12,))])   # lcp2_poseidon_row as a numpy record
+assert POSEIDON_ROW_DTYPE.itemsize == 104
 
 class RecOperand(ctypes.Structure):
     """lcp2_rec_operand: an immediate value, or a cell (row v, column col) of the witness matrix (lcp2_rec_gate_rows)"""
@@ -415,6 +417,15 @@ class Context:
     # ---- device buffers
     def buffer_zero(self, dev_ptr, words):
         self._check(self.lib.lcp2_buffer_zero(self.handle, ctypes.c_void_p(dev_ptr), int(words) * 8))
+
+    def poseidon_gate_rows(self, rows, wires_dev, n):
+        """lcp2_poseidon_gate_rows: writes all 135 cells of every PoseidonGate row of `rows` (a numpy array of POSEIDON_ROW_DTYPE
+        records: row, swap flag, 12 inputs; validated before anything runs) into the device witness matrix `wires_dev` (a
+        pointer, [>= 135][n] column-major)."""
+        if not isinstance(rows, np.ndarray) or rows.dtype != POSEIDON_ROW_DTYPE:
+            raise Lcp2Error(-1, "rows must be an array of POSEIDON_ROW_DTYPE records")
+        r = np.ascontiguousarray(rows).ravel()
+        self._check(self.lib.lcp2_poseidon_gate_rows(self.handle, _ptr(r), r.size, ctypes.c_void_p(wires_dev), n))
 
     def u32_gate_rows(self, jobs, wires_dev, n, njobs=None):
         """lcp2_u32_gate_rows: writes the cells of every job into the device witness matrix `wires_dev` (a pointer, [>= 126][n]

@@ -90,6 +90,7 @@ def build_native(force=False, verbose=False):
 
 HOST_DIR = os.path.join(PKG_DIR, "host")
 HOST_LIB = os.path.join(PKG_DIR, "liblcp2_host.so")
+HOST_SHARED_HEADERS = ("gate_program.hpp", "pos_rows.hpp", "poseidon.hpp", "gl64.hpp")  # what host/ includes from csrc/
 
 
 def build_host(force=False, verbose=False):
@@ -98,7 +99,7 @@ def build_host(force=False, verbose=False):
     build_native(verbose=verbose)
     srcs = sorted(os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith(".cpp"))
     deps = srcs + [os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith((".hpp", ".h"))] + [
-        os.path.join(PKG_DIR, "..", "include", "lcp2.h"), os.path.join(CSRC, "gate_program.hpp")]
+        os.path.join(PKG_DIR, "..", "include", "lcp2.h")] + [os.path.join(CSRC, h) for h in HOST_SHARED_HEADERS]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps):
         return HOST_LIB
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", HOST_LIB + ".tmp"] + srcs + ["-L", PKG_DIR, "-llcp2", "-Wl,-rpath,$ORIGIN"]

@@ -55,6 +55,7 @@ namespace lcp2 {
       return (ctx)->fail(e_ == hipErrorOutOfMemory ? LCP2_E_OOM : LCP2_E_HIP,                \
                          std::string(#expr) + ": " + hipGetErrorString(e_));                 \
   } while (0)
+#define LCP2_TRY(expr) do { int rc_ = (expr); if (rc_ != LCP2_OK) return rc_; } while (0)
 
 // RAII device allocation
 struct DevBuf {

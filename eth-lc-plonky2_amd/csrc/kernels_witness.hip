@@ -11,7 +11,7 @@
 // plus k_scatter_cells for the handful of non-SHA cells (constants, arithmetic glue, public inputs).
 #include "internal.hpp"
 #include "sha_layout.hpp"
-#include "poseidon.hpp"
+#include "pos_rows.hpp"
 #include "prover_kernels.hpp"
 #include "u32_rows.hpp"
 #include "rec_rows.hpp"
@@ -175,50 +175,11 @@ __global__ void k_scatter_cells(const CellDev *__restrict__ cells, u64 ncells, u
   wires[(u64)c.col * n + c.row] = c.value;
 }
 
-// One lane per PoseidonGate row: the permutation in its plain round form (constants, S-box, MDS), recording what enters every
-// S-box that has a wire - plonky2 gates/poseidon.rs PoseidonGenerator::run_once; wire layout as in kernels_quotient.hip
-// q_poseidon_native.  A few thousand rows per light-client proof (the recursive verifier's Merkle paths, its Challenger and the
-// sponge over the inner proof's public inputs): canonical arithmetic throughout, speed is irrelevant here.
+// One lane per PoseidonGate row (pos_rows.hpp pos_row_cells: the text tests/emu/emu_pos.cpp runs on the CPU and the host's
+// poseidon_gate_row calls).  A few thousand rows per light-client proof (the recursive verifier's Merkle paths, its Challenger and
+// the sponge over the inner proof's public inputs): canonical arithmetic throughout, speed is irrelevant here.
 __global__ void k_poseidon_gate_rows(const PoseidonRowDev *__restrict__ rows, u64 nrows, u64 *__restrict__ wires, u64 n, const u64 *__restrict__ rc) {
-  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nrows) return;
-  const PoseidonRowDev job = rows[i];
-  u64 *W = wires + job.row;
-  auto put = [&](u32 col, u64 v) { W[(u64)col * n] = v; };
-  u64 s[12];
-#pragma unroll
-  for (int j = 0; j < 12; j++) { s[j] = gl_canon(job.in[j]); put(j, s[j]); }
-  const bool swap = job.swap != 0;
-  put(24, swap ? 1 : 0);
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const u64 delta = swap ? gl_sub(s[j + 4], s[j]) : 0;
-    put(25 + j, delta);
-    const u64 l = gl_add(s[j], delta), r = gl_sub(s[j + 4], delta);
-    s[j] = l; s[j + 4] = r;
-  }
-#pragma unroll 1
-  for (int round = 0; round < POS_ROUNDS; round++) {
-#pragma unroll
-    for (int j = 0; j < 12; j++) s[j] = gl_add(s[j], rc[12 * round + j]);
-    const bool full = round < POS_FULL_HALF || round >= POS_FULL_HALF + POS_PARTIAL;
-    if (full) {
-#pragma unroll
-      for (int j = 0; j < 12; j++) {
-        if (round >= 1 && round < POS_FULL_HALF) put(29 + 12 * (round - 1) + j, s[j]);
-        if (round >= POS_FULL_HALF + POS_PARTIAL) put(87 + 12 * (round - POS_FULL_HALF - POS_PARTIAL) + j, s[j]);
-        s[j] = gl_canon(pos_sbox(s[j]));
-      }
-    } else {
-      put(65 + (round - POS_FULL_HALF), s[0]);
-      s[0] = gl_canon(pos_sbox(s[0]));
-    }
-    pos_mds(s);
-#pragma unroll
-    for (int j = 0; j < 12; j++) s[j] = gl_canon(s[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < 12; j++) put(12 + j, s[j]);
+  pos_rows_lane(rows, nrows, (u64)blockIdx.x * blockDim.x + threadIdx.x, wires, n, rc);
 }
 void launch_poseidon_gate_rows(hipStream_t s, const PoseidonRowDev *rows, u64 nrows, u64 *wires, u64 n, const u64 *rc) {
   if (!nrows) return;
@@ -231,11 +192,13 @@ void launch_poseidon_gate_rows(hipStream_t s, const PoseidonRowDev *rows, u64 nr
 // whole 128-byte lines - exactly when its 64 jobs are 64 consecutive rows of one (kind, op): the order the header calls fast.
 // Jobs in any other order write the same cells, one 8-byte piece of a line per lane.  Nothing is read but the job (24 bytes per
 // lane, contiguous); blocks of 256 keep four waves' stores in flight per CU and a wave never mixes kinds in a sorted list, so the
-// switch does not diverge except at the few boundaries between kinds.
+// switch does not diverge except at the few boundaries between kinds.  A refused job folds its index and problem into the flag
+// word (row_flag.hpp); a valid one never touches it.
 constexpr u32 U32_ROWS_THREADS = 256;
 __global__ __launch_bounds__(U32_ROWS_THREADS) void k_u32_gate_rows(const U32JobDev *__restrict__ jobs, u64 njobs, u64 *__restrict__ wires,
                                                                      u64 n, u64 *__restrict__ flag) {
-  u32_rows_lane(jobs, njobs, (u64)blockIdx.x * blockDim.x + threadIdx.x, wires, n, flag);
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (const u32 problem = u32_rows_lane(jobs, njobs, i, wires, n)) atomicMin((unsigned long long *)flag, (unsigned long long)row_refusal(i, problem));
 }
 void launch_u32_gate_rows(hipStream_t s, const U32JobDev *jobs, u64 njobs, u64 *wires, u64 n, u64 *flag) {
   if (!njobs) return;
@@ -252,14 +215,15 @@ void launch_u32_gate_rows(hipStream_t s, const U32JobDev *jobs, u64 njobs, u64 *
 // operands, and the records of one lane are consecutive, so the 16-byte loads of a lane walk whole cache lines; a round trip
 // through LDS would add instructions and a barrier to a kernel whose long kinds are bound by 43 / 66 / 16 DEPENDENT extension
 // multiplies per lane, which LDS cannot shorten.  The long kinds stay one lane per job; a sorted list keeps a wave on one kind.
-// The flag word is folded with a minimum, so it names the first refused job; lanes of a level after that job's return at once.
+// The flag word is folded with a minimum (row_flag.hpp), so it names the first refused job; lanes of a level after that job's return
+// at once.
 constexpr u32 REC_ROWS_THREADS = 256;
 __global__ __launch_bounds__(REC_ROWS_THREADS) void k_rec_gate_rows(const RecJobDev *__restrict__ jobs, u64 base, u64 begin, u64 end,
                                                                      const RecOperandDev *__restrict__ operands, u64 noperands, u64 *wires,
                                                                      u32 ncols, u64 n, u64 *flag, int check_structure) {
   const u64 i = begin + (u64)blockIdx.x * blockDim.x + threadIdx.x;
   const u64 problem = rec_rows_lane(jobs, base, begin, end, i, operands, noperands, wires, ncols, n, flag, check_structure != 0);
-  if (problem) atomicMin((unsigned long long *)flag, (unsigned long long)(i << 8 | problem));
+  if (problem) atomicMin((unsigned long long *)flag, (unsigned long long)row_refusal(i, problem));
 }
 void launch_rec_gate_rows(hipStream_t s, const RecJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
                           u64 *wires, u32 ncols, u64 n, u64 *flag, bool check_structure) {

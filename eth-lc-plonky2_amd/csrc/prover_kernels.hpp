@@ -159,14 +159,13 @@ void launch_gather_ext_leaves(hipStream_t s, const u64 *p0, const u64 *p1, u32 a
 void launch_pow_search(hipStream_t s, const PowArgs &a, u64 count);
 void launch_fill(hipStream_t s, u64 *p, u64 n, u64 v);
 // lcp2_u32_gate_rows (kernels_witness.hip k_u32_gate_rows, u32_rows.hpp): one lane per job writes the cells of one operation of a
-// plonky2_u32 / comparison row into wires [>= 126][n]; *flag (device, zeroed by the caller) receives 1 + the index of an invalid
-// job, which writes nothing
+// plonky2_u32 / comparison row into wires [>= 126][n]; *flag (device, set to ROW_NO_PROBLEM by the caller: row_flag.hpp) receives
+// the minimum of row_refusal(index, problem) over the refused jobs, which write nothing
 struct U32JobDev;
 void launch_u32_gate_rows(hipStream_t s, const U32JobDev *jobs, u64 njobs, u64 *wires, u64 n, u64 *flag);
 // lcp2_rec_gate_rows (kernels_witness.hip k_rec_gate_rows, rec_rows.hpp): the jobs [begin, end) of one level, one lane each; jobs[0]
-// is job `base` of the list (begin >= base); operands: the WHOLE operand list; wires [ncols >= 135][n].  *flag (device, set to
-// REC_NO_PROBLEM = ~0 by the caller) receives the minimum of (index << 8 | problem) over the refused jobs, which write nothing; a
-// launch whose level begins after the job the flag names writes nothing at all
+// is job `base` of the list (begin >= base); operands: the WHOLE operand list; wires [ncols >= 135][n].  *flag as for
+// launch_u32_gate_rows; a launch whose level begins after the job the flag names writes nothing at all
 struct RecJobDev;
 struct RecOperandDev;
 void launch_rec_gate_rows(hipStream_t s, const RecJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,

@@ -3,8 +3,8 @@
 // SimpleGenerator::run_once of ArithmeticGate, BaseSumGate<2>, ArithmeticExtensionGate, MulExtensionGate, ReducingGate,
 // ReducingExtensionGate, PoseidonMdsGate, RandomAccessGate, ExponentiationGate and CosetInterpolationGate as ONE function: job in,
 // operands through a load callback, (column, value) pairs out through a store callback.  k_rec_gate_rows (kernels_witness.hip) calls
-// it with loads from the operand list / the column-major witness matrix and stores into that matrix, lcp2_rec_gate_rows validates a
-// host list with rec_job_problem / rec_value_problem, and tests/emu/emu_rec.cpp compiles the same text for the CPU.
+// it with loads from the operand list / the column-major witness matrix and stores into that matrix, lcp2_rec_gate_rows
+// (witness_rows.hip) validates a host list with rec_job_problem / rec_value_problem, and tests/emu/emu_rec.cpp compiles the same text for the CPU.
 // Layouts and values are those of the gate programs and integer generators in eth-lc-plonky2_amd/recursion_gates.py,
 // u32_gates.py (gate_coset_interpolation / row_coset_interpolation) and circuit.py (gate_arithmetic, gate_base_sum); like them the
 // layout is [RECALL] of plonky2 0.1.4 and its parity is UNPINNED.
@@ -14,6 +14,7 @@
 // The operands are streamed: a job never holds more than a few of them, so the long kinds (47 and 68 operands) need no array.
 #pragma once
 #include "gl64.hpp"
+#include "row_flag.hpp"
 
 namespace lcp2 {
 
@@ -25,7 +26,6 @@ constexpr u32 REC_ARITH_OPS = 20, REC_BASE_SUM_LIMBS = 63, REC_ARITH_EXT_OPS = 1
               REC_REDUCING_EXT_COEFFS = 32, REC_RA_BITS = 4, REC_RA_COPIES = 4, REC_RA_ITEMS = 16, REC_RA_ROUTED = 18 * 4 + 2,
               REC_EXP_BITS = 66, REC_COSET_POINTS = 16, REC_COSET_DEGREE = 8;
 constexpr u32 REC_ROW_COLUMNS = 135;  // lcp2_rec_gate_rows asks for ncols >= 135; the highest column a job writes is 133 (ExponentiationGate)
-constexpr u64 REC_NO_PROBLEM = ~0ull; // the flag word while no job of the call has been refused
 
 struct RecOperandDev {  // = lcp2_rec_operand
   uint64_t v;
@@ -84,7 +84,7 @@ LCP2_HD u32 rec_value_problem(u32 kind, u64 v) {
   if (kind == REC_COSET_INTERPOLATION && v == 0) return 11;
   return 0;
 }
-inline const char *rec_problem_str(u64 problem) {
+inline const char *rec_problem_str(u32 problem) {
   switch (problem) {
     case 1: return "row out of range";
     case 2: return "unknown kind";
@@ -279,8 +279,8 @@ LCP2_HD void rec_job_cells(const RecJobDev &j, Get get, Put put) {
 }
 
 // Lane i of k_rec_gate_rows over the jobs [begin, end) of one level; jobs[0] is job `base` of the list.  Returns 0 when the job
-// ran (or the lane had nothing to do), else the problem of job i, which then wrote nothing: the caller folds (i << 8 | problem)
-// into the flag word with a minimum, so the flag names the FIRST refused job.  A lane returns at once when the flag names a job
+// ran (or the lane had nothing to do), else the problem of job i, which then wrote nothing: the caller folds it into the flag word
+// (row_flag.hpp), so the flag names the FIRST refused job.  A lane returns at once when the flag names a job
 // of an earlier level: levels after a refused one write nothing.  check_structure = false: the list passed rec_job_problem already.
 LCP2_HD u64 rec_rows_lane(const RecJobDev *jobs, u64 base, u64 begin, u64 end, u64 i, const RecOperandDev *operands, u64 noperands,
                           u64 *wires, u32 ncols, u64 n, const u64 *flag, bool check_structure) {

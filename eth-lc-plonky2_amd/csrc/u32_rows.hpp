@@ -2,13 +2,14 @@
 //
 // The generators of U32ArithmeticGate, U32AddManyGate, U32SubtractionGate, U32RangeCheckGate and ComparisonGate as ONE function:
 // job in, (column, value) pairs out through a store callback.  k_u32_gate_rows (kernels_witness.hip) calls it with a store into
-// the column-major witness matrix, lcp2_u32_gate_rows validates a host list with u32_job_problem, and tests/emu/emu_u32.cpp
-// compiles the same text for the CPU.  Layouts and values are those of eth-lc-plonky2_amd/u32_gates.py (the docstrings of
+// the column-major witness matrix, lcp2_u32_gate_rows (witness_rows.hip) validates a host list with u32_job_problem, and
+// tests/emu/emu_u32.cpp compiles the same text for the CPU.  Layouts and values are those of eth-lc-plonky2_amd/u32_gates.py (the docstrings of
 // gate_u32_* / gate_comparison, the integer generators row_*); like them [RECALL], parity unpinned.
 // Every value written is canonical: the inputs are u32, the outputs of the integer operations are below 2^34, and the two kinds
 // of field element (the arithmetic gate's inverse, the comparison gate's signed differences) come from gl_inv / gl_neg.
 #pragma once
 #include "gl64.hpp"
+#include "row_flag.hpp"
 
 namespace lcp2 {
 
@@ -124,16 +125,15 @@ LCP2_HD void u32_job_cells(const U32JobDev &j, Put put) {
   }
 }
 
-// lane i of k_u32_gate_rows: an invalid job writes no cell and leaves 1 + its index in *flag (any one of them, if there are several)
-LCP2_HD void u32_rows_lane(const U32JobDev *jobs, u64 njobs, u64 i, u64 *wires, u64 n, u64 *flag) {
-  if (i >= njobs) return;
+// lane i of k_u32_gate_rows.  Returns 0 when the job ran (or the lane had nothing to do), else the problem of job i, which then
+// wrote nothing: the caller folds it into the flag word (row_flag.hpp)
+LCP2_HD u32 u32_rows_lane(const U32JobDev *jobs, u64 njobs, u64 i, u64 *wires, u64 n) {
+  if (i >= njobs) return 0;
   const U32JobDev job = jobs[i];
-  if (u32_job_problem(job, n)) {
-    *flag = i + 1;
-    return;
-  }
+  if (const u32 problem = u32_job_problem(job, n)) return problem;
   u64 *W = wires + job.row;
   u32_job_cells(job, [&](u32 col, u64 v) { W[(u64)col * n] = v; });
+  return 0;
 }
 
 }  // namespace lcp2

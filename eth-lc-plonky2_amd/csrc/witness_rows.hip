@@ -1,0 +1,255 @@
+// Witness-row entry points of liblcp2.so (K10): lcp2_sha256_witness, lcp2_scatter_cells, lcp2_poseidon_gate_rows,
+// lcp2_u32_gate_rows and lcp2_rec_gate_rows, with the device scratch, the host-to-device staging and the refusal flag they share.
+// The kernels are in kernels_witness.hip; the per-row texts in sha_layout.hpp, pos_rows.hpp, u32_rows.hpp and rec_rows.hpp.
+#include <cstring>
+#include "internal.hpp"
+#include "sha_layout.hpp"
+#include "pos_rows.hpp"
+#include "prover_kernels.hpp"
+#include "u32_rows.hpp"
+#include "rec_rows.hpp"
+
+using namespace lcp2;
+
+namespace {
+// scratch slot `slot` of the context with at least `bytes` bytes (contents undefined); the stream orders its reuse
+int scratch_ensure(lcp2_ctx *ctx, int slot, size_t bytes, void **out) {
+  if (ctx->scratch_bytes[slot] < bytes) {
+    if (ctx->scratch[slot]) { LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream)); LCP2_HIP(ctx, hipFree(ctx->scratch[slot])); ctx->scratch[slot] = nullptr; ctx->scratch_bytes[slot] = 0; }
+    const size_t want = bytes + bytes / 4 + 4096;
+    LCP2_HIP(ctx, hipMalloc(&ctx->scratch[slot], want));
+    ctx->scratch_bytes[slot] = want;
+  }
+  *out = ctx->scratch[slot];
+  return LCP2_OK;
+}
+
+// Host -> device staging of one call through the context's pinned buffer (a copy out of pinned memory is a plain DMA that the
+// stream orders).  The buffer is free when a call begins: every entry point here waits for its transfers before it returns.
+struct Stage {
+  lcp2_ctx *ctx;
+  size_t used = 0;  // bytes of the pinned buffer this call has handed out
+  // the next `bytes` bytes of the pinned buffer, nullptr when they do not fit (or there is no buffer)
+  char *room(size_t bytes) const { return ctx->pin && used + bytes <= lcp2_ctx::PIN_BYTES ? (char *)ctx->pin + used : nullptr; }
+  // Behind what this call already staged, else from the caller's memory: `src` must stay until the stream is synchronised.
+  // via_pin = false: never through the pinned buffer, for a list that goes up in pieces (the buffer serves one transfer per
+  // call, and the copy of an earlier piece may still be reading it)
+  int behind(void *dst, const void *src, size_t bytes, bool via_pin = true) {
+    char *p = via_pin ? room(bytes) : nullptr;
+    if (p) { memcpy(p, src, bytes); used += (bytes + 63) & ~(size_t)63; }
+    LCP2_HIP(ctx, hipMemcpyAsync(dst, p ? p : src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return LCP2_OK;
+  }
+  // Whole payload through the whole pinned buffer, in pieces of its size: `src` is reusable on return, and so is the buffer for
+  // the next call of whole(), which first waits for the copy this one left in flight.  Not to be mixed with behind() in one call
+  int whole(void *dst, const void *src, size_t bytes) {
+    if (!ctx->pin) {
+      LCP2_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+      LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      return LCP2_OK;
+    }
+    for (size_t at = 0; at < bytes; at += lcp2_ctx::PIN_BYTES) {
+      const size_t piece = std::min(lcp2_ctx::PIN_BYTES, bytes - at);
+      LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the copy out of the staging buffer that may still be in flight
+      memcpy(ctx->pin, (const char *)src + at, piece);
+      LCP2_HIP(ctx, hipMemcpyAsync((char *)dst + at, ctx->pin, piece, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return LCP2_OK;
+  }
+};
+
+// The refusal flag of a call whose kernels validate jobs (row_flag.hpp), in scratch slot 1
+struct RefusalFlag {
+  lcp2_ctx *ctx;
+  u64 *d = nullptr;
+  int begin() {
+    LCP2_TRY(scratch_ensure(ctx, 1, sizeof(u64), (void **)&d));
+    LCP2_HIP(ctx, hipMemsetAsync(d, 0xFF, sizeof(u64), ctx->stream));  // ROW_NO_PROBLEM
+    return LCP2_OK;
+  }
+  // after the last launch: launch errors first, then the word comes back and the stream is waited for (the caller's lists may go;
+  // every cell is written).  A refusal is LCP2_E_INVALID, "<family>: job N: <reason> (found on the device: <written>)"
+  int end(const char *family, const char *(*reason)(u32), const char *written) {
+    LCP2_HIP(ctx, hipGetLastError());
+    u64 flag = 0;
+    LCP2_HIP(ctx, hipMemcpyAsync(&flag, d, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+    LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag == ROW_NO_PROBLEM) return LCP2_OK;
+    return ctx->fail(LCP2_E_INVALID, std::string(family) + ": job " + std::to_string(flag >> 8) + ": " + reason((u32)(flag & 0xFF)) +
+                                         " (found on the device: " + written + ")");
+  }
+};
+}  // namespace
+
+// ------------------------------------------------------------------ K10: witness generation, device buffers
+static_assert(sizeof(lcp2_sha_job) == sizeof(ShaJobDev) && sizeof(lcp2_cell) == sizeof(CellDev), "ABI structs must match the kernels'");
+
+extern "C" int lcp2_sha256_witness(lcp2_ctx *ctx, const lcp2_sha_job *jobs, size_t njobs, const uint32_t *level_start, uint32_t nlevels,
+                                   const uint32_t *words_in, size_t nwords, uint64_t *wires, uint64_t n, uint32_t *digests) {
+  if (!ctx || !wires || (njobs && (!jobs || !level_start || nlevels == 0)) || (nwords && !words_in)) return LCP2_E_INVALID;
+  if (njobs == 0) return LCP2_OK;
+  if (level_start[0] != 0 || level_start[nlevels] != njobs) return ctx->fail(LCP2_E_INVALID, "sha witness: level table does not cover the jobs");
+  // validate once so that the kernels cannot read or write out of range
+  for (uint32_t l = 0; l < nlevels; l++) {
+    if (level_start[l] > level_start[l + 1]) return ctx->fail(LCP2_E_INVALID, "sha witness: level table not monotone");
+    for (uint32_t j = level_start[l]; j < level_start[l + 1]; j++) {
+      if ((uint64_t)jobs[j].first_row + SHA_ROWS > n) return ctx->fail(LCP2_E_INVALID, "sha witness: rows out of range");
+      for (int i = 0; i < 16; i++) {
+        int32_t s = jobs[j].in_src[i];
+        if (s >= 0 ? (size_t)s >= nwords : (uint32_t)((~s) >> 3) >= level_start[l]) return ctx->fail(LCP2_E_INVALID, "sha witness: bad message source");
+      }
+    }
+  }
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  void *d_jobs, *d_words, *d_rec;
+  LCP2_TRY(scratch_ensure(ctx, 0, njobs * sizeof(lcp2_sha_job), &d_jobs));
+  LCP2_TRY(scratch_ensure(ctx, 1, std::max<size_t>(nwords, 1) * 4, &d_words));
+  LCP2_TRY(scratch_ensure(ctx, 2, njobs * (size_t)SHA_REC_WORDS * 4, &d_rec));
+  Stage stage{ctx};
+  LCP2_TRY(stage.behind(d_jobs, jobs, njobs * sizeof(lcp2_sha_job)));
+  if (nwords) LCP2_TRY(stage.behind(d_words, words_in, nwords * 4));
+  {
+    ProfScope ps(ctx, LCP2_K_SHA256, 96.0 * njobs + 8.0 * 108 * SHA_ROWS * njobs);
+    for (uint32_t l = 0; l < nlevels; l++)
+      launch_sha_jobs_level(ctx->stream, (const ShaJobDev *)d_jobs, level_start[l], level_start[l + 1] - level_start[l],
+                            (const uint32_t *)d_words, (uint32_t *)d_rec);
+    launch_sha_fill_rows(ctx->stream, (const ShaJobDev *)d_jobs, (u32)njobs, (const uint32_t *)d_rec, (u64 *)wires, n);
+  }
+  LCP2_HIP(ctx, hipGetLastError());
+  // the 8 digest words of every job's record, as one strided copy (not the whole record buffer), through the pinned staging buffer
+  // when they fit behind the uploads
+  char *back = digests ? stage.room(njobs * 32) : nullptr;
+  if (digests)
+    LCP2_HIP(ctx, hipMemcpy2DAsync(back ? (void *)back : (void *)digests, 32, (const uint32_t *)d_rec + SHA_REC_DIGEST,
+                                   (size_t)SHA_REC_WORDS * 4, 32, njobs, hipMemcpyDeviceToHost, ctx->stream));
+  LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's job list and words may go; the digests have landed
+  if (back) memcpy(digests, back, njobs * 32);
+  return LCP2_OK;
+}
+
+extern "C" int lcp2_scatter_cells(lcp2_ctx *ctx, const lcp2_cell *cells, size_t ncells, uint64_t *wires, uint64_t n) {
+  if (!ctx || !wires || (ncells && !cells)) return LCP2_E_INVALID;
+  if (!ncells) return LCP2_OK;
+  for (size_t i = 0; i < ncells; i++)
+    if (cells[i].row >= n) return ctx->fail(LCP2_E_INVALID, "scatter: row out of range");
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  void *d;
+  LCP2_TRY(scratch_ensure(ctx, 3, ncells * sizeof(lcp2_cell), &d));
+  LCP2_TRY(Stage{ctx}.behind(d, cells, ncells * sizeof(lcp2_cell)));  // (a list pinned by the caller - lcp2_host_register - goes up as a DMA too)
+  launch_scatter_cells(ctx->stream, (const CellDev *)d, ncells, (u64 *)wires, n);
+  LCP2_HIP(ctx, hipGetLastError());
+  LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's list may go
+  return LCP2_OK;
+}
+
+extern "C" int lcp2_poseidon_gate_rows(lcp2_ctx *ctx, const lcp2_poseidon_row *rows, size_t nrows, uint64_t *wires, uint64_t n) {
+  static_assert(sizeof(lcp2_poseidon_row) == sizeof(PoseidonRowDev), "row job layouts must agree");
+  if (!ctx || !wires || (nrows && !rows)) return LCP2_E_INVALID;
+  if (!nrows) return LCP2_OK;
+  for (size_t i = 0; i < nrows; i++)
+    if (pos_row_problem(((const PoseidonRowDev *)rows)[i], n)) return ctx->fail(LCP2_E_INVALID, "poseidon rows: row out of range or swap flag not boolean");
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  void *d;
+  LCP2_TRY(scratch_ensure(ctx, 0, nrows * sizeof(lcp2_poseidon_row), &d));
+  LCP2_TRY(Stage{ctx}.behind(d, rows, nrows * sizeof(lcp2_poseidon_row)));
+  launch_poseidon_gate_rows(ctx->stream, (const PoseidonRowDev *)d, nrows, (u64 *)wires, n, ctx->d_rc);
+  LCP2_HIP(ctx, hipGetLastError());
+  LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's list may go
+  return LCP2_OK;
+}
+
+// plonky2_u32 / comparison rows: one job per operation of a row.  A host list is validated here, before anything is queued, and
+// goes up in pieces through scratch slot 0 (a 2^22-row circuit of the reference's mix has 13 M jobs, 315 MB: the piece bounds the
+// scratch, and the stream orders the kernel of one piece before the upload of the next).  A device list is validated by the
+// kernel, which is why the flag word is read back either way.
+extern "C" int lcp2_u32_gate_rows(lcp2_ctx *ctx, const lcp2_u32_job *jobs, size_t njobs, lcp2_mem jobs_mem, uint64_t *wires, uint64_t n) {
+  static_assert(sizeof(lcp2_u32_job) == 24 && sizeof(lcp2_u32_job) == sizeof(U32JobDev), "job layouts must agree");
+  static_assert(LCP2_U32_ARITHMETIC == U32_KIND_ARITHMETIC && LCP2_U32_ADD_MANY == U32_KIND_ADD_MANY && LCP2_U32_SUBTRACTION == U32_KIND_SUBTRACTION &&
+                LCP2_U32_RANGE_CHECK == U32_KIND_RANGE_CHECK && LCP2_U32_COMPARISON == U32_KIND_COMPARISON, "kind numbering must agree");
+  if (!ctx || !wires || (njobs && !jobs)) return LCP2_E_INVALID;
+  if (jobs_mem != LCP2_MEM_HOST && jobs_mem != LCP2_MEM_DEVICE) return ctx->fail(LCP2_E_INVALID, "u32 rows: bad lcp2_mem");
+  if (!njobs) return LCP2_OK;
+  const U32JobDev *list = (const U32JobDev *)jobs;
+  if (jobs_mem == LCP2_MEM_HOST)
+    for (size_t i = 0; i < njobs; i++)
+      if (u32 problem = u32_job_problem(list[i], n))
+        return ctx->fail(LCP2_E_INVALID, "u32 rows: job " + std::to_string(i) + ": " + u32_problem_str(problem));
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  RefusalFlag flag{ctx};
+  LCP2_TRY(flag.begin());
+  if (jobs_mem == LCP2_MEM_DEVICE) {
+    launch_u32_gate_rows(ctx->stream, list, njobs, (u64 *)wires, n, flag.d);
+  } else {
+    constexpr size_t PIECE = (size_t)1 << 20;  // jobs: 24 MiB
+    void *d;
+    LCP2_TRY(scratch_ensure(ctx, 0, std::min(njobs, PIECE) * sizeof(lcp2_u32_job), &d));
+    for (size_t at = 0; at < njobs; at += PIECE) {
+      const size_t count = std::min(PIECE, njobs - at);
+      LCP2_TRY(Stage{ctx}.behind(d, list + at, count * sizeof(lcp2_u32_job), njobs <= PIECE));
+      launch_u32_gate_rows(ctx->stream, (const U32JobDev *)d, count, (u64 *)wires, n, flag.d);
+    }
+  }
+  return flag.end("u32 rows", u32_problem_str, "the valid jobs are written");
+}
+
+// Recursion-gate rows, level by level.  A host list is validated here before anything is queued (structure of every job, and the
+// value conditions of the operands that are IMM); its operands go up whole, before any job, and its jobs in pieces of the pinned
+// staging buffer's size.  A piece may end inside a level: the jobs of a level do not depend on one another, so the level is then two
+// launches, and a piece that holds the end of one level and the start of the next launches them apart, in order.  A device list is
+// validated by the kernel.  Either way the value conditions of CELL operands can only be seen on the device: the flag word is
+// read once, after the last level, because a level that begins after a refused job writes nothing (rec_rows_lane).
+extern "C" int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_t njobs, const lcp2_rec_operand *operands, size_t noperands,
+                                  const uint32_t *level_ends, size_t nlevels, lcp2_mem lists_mem, uint64_t *wires, uint32_t ncols, uint64_t n) {
+  static_assert(sizeof(lcp2_rec_job) == 16 && sizeof(lcp2_rec_job) == sizeof(RecJobDev) && sizeof(lcp2_rec_operand) == 16 &&
+                sizeof(lcp2_rec_operand) == sizeof(RecOperandDev), "record layouts must agree");
+  static_assert(LCP2_REC_ARITHMETIC == REC_ARITHMETIC && LCP2_REC_BASE_SUM == REC_BASE_SUM && LCP2_REC_ARITHMETIC_EXT == REC_ARITHMETIC_EXT &&
+                LCP2_REC_MUL_EXT == REC_MUL_EXT && LCP2_REC_REDUCING == REC_REDUCING && LCP2_REC_REDUCING_EXT == REC_REDUCING_EXT &&
+                LCP2_REC_POSEIDON_MDS == REC_POSEIDON_MDS && LCP2_REC_RANDOM_ACCESS == REC_RANDOM_ACCESS &&
+                LCP2_REC_EXPONENTIATION == REC_EXPONENTIATION && LCP2_REC_COSET_INTERPOLATION == REC_COSET_INTERPOLATION &&
+                LCP2_REC_KINDS == REC_KINDS && LCP2_REC_IMM == REC_IMM && LCP2_REC_CELL == REC_CELL, "numbering must agree");
+  if (!ctx || !wires || (njobs && (!jobs || !level_ends || !nlevels)) || (noperands && !operands)) return LCP2_E_INVALID;
+  if (lists_mem != LCP2_MEM_HOST && lists_mem != LCP2_MEM_DEVICE) return ctx->fail(LCP2_E_INVALID, "rec rows: bad lcp2_mem");
+  if (!njobs) return LCP2_OK;
+  if (ncols < REC_ROW_COLUMNS) return ctx->fail(LCP2_E_INVALID, "rec rows: the matrix needs at least 135 columns");
+  for (size_t l = 0; l < nlevels; l++)
+    if (level_ends[l] < (l ? level_ends[l - 1] : 0) || level_ends[l] > njobs)
+      return ctx->fail(LCP2_E_INVALID, "rec rows: level_ends is not ascending at level " + std::to_string(l));
+  if (level_ends[nlevels - 1] != njobs) return ctx->fail(LCP2_E_INVALID, "rec rows: level_ends does not end at njobs");
+  const RecJobDev *list = (const RecJobDev *)jobs;
+  const RecOperandDev *ops = (const RecOperandDev *)operands;
+  const bool host = lists_mem == LCP2_MEM_HOST;
+  if (host)
+    for (size_t i = 0; i < njobs; i++) {
+      u32 problem = rec_job_problem(list[i], ops, noperands, ncols, n);
+      const int checked = problem ? -1 : rec_value_operand(list[i].kind, list[i].op);
+      if (checked >= 0 && ops[(size_t)list[i].first_operand + checked].src == REC_IMM)
+        problem = rec_value_problem(list[i].kind, gl_canon(ops[(size_t)list[i].first_operand + checked].v));
+      if (problem) return ctx->fail(LCP2_E_INVALID, "rec rows: job " + std::to_string(i) + ": " + rec_problem_str(problem));
+    }
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  RefusalFlag flag{ctx};
+  LCP2_TRY(flag.begin());
+  if (!host) {
+    for (size_t l = 0; l < nlevels; l++)
+      launch_rec_gate_rows(ctx->stream, list, 0, l ? level_ends[l - 1] : 0, level_ends[l], ops, noperands, (u64 *)wires, ncols, n, flag.d, true);
+  } else {
+    constexpr size_t PIECE = lcp2_ctx::PIN_BYTES / sizeof(lcp2_rec_job);  // jobs
+    void *d_jobs, *d_ops;
+    LCP2_TRY(scratch_ensure(ctx, 0, std::min(njobs, PIECE) * sizeof(lcp2_rec_job), &d_jobs));
+    LCP2_TRY(scratch_ensure(ctx, 2, std::max<size_t>(noperands, 1) * sizeof(lcp2_rec_operand), &d_ops));
+    Stage stage{ctx};
+    if (noperands) LCP2_TRY(stage.whole(d_ops, ops, noperands * sizeof(lcp2_rec_operand)));  // before the jobs that use them
+    size_t level = 0;
+    for (size_t at = 0; at < njobs; at += PIECE) {
+      const size_t stop = std::min(njobs, at + PIECE);
+      LCP2_TRY(stage.whole(d_jobs, list + at, (stop - at) * sizeof(lcp2_rec_job)));  // (waits for the launches of the piece before)
+      for (; level < nlevels; level++) {  // the part of every level that lies in [at, stop)
+        const size_t begin = std::max<size_t>(level ? level_ends[level - 1] : 0, at), end = std::min<size_t>(level_ends[level], stop);
+        launch_rec_gate_rows(ctx->stream, (const RecJobDev *)d_jobs, at, begin, end, (const RecOperandDev *)d_ops, noperands, (u64 *)wires, ncols, n,
+                             flag.d, false);
+        if (level_ends[level] > stop) break;  // the level goes on in the next piece
+      }
+    }
+  }
+  return flag.end("rec rows", rec_problem_str, "the valid jobs of its level and of the levels before are written, later levels are not");
+}

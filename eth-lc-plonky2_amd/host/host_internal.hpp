@@ -4,6 +4,7 @@
 #include <cstring>
 #include <functional>
 #include "lc_plonky2.hpp"
+#include "../csrc/pos_rows.hpp"
 
 namespace lc {
 
@@ -20,11 +21,9 @@ struct GateSetLayout {
 };
 GateSetLayout build_gate_set(uint32_t max_degree);
 
-// PoseidonGate wire layout (plonky2 gates/poseidon.rs) and the host-side permutation that fills a row (poseidon_host.cpp)
-constexpr uint32_t POS_WIRE_INPUT = 0, POS_WIRE_OUTPUT = 12, POS_WIRE_SWAP = 24, POS_WIRE_DELTA = 25, POS_WIRE_FULL_0 = 29,
-                   POS_WIRE_PARTIAL = 65, POS_WIRE_FULL_1 = 87, POS_GATE_WIRES = 135;
-inline uint32_t pos_wire_full_sbox_0(uint32_t round, uint32_t i) { return POS_WIRE_FULL_0 + 12 * (round - 1) + i; }  // rounds 1..3
-inline uint32_t pos_wire_full_sbox_1(uint32_t round, uint32_t i) { return POS_WIRE_FULL_1 + 12 * round + i; }
+// PoseidonGate wire layout (csrc/pos_rows.hpp, shared with the device) and the host-side permutation that fills a row (poseidon_host.cpp)
+using lcp2::POS_WIRE_INPUT; using lcp2::POS_WIRE_OUTPUT; using lcp2::POS_WIRE_SWAP; using lcp2::POS_WIRE_DELTA; using lcp2::POS_WIRE_PARTIAL;
+using lcp2::POS_GATE_WIRES; using lcp2::pos_wire_full_sbox_0; using lcp2::pos_wire_full_sbox_1;
 const uint64_t *poseidon_round_constants();                    // 360 values
 void poseidon_gate_row(const F in[12], bool swap, F row[135]); // PoseidonGenerator::run_once: every wire of one row
 void poseidon_gate_outputs(const F in[12], bool swap, F out[12]); // the 12 output wires alone (the row itself is generated on the device)

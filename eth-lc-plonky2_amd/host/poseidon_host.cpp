@@ -1,7 +1,6 @@
 // Host-side Poseidon for circuit construction: the witness of a PoseidonGate row (plonky2 0.1.4 gates/poseidon.rs
 // `PoseidonGenerator::run_once`).  A handful of rows per circuit (the in-circuit public-input hash); the prover's
 // hashing runs in the HIP kernels.  Uses the portable arithmetic of csrc/poseidon.hpp (plain C++ outside hipcc).
-#include "../csrc/poseidon.hpp"
 #include <cstring>
 #include "host_internal.hpp"
 
@@ -57,41 +56,6 @@ const uint64_t *poseidon_round_constants() {
   if (!ready) { lcp2::pos_derive_round_constants((lcp2::u64 *)rc); ready = true; }
   return rc;
 }
-
-// The naive round form (add constants, S-box, MDS), recording the value that enters every S-box that has a wire.  The value
-// entering lane 0's S-box in a partial round is the same in plonky2's fast-partial-round refactoring.
-void poseidon_gate_row(const F in[12], bool swap, F row[135]) {
-  using namespace lcp2;
-  const uint64_t *rc = poseidon_round_constants();
-  for (uint32_t i = 0; i < POS_GATE_WIRES; i++) row[i] = 0;
-  u64 s[12];
-  for (int i = 0; i < 12; i++) { row[POS_WIRE_INPUT + i] = in[i] % GL_P; s[i] = row[POS_WIRE_INPUT + i]; }
-  row[POS_WIRE_SWAP] = swap ? 1 : 0;
-  for (int i = 0; i < 4; i++) {
-    const u64 delta = swap ? gl_sub(s[i + 4], s[i]) : 0;
-    row[POS_WIRE_DELTA + i] = delta;
-    const u64 l = gl_add(s[i], delta), r = gl_sub(s[i + 4], delta);
-    s[i] = l; s[i + 4] = r;
-  }
-  for (int round = 0; round < POS_ROUNDS; round++) {
-    for (int i = 0; i < 12; i++) s[i] = gl_add(s[i], rc[12 * round + i]);
-    const bool full = round < POS_FULL_HALF || round >= POS_FULL_HALF + POS_PARTIAL;
-    if (full) {
-      for (int i = 0; i < 12; i++) {
-        if (round >= 1 && round < POS_FULL_HALF) row[pos_wire_full_sbox_0(round, i)] = s[i];
-        if (round >= POS_FULL_HALF + POS_PARTIAL) row[pos_wire_full_sbox_1(round - POS_FULL_HALF - POS_PARTIAL, i)] = s[i];
-        s[i] = gl_canon(pos_sbox(s[i]));
-      }
-    } else {
-      row[POS_WIRE_PARTIAL + (round - POS_FULL_HALF)] = s[0];
-      s[0] = gl_canon(pos_sbox(s[0]));
-    }
-    host_mds(s);
-    for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
-  }
-  for (int i = 0; i < 12; i++) row[POS_WIRE_OUTPUT + i] = s[i];
-}
-
 
 // The outputs of a PoseidonGate row without its trace: swap, then the permutation.  This is what a generator downstream needs; the
 // row's 135 cells are produced on the device from (inputs, swap) (lcp2_poseidon_gate_rows).  The recursive verifier's sponge over
@@ -277,6 +241,13 @@ inline void partial3(lcp2::u64 s[12], const lcp2::u64 *k) {
   if (HAVE_AVX2) partial3_avx2(s, k); else partial3_portable(s, k);
 }
 }  // namespace
+
+// Every wire of one PoseidonGate row: the text the device runs (csrc/pos_rows.hpp), with the vector form of the MDS layer
+void poseidon_gate_row(const F in[12], bool swap, F row[135]) {
+  lcp2::u64 x[12];
+  for (int i = 0; i < 12; i++) x[i] = in[i];
+  lcp2::pos_row_cells(x, swap, extended_round_constants(), host_mds, [&](lcp2::u32 col, lcp2::u64 v) { row[col] = v; });
+}
 
 // for the tests: the same function on the portable path
 void poseidon_gate_outputs_impl(const F in[12], bool swap, F out[12], bool portable);

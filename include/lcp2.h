@@ -222,7 +222,8 @@ int lcp2_poseidon_gate_rows(lcp2_ctx *ctx, const lcp2_poseidon_row *rows, size_t
  * neighbouring rows of the same columns and every store of a wave is contiguous.  The library does not sort.
  * jobs_mem = LCP2_MEM_HOST: the list is validated before anything is launched, and a refused list writes nothing.
  * LCP2_MEM_DEVICE: the kernel validates; an invalid job writes no cell, the valid ones are written, and the call still returns
- * LCP2_E_INVALID.  Refused (LCP2_E_INVALID, the reason in lcp2_last_error): row >= n, an unknown kind, op out of range for the
+ * LCP2_E_INVALID; lcp2_last_error then names the FIRST refused job of the list ("job N: reason"), as it does for a host list.
+ * Refused (LCP2_E_INVALID, the reason in lcp2_last_error): row >= n, an unknown kind, op out of range for the
  * kind, a subtraction borrow above 1; also a null ctx or wires, or a null list with njobs > 0.  njobs = 0 is LCP2_OK.
  * The context's stream is synchronised on return. */
 enum { LCP2_U32_ARITHMETIC = 0, LCP2_U32_ADD_MANY = 1, LCP2_U32_SUBTRACTION = 2, LCP2_U32_RANGE_CHECK = 3, LCP2_U32_COMPARISON = 4 };

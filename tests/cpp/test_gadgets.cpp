@@ -828,8 +828,12 @@ static void test_wrap_chain() { wrap_chain(wrap_first(), wrap_second(), false); 
 static void test_wrap_chain_tampered_inner_panics() { wrap_chain(wrap_first(), wrap_second(), true); }
 
 // the outputs-only generator of a PoseidonGate row (what generate_witness_gpu runs on the host; the row itself is filled on the device)
-// against the full row generator and the oracle's permutation, swap included, non-canonical inputs included
+// against the full row generator and the oracle's permutation, swap included, non-canonical inputs included; and the full row
+// generator (the AVX2 MDS layer where the CPU has it) against the text it shares with the device (csrc/pos_rows.hpp) run with the
+// portable layer pos_mds, every one of the 135 cells
 static void test_poseidon_gate_outputs_match_rows() {
+  static lcp2::u64 rc[lcp2::POS_ROUNDS * lcp2::POS_W];
+  lcp2::pos_derive_round_constants(rc);
   uint64_t seed = 12345;
   auto rnd = [&]() { seed = seed * 6364136223846793005ull + 1442695040888963407ull; uint64_t z = seed; z ^= z >> 29; z *= 0xBF58476D1CE4E5B9ull; return z ^ (z >> 32); };
   for (int t = 0; t < 500; t++) {
@@ -838,6 +842,14 @@ static void test_poseidon_gate_outputs_match_rows() {
     const bool swap = t & 1;
     F out_portable[12];
     poseidon_gate_row(in, swap, row);
+    lcp2::u64 x[12], shared[POS_GATE_WIRES];
+    uint32_t stores = 0;
+    for (int i = 0; i < 12; i++) x[i] = in[i];
+    for (auto &c : shared) c = ~0ull;
+    lcp2::pos_row_cells(x, swap, rc, [](lcp2::u64 *s) { lcp2::pos_mds(s); }, [&](lcp2::u32 col, lcp2::u64 v) { shared[col] = v; stores++; });
+    if (stores != POS_GATE_WIRES) throw std::runtime_error("pos_row_cells does not store 135 cells");
+    for (uint32_t c = 0; c < POS_GATE_WIRES; c++)
+      if (row[c] != shared[c]) throw std::runtime_error("poseidon_gate_row differs from the shared row text at case " + std::to_string(t) + ", column " + std::to_string(c));
     poseidon_gate_outputs(in, swap, out);                         // AVX2 linear layers where the CPU has them
     poseidon_gate_outputs_impl(in, swap, out_portable, true);     // 128-bit multiply-accumulates
     for (int i = 0; i < 12; i++) if (out[i] != out_portable[i]) throw std::runtime_error("poseidon_gate_outputs: AVX2 and portable paths differ");

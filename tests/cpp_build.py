@@ -7,7 +7,8 @@ CPP = os.path.join(ROOT, "tests", "cpp")
 HOST = os.path.join(ROOT, "eth-lc-plonky2_amd", "host")
 BIN = os.path.join(CPP, "test_gadgets")
 HOST_SOURCES = ("gates.cpp", "builder.cpp", "gadgets.cpp", "light_client_update.cpp", "poseidon_host.cpp", "recursion.cpp", "biguint.cpp")
-SHARED_HEADERS = [os.path.join(ROOT, "include", "lcp2.h"), os.path.join(ROOT, "eth-lc-plonky2_amd", "csrc", "gate_program.hpp")]  # what host/ includes from outside
+SHARED_HEADERS = [os.path.join(ROOT, "include", "lcp2.h")] + [os.path.join(ROOT, "eth-lc-plonky2_amd", "csrc", h) for h in
+                  ("gate_program.hpp", "pos_rows.hpp", "poseidon.hpp", "gl64.hpp")]  # what host/ includes from outside
 EXAMPLE_SRC = os.path.join(ROOT, "examples", "lc_prover.cpp")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "lc_prover")
 

@@ -36,7 +36,7 @@ unsigned emu_rec_job_cells(const RecJobDev *job, const RecOperandDev *operands, 
 }
 
 // k_rec_gate_rows for the jobs [begin, end) of one level over a grid of blocks of `threads` lanes, lane by lane; *flag as the
-// kernel keeps it (REC_NO_PROBLEM = ~0 before the first level)
+// kernel keeps it (ROW_NO_PROBLEM = ~0 before the first level)
 void emu_rec_level(const RecJobDev *jobs, unsigned long long begin, unsigned long long end, const RecOperandDev *operands,
                    unsigned long long noperands, unsigned long long *wires, unsigned ncols, unsigned long long n, unsigned long long *flag,
                    unsigned threads) {
@@ -45,7 +45,7 @@ void emu_rec_level(const RecJobDev *jobs, unsigned long long begin, unsigned lon
     for (unsigned t = 0; t < threads; t++) {
       const u64 i = begin + b * threads + t;
       const u64 problem = rec_rows_lane(jobs, 0, begin, end, i, operands, noperands, wires, ncols, n, flag, true);
-      if (problem && (i << 8 | problem) < *flag) *flag = i << 8 | problem;
+      if (problem && row_refusal(i, problem) < *flag) *flag = row_refusal(i, problem);
     }
 }
 

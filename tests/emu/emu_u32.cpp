@@ -22,11 +22,19 @@ unsigned emu_u32_job_cells(const U32JobDev *job, unsigned *cols, unsigned long l
   return count;
 }
 
-// k_u32_gate_rows over a grid of `blocks` blocks of `threads` lanes, lane by lane
+unsigned long long emu_u32_no_problem() { return ROW_NO_PROBLEM; }
+const char *emu_u32_problem_str(unsigned problem) { return u32_problem_str(problem); }
+
+// k_u32_gate_rows over a grid of `blocks` blocks of `threads` lanes, lane by lane; *flag as the kernel keeps it (ROW_NO_PROBLEM
+// before the launch)
 void emu_u32_gate_rows(const U32JobDev *jobs, unsigned long long njobs, unsigned long long *wires, unsigned long long n,
                        unsigned long long *flag, unsigned blocks, unsigned threads) {
   for (unsigned b = 0; b < blocks; b++)
-    for (unsigned t = 0; t < threads; t++) u32_rows_lane(jobs, njobs, (u64)b * threads + t, wires, n, flag);
+    for (unsigned t = 0; t < threads; t++) {
+      const u64 i = (u64)b * threads + t;
+      const u32 problem = u32_rows_lane(jobs, njobs, i, wires, n);
+      if (problem && row_refusal(i, problem) < *flag) *flag = row_refusal(i, problem);
+    }
 }
 
 }  // extern "C"

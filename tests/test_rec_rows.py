@@ -38,7 +38,7 @@ def rg():
 @pytest.fixture(scope="module")
 def emur():
     """tests/emu/libemu_rec.so, built with g++ the way emu32 builds libemu_u32.so"""
-    deps = [SRC, os.path.join(CSRC, "rec_rows.hpp"), os.path.join(CSRC, "gl64.hpp")]
+    deps = [SRC] + [os.path.join(CSRC, h) for h in ("rec_rows.hpp", "row_flag.hpp", "gl64.hpp")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
     E = ctypes.CDLL(LIB)

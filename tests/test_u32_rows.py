@@ -21,6 +21,7 @@ CSRC = os.path.join(HERE, "..", "eth-lc-plonky2_amd", "csrc")
 P = 0xFFFFFFFF00000001
 M = 0xFFFFFFFF
 INVALID = -1
+NONE = (1 << 64) - 1   # the flag word while nothing is refused
 ARITH, ADD, SUB, RANGE, CMP = range(5)
 OPS = {ARITH: 3, ADD: 5, SUB: 6, RANGE: 7, CMP: 1}
 GATE = {ARITH: "U32ArithmeticGate", ADD: "U32AddManyGate", SUB: "U32SubtractionGate", RANGE: "U32RangeCheckGate", CMP: "ComparisonGate"}
@@ -30,7 +31,7 @@ NW = 135
 @pytest.fixture(scope="module")
 def emu32():
     """tests/emu/libemu_u32.so, built with g++ the way emu_lib builds libemu.so"""
-    deps = [SRC, os.path.join(CSRC, "u32_rows.hpp"), os.path.join(CSRC, "gl64.hpp")]
+    deps = [SRC] + [os.path.join(CSRC, h) for h in ("u32_rows.hpp", "row_flag.hpp", "gl64.hpp")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
     E = ctypes.CDLL(LIB)
@@ -43,6 +44,9 @@ def emu32():
     E.emu_u32_job_problem.argtypes = [V, c.c_uint64]
     E.emu_u32_job_cells.restype = c.c_uint
     E.emu_u32_job_cells.argtypes = [V, V, V, c.c_uint]
+    E.emu_u32_no_problem.restype = c.c_uint64
+    E.emu_u32_problem_str.restype = c.c_char_p
+    E.emu_u32_problem_str.argtypes = [c.c_uint]
     E.emu_u32_gate_rows.restype = None
     E.emu_u32_gate_rows.argtypes = [V, c.c_uint64, V, c.c_uint64, V, c.c_uint, c.c_uint]
     return E
@@ -255,20 +259,39 @@ def test_witness_jobs_of_a_small_mix_circuit_refill_it_on_the_cpu(emu32):
     n = circ.n
     zeroed, owned = zeroed_and_owned(wires, gate_of_row, G)
     for threads in (64, 256):
-        got, flag = zeroed.copy(), np.zeros(1, dtype=np.uint64)
+        got, flag = zeroed.copy(), np.full(1, NONE, dtype=np.uint64)
         blocks = (jobs.size + threads - 1) // threads
         emu32.emu_u32_gate_rows(vp(jobs), jobs.size, vp(got), n, vp(flag), blocks, threads)
-        assert flag[0] == 0
+        assert flag[0] == NONE == emu32.emu_u32_no_problem()
         assert (got[owned] == wires[owned]).all() and (got[~owned] == zeroed[~owned]).all()
-    # an invalid job in the list: it writes nothing, the others are written, the flag names it
+    # an invalid job in the list: it writes nothing, the others are written, the flag names it and why
     bad = jobs.copy()
     bad[7]["row"] = n
-    got, flag = zeroed.copy(), np.zeros(1, dtype=np.uint64)
+    got, flag = zeroed.copy(), np.full(1, NONE, dtype=np.uint64)
     emu32.emu_u32_gate_rows(vp(bad), bad.size, vp(got), n, vp(flag), (bad.size + 63) // 64, 64)
-    assert flag[0] == 8
+    assert flag[0] == (7 << 8 | 1)
     skipped = np.zeros_like(owned)
     skipped[ug.job_columns(int(jobs[7]["kind"]), int(jobs[7]["op"])), int(jobs[7]["row"])] = True
     assert (got[owned & ~skipped] == wires[owned & ~skipped]).all() and (got[~owned | skipped] == zeroed[~owned | skipped]).all()
+    # two invalid jobs, the later one in another block: the flag names the lower index, neither writes
+    assert jobs.size > 70
+    bad[70]["kind"] = 9
+    for threads in (64, 256):
+        got, flag = zeroed.copy(), np.full(1, NONE, dtype=np.uint64)
+        emu32.emu_u32_gate_rows(vp(bad), bad.size, vp(got), n, vp(flag), (bad.size + threads - 1) // threads, threads)
+        assert flag[0] == (7 << 8 | 1)
+        skipped[ug.job_columns(int(jobs[70]["kind"]), int(jobs[70]["op"])), int(jobs[70]["row"])] = True
+        assert (got[owned & ~skipped] == wires[owned & ~skipped]).all() and (got[~owned | skipped] == zeroed[~owned | skipped]).all()
+    only_later = jobs.copy()
+    only_later[70]["kind"] = 9
+    flag = np.full(1, NONE, dtype=np.uint64)
+    emu32.emu_u32_gate_rows(vp(only_later), only_later.size, vp(zeroed.copy()), n, vp(flag), (jobs.size + 63) // 64, 64)
+    assert flag[0] == (70 << 8 | 2)
+    # the fold is a minimum: a word that already names a later job is replaced, one that names an earlier job stays
+    for before, after in ((100 << 8 | 3, 70 << 8 | 2), (3 << 8 | 4, 3 << 8 | 4)):
+        flag = np.full(1, before, dtype=np.uint64)
+        emu32.emu_u32_gate_rows(vp(only_later), only_later.size, vp(zeroed.copy()), n, vp(flag), (jobs.size + 63) // 64, 64)
+        assert flag[0] == after
 
 
 def zeroed_and_owned(wires, gate_of_row, G):
@@ -461,6 +484,29 @@ def test_refusals_on_the_device(gpu_ctx):
     gpu_ctx.u32_gate_rows(good, dm.ptr, n)   # the context still works after the refusals
     assert (dm.read() == want).all()
     dm.free()
+
+
+@pytest.mark.gpu
+def test_two_refused_jobs_in_a_device_list(gpu_ctx, emu32):
+    """600 jobs in HBM (three blocks of 256 lanes) with two refused ones, the later one in the first wave of the last block, the
+    earlier one in the middle block: the call names the lower index and its reason, whichever lane ran first; both write nothing"""
+    import eth_lc_plonky2_amd as m
+    lib = gpu_ctx.lib
+    n = 128
+    good, want = range_jobs(598, n, np.random.default_rng(19))
+    first, second = make_jobs([BAD_JOBS[8]]), make_jobs([(n, RANGE, 0, (1,))])   # borrow above 1; then row out of range
+    for lo, hi in ((300, 513), (0, 599), (255, 256)):
+        mixed = np.concatenate([good[:lo], first, good[lo:hi - 1], second, good[hi - 1:]])
+        assert mixed.size == 600 and emu32.emu_u32_job_problem(vp(mixed[lo:lo + 1]), n) == 4 and emu32.emu_u32_job_problem(vp(mixed[hi:hi + 1]), n) == 1
+        dm = DeviceMatrix(gpu_ctx, np.zeros((NW, n), dtype=np.uint64))
+        d_jobs = upload_jobs(gpu_ctx, mixed)
+        assert lib.lcp2_u32_gate_rows(gpu_ctx.handle, ctypes.c_void_p(d_jobs), mixed.size, m.MEM_DEVICE, ctypes.c_void_p(dm.ptr), n) == INVALID
+        reason = lib.lcp2_last_error(gpu_ctx.handle)
+        assert b"job %d:" % lo in reason and emu32.emu_u32_problem_str(4) in reason and b"job %d:" % hi not in reason, reason
+        assert emu32.emu_u32_problem_str(4) == b"subtraction borrow above 1"
+        assert (dm.read() == want).all()
+        gpu_ctx.buffer_free(d_jobs)
+        dm.free()
 
 
 @pytest.mark.gpu
