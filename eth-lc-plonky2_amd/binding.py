@@ -83,6 +83,17 @@ REC_IMM, REC_CELL = 0, 1
 REC_OPERAND_DTYPE = np.dtype([("v", "<u8"), ("col", "<u4"), ("src", "<u4")])   # RecOperand as a numpy record
 REC_JOB_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u2"), ("op", "<u2"), ("first_operand", "<u4"), ("reserved", "<u4")])
 assert REC_OPERAND_DTYPE.itemsize == ctypes.sizeof(RecOperand) == 16 and REC_JOB_DTYPE.itemsize == ctypes.sizeof(RecJob) == 16
+PLAN_IMM, PLAN_CELL, PLAN_PREV = 0, 1, 2   # src of a PoseidonGate operand of a witness plan; PREV: output `col` of the chain's previous job
+POS_JOB_DTYPE = np.dtype([("row", "<u4"), ("first_operand", "<u4")])   # lcp2_pos_job: 13 operands, swap then in[0..11]
+assert POS_JOB_DTYPE.itemsize == 8
+
+
+class WitnessPlan(ctypes.Structure):
+    """lcp2_witness_plan: rec jobs and PoseidonGate chains over one operand list, in levels (lcp2_witness_plan_rows)"""
+    _fields_ = [("rec_jobs", ctypes.c_void_p), ("nrec", ctypes.c_size_t), ("rec_level_ends", ctypes.c_void_p),
+                ("pos_jobs", ctypes.c_void_p), ("npos", ctypes.c_size_t), ("chain_ends", ctypes.c_void_p), ("nchains", ctypes.c_size_t),
+                ("pos_level_ends", ctypes.c_void_p), ("operands", ctypes.c_void_p), ("noperands", ctypes.c_size_t), ("nlevels", ctypes.c_size_t)]
+
 
 _lib = None
 
@@ -147,6 +158,7 @@ def load_library():
         "lcp2_u32_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.c_uint64]),
         "lcp2_rec_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p,
                                          c.c_uint32, c.c_uint64]),
+        "lcp2_witness_plan_rows": (c.c_int, [c.c_void_p, c.POINTER(WitnessPlan), c.c_int, c.c_void_p, c.c_uint32, c.c_uint64]),
         "lcp2_commit_wires_rows_begin": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_commit_wires_chunk": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32]),
         "lcp2_commit_wires_rows_finish": (c.c_int, [c.c_void_p, c.c_void_p]),
@@ -463,6 +475,35 @@ class Context:
             nj, no, pj, po, mem = int(njobs), int(noperands), ctypes.c_void_p(jobs), ctypes.c_void_p(operands), MEM_DEVICE
         self._check(self.lib.lcp2_rec_gate_rows(self.handle, pj, nj, po, no, _ptr(ends) if ends.size else None, ends.size, mem,
                                                 ctypes.c_void_p(wires_dev), int(ncols), int(n)))
+
+    def witness_plan_rows(self, rec_jobs, pos_jobs, chain_ends, operands, rec_level_ends, pos_level_ends, wires_dev, ncols, n,
+                          nrec=None, npos=None, nchains=None, noperands=None):
+        """lcp2_witness_plan_rows: runs a recorded plan of rec jobs and PoseidonGate chains level by level on the device witness
+        matrix `wires_dev` (a pointer, [ncols >= 135][n] column-major).  rec_jobs / pos_jobs / chain_ends / operands: numpy arrays
+        of REC_JOB_DTYPE / POS_JOB_DTYPE / uint32 / REC_OPERAND_DTYPE (host lists: validated before anything runs), or four device
+        pointers with nrec, npos, nchains and noperands (validated by the kernels).  rec_level_ends / pos_level_ends: the index
+        after the last rec job / the last CHAIN of every level, always on the host and equally long.
+        recursion_gates.pack_witness_plan returns all six."""
+        rends = np.ascontiguousarray(rec_level_ends, dtype=np.uint32).ravel()
+        pends = np.ascontiguousarray(pos_level_ends, dtype=np.uint32).ravel()
+        if rends.size != pends.size:
+            raise Lcp2Error(-1, "rec_level_ends and pos_level_ends must have one entry per level each")
+        lists = (rec_jobs, pos_jobs, chain_ends, operands)
+        on_host = [isinstance(a, np.ndarray) for a in lists]
+        if any(on_host) != all(on_host):
+            raise Lcp2Error(-1, "the four lists must all be host arrays or all be device pointers")
+        if all(on_host):
+            if (rec_jobs.dtype, pos_jobs.dtype, chain_ends.dtype, operands.dtype) != (REC_JOB_DTYPE, POS_JOB_DTYPE, np.dtype(np.uint32), REC_OPERAND_DTYPE):
+                raise Lcp2Error(-1, "the lists must be arrays of REC_JOB_DTYPE / POS_JOB_DTYPE / uint32 / REC_OPERAND_DTYPE records")
+            keep = [np.ascontiguousarray(a).ravel() for a in lists]
+            counts, ptrs, mem = [a.size for a in keep], [a.ctypes.data if a.size else None for a in keep], MEM_HOST
+        else:
+            if None in (nrec, npos, nchains, noperands):
+                raise Lcp2Error(-1, "device lists need nrec, npos, nchains and noperands")
+            counts, ptrs, mem = [int(nrec), int(npos), int(nchains), int(noperands)], [a or None for a in lists], MEM_DEVICE
+        plan = WitnessPlan(ptrs[0], counts[0], rends.ctypes.data if rends.size else None, ptrs[1], counts[1], ptrs[2], counts[2],
+                           pends.ctypes.data if pends.size else None, ptrs[3], counts[3], rends.size)
+        self._check(self.lib.lcp2_witness_plan_rows(self.handle, ctypes.byref(plan), mem, ctypes.c_void_p(wires_dev), int(ncols), int(n)))
 
     def buffer_alloc(self, words):
         p = ctypes.c_void_p()

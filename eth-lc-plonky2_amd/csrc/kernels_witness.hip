@@ -15,6 +15,7 @@
 #include "prover_kernels.hpp"
 #include "u32_rows.hpp"
 #include "rec_rows.hpp"
+#include "pos_plan.hpp"
 
 namespace lcp2 {
 
@@ -230,6 +231,103 @@ void launch_rec_gate_rows(hipStream_t s, const RecJobDev *jobs, u64 base, u64 be
   if (begin >= end) return;
   hipLaunchKernelGGL(k_rec_gate_rows, dim3((unsigned)((end - begin + REC_ROWS_THREADS - 1) / REC_ROWS_THREADS)), dim3(REC_ROWS_THREADS), 0, s,
                      jobs, base, begin, end, operands, noperands, wires, ncols, n, flag, check_structure ? 1 : 0);
+}
+
+// PoseidonGate CHAINS of one level of lcp2_witness_plan_rows (pos_plan.hpp: pos_plan_chain_lane is the one-lane reference of this
+// kernel and writes the same cells).  A chain is a sequence of dependent permutations, so it is latency bound and runs in the
+// lane-cooperative form of poseidon.hpp (pos_permute_coop_hooked): ONE 16-LANE GROUP PER CHAIN, four chains per wave, 16 per block;
+// lane j < 12 owns state element j, lane 12 the swap flag, lanes 13..15 ride along with lane 12's operand and store nothing.
+// Per row: every lane reads the 8-byte job (one address per group) and ITS operand record (16 bytes; lanes 0..11 neighbouring
+// records), checks it before any index of it is used, and loads its cell (8 bytes) if it is a CELL; a PREV operand is one shuffle
+// of the outputs the group kept in registers from the row before - they are never re-read from the matrix, so a chain has no
+// store-then-load dependency inside the launch.  The group's verdict is a minimum over its 16 lanes in pos_plan_problem's order
+// (structure by operand index, then the swap value); the swap flag is one shuffle from lane 12, the four deltas one shuffle between
+// lanes j and j ^ 4; the 30 rounds take their constants from LDS.  Lane j stores input j, output j and what enters S-box j of the
+// full rounds that have a wire, lane 0 the 22 partial-round values, lanes 0..3 the deltas, lane 12 the swap flag: all canonical.
+// Control flow: the shuffles read only the group's own lanes, and all 16 lanes of a group enter and leave the row loop together
+// (every condition that leaves it - the chain's end, a refusal - is the same in the whole group).  Groups of a wave walk chains of
+// different lengths, so nothing in the row loop waits for another group: the only barrier is the one after the constants are
+// staged, before the loop.  A refused row folds its job into flags[1] and the family bit into flags[0] (row_flag.hpp).
+constexpr u32 PLAN_CHAIN_THREADS = 256;
+__device__ __forceinline__ u64 group_read64(u32 byte_index, u64 v) {
+  const u32 lo = (u32)__builtin_amdgcn_ds_bpermute((int)byte_index, (int)(u32)v), hi = (u32)__builtin_amdgcn_ds_bpermute((int)byte_index, (int)(u32)(v >> 32));
+  return ((u64)hi << 32) | lo;
+}
+__global__ __launch_bounds__(PLAN_CHAIN_THREADS) void k_pos_plan_chains(const PosJobDev *__restrict__ jobs, u64 npos, const u32 *__restrict__ chain_ends,
+                                                                         u64 chain_begin, u64 chain_end, const RecOperandDev *__restrict__ operands,
+                                                                         u64 noperands, u64 *wires, u32 ncols, u64 n, const u64 *__restrict__ rc,
+                                                                         u64 *flags, u64 gate, u64 marker) {
+  __shared__ u64 rcs[POS_ROUNDS * POS_W];
+  for (u32 i = threadIdx.x; i < POS_ROUNDS * POS_W; i += PLAN_CHAIN_THREADS) rcs[i] = rc[i];
+  __syncthreads();
+  const u64 t = (u64)blockIdx.x * PLAN_CHAIN_THREADS + threadIdx.x, chain = chain_begin + (t >> 4);
+  const u32 j = (u32)t & 15, base = (__lane_id() - j) << 2;  // base: the byte index of the group's lane 0 for ds_bpermute
+  if (chain >= chain_end) return;      // whole groups
+  if ((flags[0] >> 8) < gate) return;  // a job of an earlier level was refused: this level writes nothing
+  u64 begin, end;
+  pos_plan_chain_range(chain_ends, chain, npos, begin, end);
+  const u32 k = j < 12 ? j + 1 : 0;  // the operand this lane fetches
+  u64 prev = 0;                      // output j of the row before
+  for (u64 r = begin; r < end; r++) {
+    const PosJobDev job = jobs[r];
+    u32 problem = pos_plan_job_problem(job, noperands, n);
+    RecOperandDev o = {0, 0, PLAN_IMM};
+    if (!problem) {
+      o = operands[(u64)job.first_operand + k];
+      problem = pos_plan_operand_problem(o, k, r == begin, ncols, n);
+    }
+    u64 v = o.v;
+    if (!problem && o.src == PLAN_CELL) v = wires[(u64)o.col * n + o.v];
+    const u64 carried = group_read64(base + ((o.col & 15) << 2), prev);  // every lane shuffles; a valid PREV column is below 12
+    if (o.src == PLAN_PREV) v = carried;
+    v = gl_canon(v);
+    if (!problem && k == 0) problem = pos_plan_swap_problem(v);
+    u32 verdict = problem ? ((problem == POS_PLAN_SWAP_NOT_BOOLEAN ? POS_PLAN_OPERANDS : k) << 8 | problem) : 0xFFFFu;
+#pragma unroll
+    for (u32 m = 1; m < 16; m <<= 1) verdict = min(verdict, (u32)__shfl_xor((int)verdict, (int)m, 16));
+    if (verdict != 0xFFFFu) {
+      if (j == 0) {
+        atomicMin((unsigned long long *)flags + 1, (unsigned long long)row_refusal(r, verdict & 0xFF));
+        atomicMin((unsigned long long *)flags, (unsigned long long)row_refusal(marker, ROW_OTHER_FAMILY));
+      }
+      break;
+    }
+    const bool swap = __builtin_amdgcn_ds_bpermute((int)(base + (12 << 2)), (int)(u32)v) != 0;
+    const u64 other = group_read64(base + ((j < 8 ? j ^ 4 : j) << 2), v);  // lanes 0..3 and 4..7 exchange their inputs
+    u64 *W = wires + job.row;
+    u64 s = 0;
+    if (j < 12) {
+      W[(u64)(POS_WIRE_INPUT + j) * n] = v;
+      s = v;
+      if (j < 8) {
+        const u64 delta = swap ? (j < 4 ? gl_sub(other, v) : gl_sub(v, other)) : 0;
+        s = j < 4 ? gl_add(v, delta) : gl_sub(v, delta);
+        if (j < 4) W[(u64)(POS_WIRE_DELTA + j) * n] = delta;
+      }
+    } else if (j == 12) {
+      W[(u64)POS_WIRE_SWAP * n] = v;
+    }
+    const u64 out = pos_permute_coop_hooked(s, j, rcs, [&](int round, u32 lo, u32 hi) {
+      const bool first_half = round >= 1 && round < POS_FULL_HALF, second_half = round >= POS_FULL_HALF + POS_PARTIAL;
+      const bool partial = round >= POS_FULL_HALF && round < POS_FULL_HALF + POS_PARTIAL;
+      if (j < 12 && (first_half || second_half || (partial && j == 0))) {
+        const u32 col = first_half ? POS_WIRE_FULL_0 + 12 * (round - 1) + j
+                      : partial   ? POS_WIRE_PARTIAL + (round - POS_FULL_HALF)
+                                  : POS_WIRE_FULL_1 + 12 * (round - POS_FULL_HALF - POS_PARTIAL) + j;
+        W[(u64)col * n] = gl_canon(((u64)hi << 32) | lo);
+      }
+    });
+    if (j < 12) W[(u64)(POS_WIRE_OUTPUT + j) * n] = out;
+    prev = out;
+  }
+}
+void launch_pos_plan_chains(hipStream_t s, const PosJobDev *jobs, u64 npos, const u32 *chain_ends, u64 chain_begin, u64 chain_end,
+                            const RecOperandDev *operands, u64 noperands, u64 *wires, u32 ncols, u64 n, const u64 *rc, u64 *flags, u64 gate,
+                            u64 marker) {
+  if (chain_begin >= chain_end) return;
+  const u64 threads = (chain_end - chain_begin) * 16;
+  hipLaunchKernelGGL(k_pos_plan_chains, dim3((unsigned)((threads + PLAN_CHAIN_THREADS - 1) / PLAN_CHAIN_THREADS)), dim3(PLAN_CHAIN_THREADS), 0, s,
+                     jobs, npos, chain_ends, chain_begin, chain_end, operands, noperands, wires, ncols, n, rc, flags, gate, marker);
 }
 
 void launch_sha_jobs_level(hipStream_t s, const ShaJobDev *jobs, u32 first, u32 count, const uint32_t *words_in, uint32_t *rec) {

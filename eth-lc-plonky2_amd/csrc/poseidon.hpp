@@ -523,7 +523,10 @@ __device__ __forceinline__ void pos_permute_gfx950(u64 s[12], const u64 *__restr
 // ~12 us instead of ~58 us.  Throughput per CU is ~3x lower than one permutation per lane (the partial rounds keep 11
 // of 12 lanes idle), so this form is used where the work is latency bound: Merkle levels and FRI layers with at most
 // POS_COOP_MAX_NODES nodes.  v: element j of the state (any u64); returns the canonical output element j.
-__device__ __forceinline__ u64 pos_permute_coop(u64 v, u32 j, const u64 *__restrict__ rc /* LDS copy of the round constants */) {
+// sbox_in(round, lo, hi): called on every lane before each S-box layer with the lazy halves of what enters the lane's S-box (in a
+// partial round only lane 0's goes through one): the PoseidonGate row generator of k_pos_plan_chains stores the wired ones.
+template <class SboxIn>
+__device__ __forceinline__ u64 pos_permute_coop_hooked(u64 v, u32 j, const u64 *__restrict__ rc /* LDS copy of the round constants */, SboxIn sbox_in) {
   const u32 C[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
   const u32 lane = __lane_id(), jj = j < 12 ? j : 0, base = lane - j;
   u32 src[12];
@@ -548,12 +551,14 @@ __device__ __forceinline__ u64 pos_permute_coop(u64 v, u32 j, const u64 *__restr
 #pragma unroll 1
   for (int r = 0; r < POS_FULL_HALF; r++, round++) {
     const u64 next = rc[(round + 1) * 12 + jj];
+    sbox_in(round, lo, hi);
     pos_sbox_h(lo, hi);
     mds(next);
   }
 #pragma unroll 1
   for (int r = 0; r < POS_PARTIAL; r++, round++) {
     const u64 next = rc[(round + 1) * 12 + jj];
+    sbox_in(round, lo, hi);
     u32 s0 = lo, s1 = hi;
     pos_sbox_h(s0, s1);
     if (j == 0) { lo = s0; hi = s1; }
@@ -562,13 +567,19 @@ __device__ __forceinline__ u64 pos_permute_coop(u64 v, u32 j, const u64 *__restr
 #pragma unroll 1
   for (int r = 0; r < POS_FULL_HALF; r++, round++) {
     const u64 next = round + 1 < POS_ROUNDS ? rc[(round + 1) * 12 + jj] : 0;
+    sbox_in(round, lo, hi);
     pos_sbox_h(lo, hi);
     mds(next);
   }
   return gl_canon(((u64)hi << 32) | lo);
 }
+__device__ __forceinline__ u64 pos_permute_coop(u64 v, u32 j, const u64 *__restrict__ rc) {
+  return pos_permute_coop_hooked(v, j, rc, [](int, u32, u32) {});
+}
 #elif defined(__HIPCC__)
 __device__ u64 pos_permute_coop(u64 v, u32 j, const u64 *__restrict__ rc);  // host pass of hipcc: declaration only
+template <class SboxIn>  // (a lambda has no linkage, so the host pass needs a body for what it never calls)
+__device__ __forceinline__ u64 pos_permute_coop_hooked(u64, u32, const u64 *__restrict__, SboxIn) { return 0; }
 #endif
 constexpr u32 POS_COOP_MAX_NODES = 4096;
 

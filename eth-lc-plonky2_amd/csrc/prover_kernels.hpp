@@ -170,6 +170,13 @@ struct RecJobDev;
 struct RecOperandDev;
 void launch_rec_gate_rows(hipStream_t s, const RecJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
                           u64 *wires, u32 ncols, u64 n, u64 *flag, bool check_structure);
+// lcp2_witness_plan_rows (kernels_witness.hip k_pos_plan_chains, pos_plan.hpp): the PoseidonGate chains [chain_begin, chain_end) of one
+// level, one 16-lane group each; jobs / chain_ends / operands: the WHOLE lists; rc: the context's round constants; flags: the two
+// words of row_flag.hpp, gate the key of this level and marker the index a refused chain folds into flags[0]
+struct PosJobDev;
+void launch_pos_plan_chains(hipStream_t s, const PosJobDev *jobs, u64 npos, const u32 *chain_ends, u64 chain_begin, u64 chain_end,
+                            const RecOperandDev *operands, u64 noperands, u64 *wires, u32 ncols, u64 n, const u64 *rc, u64 *flags, u64 gate,
+                            u64 marker);
 // *flag = 1 if a word of p[r * pitch + i] (r < rows, i < width) is a non-zero field element (flag zeroed by the caller)
 void launch_any_nonzero(hipStream_t s, const u64 *p, u64 pitch, u64 width, u32 rows, unsigned long long *flag);
 

@@ -1,4 +1,5 @@
-// The refusal flag of the row generators that validate a job list on the device (lcp2_u32_gate_rows, lcp2_rec_gate_rows).
+// The refusal flag of the row generators that validate a job list on the device (lcp2_u32_gate_rows, lcp2_rec_gate_rows,
+// lcp2_witness_plan_rows).
 //
 // One 64-bit word per call.  The entry point sets it to ROW_NO_PROBLEM before the first launch; a lane whose job is refused writes
 // no cell and folds row_refusal(index, problem) into the word with a minimum (the kernels: atomicMin; tests/emu: a compare), so
@@ -11,5 +12,21 @@ namespace lcp2 {
 
 constexpr u64 ROW_NO_PROBLEM = ~0ull;  // no job of the call has been refused
 LCP2_HD u64 row_refusal(u64 index, u64 problem) { return index << 8 | problem; }  // problem in [1, 255]
+
+
+// lcp2_witness_plan_rows runs TWO families level by level - rec jobs (k_rec_gate_rows, unchanged) and PoseidonGate chains
+// (k_pos_plan_chains) - and a refusal in either must stop every later level of both.  The choice: a family bit folded into ONE word,
+// and a second word that only names the PoseidonGate job.
+//   flags[0]  the word k_rec_gate_rows already folds its refusals into and tests before it runs.  Level l is launched with its job
+//             indices shifted by plan_shift(l) = l + 1, so the key of level l, plan_gate(begin_l, l) = begin_l + l + 1, grows
+//             strictly from level to level even where a level holds no rec job.  A refused rec job i of level l folds
+//             row_refusal(i + l + 1, problem); a refused chain of level l folds row_refusal(end_l + l + 1, ROW_OTHER_FAMILY): above
+//             every rec refusal of its own level - the minimum keeps the rec job, which is the one the error names when both
+//             families refuse in a level - not below the key of level l, so the other chains of the level still run, and below the
+//             key of level l + 1.  Both kernels return at once when (flags[0] >> 8) < the key of their level.
+//   flags[1]  the minimum of row_refusal(PoseidonGate job, problem) over the refused chains, read when flags[0] carries the bit.
+constexpr u64 ROW_OTHER_FAMILY = 0xFF;  // the problem byte of flags[0] when the refusal is the other family's: above every reason
+LCP2_HD u64 plan_shift(u64 level) { return level + 1; }
+LCP2_HD u64 plan_gate(u64 rec_begin, u64 level) { return rec_begin + plan_shift(level); }
 
 }  // namespace lcp2

@@ -1,6 +1,7 @@
 // Witness-row entry points of liblcp2.so (K10): lcp2_sha256_witness, lcp2_scatter_cells, lcp2_poseidon_gate_rows,
-// lcp2_u32_gate_rows and lcp2_rec_gate_rows, with the device scratch, the host-to-device staging and the refusal flag they share.
-// The kernels are in kernels_witness.hip; the per-row texts in sha_layout.hpp, pos_rows.hpp, u32_rows.hpp and rec_rows.hpp.
+// lcp2_u32_gate_rows, lcp2_rec_gate_rows and lcp2_witness_plan_rows, with the device scratch, the host-to-device staging and the
+// refusal flag they share.  The kernels are in kernels_witness.hip; the per-row texts in sha_layout.hpp, pos_rows.hpp, u32_rows.hpp,
+// rec_rows.hpp and pos_plan.hpp.
 #include <cstring>
 #include "internal.hpp"
 #include "sha_layout.hpp"
@@ -8,6 +9,7 @@
 #include "prover_kernels.hpp"
 #include "u32_rows.hpp"
 #include "rec_rows.hpp"
+#include "pos_plan.hpp"
 
 using namespace lcp2;
 
@@ -252,4 +254,91 @@ extern "C" int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_
     }
   }
   return flag.end("rec rows", rec_problem_str, "the valid jobs of its level and of the levels before are written, later levels are not");
+}
+
+// A recorded plan of BOTH families, level by level: the rec jobs of a level through k_rec_gate_rows (the kernel of
+// lcp2_rec_gate_rows, unchanged: its job indices are shifted per level, row_flag.hpp), then the level's PoseidonGate chains through
+// k_pos_plan_chains, all on the context's stream with no host wait in between.  Host lists are validated completely first (rec
+// jobs, then PoseidonGate jobs: structure, and the values that are IMM) and go up whole through the pinned staging buffer, in
+// pieces of its size: operands into scratch slot 2, rec jobs into slot 0, PoseidonGate jobs and chain_ends into slot 3.  The two flag
+// words are in slot 1 and come back once, after the last level.
+extern "C" int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *plan, lcp2_mem lists_mem, uint64_t *wires, uint32_t ncols, uint64_t n) {
+  static_assert(sizeof(lcp2_pos_job) == 8 && sizeof(lcp2_pos_job) == sizeof(PosJobDev), "record layouts must agree");
+  static_assert(LCP2_PLAN_IMM == PLAN_IMM && LCP2_PLAN_CELL == PLAN_CELL && LCP2_PLAN_PREV == PLAN_PREV && LCP2_PLAN_IMM == LCP2_REC_IMM &&
+                LCP2_PLAN_CELL == LCP2_REC_CELL, "numbering must agree");
+  if (!ctx || !plan || !wires) return LCP2_E_INVALID;
+  const lcp2_witness_plan &p = *plan;
+  if (lists_mem != LCP2_MEM_HOST && lists_mem != LCP2_MEM_DEVICE) return ctx->fail(LCP2_E_INVALID, "plan rows: bad lcp2_mem");
+  if ((p.nrec && (!p.rec_jobs || !p.rec_level_ends)) || (p.npos && !p.pos_jobs) || (p.nchains && (!p.chain_ends || !p.pos_level_ends)) ||
+      (p.noperands && !p.operands) || ((p.nrec || p.nchains) && !p.nlevels))
+    return ctx->fail(LCP2_E_INVALID, "plan rows: a list is null but its count is not zero");
+  if (!p.nrec && !p.npos) return LCP2_OK;
+  if (ncols < POS_GATE_WIRES) return ctx->fail(LCP2_E_INVALID, "plan rows: the matrix needs at least 135 columns");
+  if (p.nrec > 0xFFFFFFFFull || p.npos > 0xFFFFFFFFull || p.nchains > 0xFFFFFFFFull)
+    return ctx->fail(LCP2_E_INVALID, "plan rows: more than 2^32 - 1 jobs or chains");
+  const bool host = lists_mem == LCP2_MEM_HOST;
+  auto ends_problem = [&](const uint32_t *ends, size_t count, size_t total, const char *name) -> std::string {
+    if (!total) return "";
+    for (size_t l = 0; l < count; l++)
+      if (ends[l] < (l ? ends[l - 1] : 0) || ends[l] > total) return std::string("plan rows: ") + name + " is not ascending at entry " + std::to_string(l);
+    if (!count || ends[count - 1] != total) return std::string("plan rows: ") + name + " does not end at its count";
+    return "";
+  };
+  std::string bad = ends_problem(p.rec_level_ends, p.nlevels, p.nrec, "rec_level_ends");
+  if (bad.empty()) bad = ends_problem(p.pos_level_ends, p.nlevels, p.nchains, "pos_level_ends");
+  if (bad.empty() && host) {
+    bad = ends_problem(p.chain_ends, p.nchains, p.npos, "chain_ends");
+    if (bad.empty() && p.npos && !p.nchains) bad = "plan rows: chain_ends does not end at its count";
+  }
+  if (!bad.empty()) return ctx->fail(LCP2_E_INVALID, bad);
+  const RecJobDev *rec = (const RecJobDev *)p.rec_jobs;
+  const PosJobDev *pos = (const PosJobDev *)p.pos_jobs;
+  const RecOperandDev *ops = (const RecOperandDev *)p.operands;
+  if (host)
+    if (const PlanProblem bad_job = plan_lists_problem(rec, p.nrec, pos, p.chain_ends, p.nchains, ops, p.noperands, ncols, n); bad_job.problem)
+      return ctx->fail(LCP2_E_INVALID, std::string("plan rows: ") + (bad_job.family ? "poseidon job " : "rec job ") + std::to_string(bad_job.job) + ": " +
+                                           (bad_job.family ? pos_plan_problem_str(bad_job.problem) : rec_problem_str(bad_job.problem)));
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  u64 *flags;
+  LCP2_TRY(scratch_ensure(ctx, 1, 2 * sizeof(u64), (void **)&flags));
+  LCP2_HIP(ctx, hipMemsetAsync(flags, 0xFF, 2 * sizeof(u64), ctx->stream));  // ROW_NO_PROBLEM twice
+  const u32 *chain_ends = p.chain_ends;
+  if (host) {
+    void *d_rec, *d_ops, *d_pos;
+    const size_t pos_bytes = (p.npos * sizeof(lcp2_pos_job) + 15) & ~(size_t)15;
+    LCP2_TRY(scratch_ensure(ctx, 0, std::max<size_t>(p.nrec, 1) * sizeof(lcp2_rec_job), &d_rec));
+    LCP2_TRY(scratch_ensure(ctx, 2, std::max<size_t>(p.noperands, 1) * sizeof(lcp2_rec_operand), &d_ops));
+    LCP2_TRY(scratch_ensure(ctx, 3, pos_bytes + std::max<size_t>(p.nchains, 1) * sizeof(uint32_t), &d_pos));
+    Stage stage{ctx};
+    if (p.noperands) LCP2_TRY(stage.whole(d_ops, ops, p.noperands * sizeof(lcp2_rec_operand)));
+    if (p.nrec) LCP2_TRY(stage.whole(d_rec, rec, p.nrec * sizeof(lcp2_rec_job)));
+    if (p.npos) LCP2_TRY(stage.whole(d_pos, pos, p.npos * sizeof(lcp2_pos_job)));
+    if (p.nchains) LCP2_TRY(stage.whole((char *)d_pos + pos_bytes, p.chain_ends, p.nchains * sizeof(uint32_t)));
+    rec = (const RecJobDev *)d_rec;
+    ops = (const RecOperandDev *)d_ops;
+    pos = (const PosJobDev *)d_pos;
+    chain_ends = (const u32 *)((char *)d_pos + pos_bytes);
+  }
+  for (size_t l = 0; l < p.nlevels; l++) {
+    const u64 rec_begin = p.nrec && l ? p.rec_level_ends[l - 1] : 0, rec_end = p.nrec ? p.rec_level_ends[l] : 0, shift = plan_shift(l);
+    launch_rec_gate_rows(ctx->stream, rec, shift, rec_begin + shift, rec_end + shift, ops, p.noperands, (u64 *)wires, ncols, n, flags, !host);
+    if (p.nchains)
+      launch_pos_plan_chains(ctx->stream, pos, p.npos, chain_ends, l ? p.pos_level_ends[l - 1] : 0, p.pos_level_ends[l], ops, p.noperands,
+                             (u64 *)wires, ncols, n, ctx->d_rc, flags, plan_gate(rec_begin, l), rec_end + shift);
+  }
+  LCP2_HIP(ctx, hipGetLastError());
+  u64 words[2] = {0, 0};
+  LCP2_HIP(ctx, hipMemcpyAsync(words, flags, sizeof words, hipMemcpyDeviceToHost, ctx->stream));
+  LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's lists may go; every cell is written
+  if (words[0] == ROW_NO_PROBLEM) return LCP2_OK;
+  const char *written = " (found on the device: the valid rec jobs of its level, the rows of its chain before it, the other chains of its level and all "
+                        "earlier levels are written, later levels are not)";
+  if ((words[0] & 0xFF) != ROW_OTHER_FAMILY) {  // a rec job: its level is the one whose shifted range holds the index
+    const u64 shifted = words[0] >> 8;
+    u64 job = 0;
+    for (size_t l = 0; l < p.nlevels; l++)
+      if (shifted >= plan_gate(l ? p.rec_level_ends[l - 1] : 0, l) && shifted < p.rec_level_ends[l] + plan_shift(l)) job = shifted - plan_shift(l);
+    return ctx->fail(LCP2_E_INVALID, "plan rows: rec job " + std::to_string(job) + ": " + rec_problem_str((u32)(words[0] & 0xFF)) + written);
+  }
+  return ctx->fail(LCP2_E_INVALID, "plan rows: poseidon job " + std::to_string(words[1] >> 8) + ": " + pos_plan_problem_str((u32)(words[1] & 0xFF)) + written);
 }

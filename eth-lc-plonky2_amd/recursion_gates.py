@@ -688,3 +688,185 @@ def chain_circuit(params, plan, native=True):
     sig = sigma_values(np.tile(rows, (NR, 1)), np.tile(np.arange(NR)[:, None], (1, n)), k_is, params.degree_bits)
     cs = np.concatenate([gs.selector_columns(plan.gate_of_row), plan.c0[None, :], plan.c1[None, :], sig])
     return Circuit(params, gs, cs, k_is, 0), np.zeros(0, dtype=np.uint64)
+
+
+# ---------------------------------------------------------------- witness plans that hold PoseidonGate rows (lcp2_witness_plan_rows)
+from .binding import PLAN_PREV, POS_JOB_DTYPE  # noqa: E402
+
+PREV = lambda j: (0, int(j), PLAN_PREV)   # noqa: E731  output j of the previous job of the same chain
+POS_PLAN_OPERANDS = 13
+
+
+def pack_witness_plan(levels):
+    """levels: [(rec items, chains), ..]: rec items as in pack_plan, a chain a list of (row, swap operand, [12 input operands])
+    -> a namespace of the six lists of lcp2_witness_plan_rows: rec_jobs, pos_jobs, chain_ends, operands, rec_level_ends,
+    pos_level_ends.  The operands of a level follow those of the level before (rec jobs, sorted as pack_plan sorts them, then the
+    chains in order), so level 0's operands come first; `leaves` is their number."""
+    rec_items = [sorted(rec, key=lambda it: (it[1], it[2], it[0])) for rec, _ in levels]
+    rec_jobs = np.zeros(sum(len(rec) for rec in rec_items), dtype=REC_JOB_DTYPE)
+    pos_jobs = np.zeros(sum(len(chain) for _, chains in levels for chain in chains), dtype=POS_JOB_DTYPE)
+    count = sum(len(it[3]) for rec in rec_items for it in rec) + POS_PLAN_OPERANDS * pos_jobs.size
+    ops = np.zeros(count, dtype=REC_OPERAND_DTYPE)
+    at = kr = kp = 0
+    chain_ends, rec_ends, pos_ends, leaves = [], [], [], None
+    for rec, (_, chains) in zip(rec_items, levels):
+        for row, kind, op, operands in rec:
+            assert len(operands) == REC_JOB_KINDS[kind][2](op), (kind, op, len(operands))
+            rec_jobs[kr] = (row, kind, op, at, 0)
+            for v, col, src in operands:
+                ops[at] = (v % (1 << 64), col, src)
+                at += 1
+            kr += 1
+        for chain in chains:
+            for row, swap, inputs in chain:
+                assert len(inputs) == 12
+                pos_jobs[kp] = (row, at)
+                for v, col, src in [swap] + list(inputs):
+                    ops[at] = (v % (1 << 64), col, src)
+                    at += 1
+                kp += 1
+            chain_ends.append(kp)
+        rec_ends.append(kr)
+        pos_ends.append(len(chain_ends))
+        leaves = at if leaves is None else leaves
+    u32 = lambda a: np.array(a, dtype=np.uint32)   # noqa: E731
+    return SimpleNamespace(rec_jobs=rec_jobs, pos_jobs=pos_jobs, chain_ends=u32(chain_ends), operands=ops, rec_level_ends=u32(rec_ends),
+                           pos_level_ends=u32(pos_ends), leaves=leaves or 0)
+
+
+def run_witness_plan(plan, ncols, n, start=None, levels=None):
+    """lcp2_witness_plan_rows in Python integers: the matrix [ncols][n] after the plan (its first `levels` levels) ran on `start`
+    (zeros by default).  The rec jobs of a level through run_plan, then its chains row by row through poseidon_py.gate_row"""
+    from . import poseidon_py as pp
+    out = np.zeros((ncols, n), dtype=np.uint64) if start is None else start.copy()
+    nlevels = len(plan.rec_level_ends) if levels is None else levels
+    for lv in range(nlevels):
+        rb, re = (int(plan.rec_level_ends[lv - 1]) if lv else 0), int(plan.rec_level_ends[lv])
+        out = run_plan(plan.rec_jobs[rb:re], plan.operands, [re - rb], ncols, n, start=out)
+        for g in range(int(plan.pos_level_ends[lv - 1]) if lv else 0, int(plan.pos_level_ends[lv])):
+            prev = None
+            for j in plan.pos_jobs[(int(plan.chain_ends[g - 1]) if g else 0):int(plan.chain_ends[g])]:
+                vals = []
+                for o in plan.operands[int(j["first_operand"]):int(j["first_operand"]) + POS_PLAN_OPERANDS]:
+                    src = int(o["src"])
+                    vals.append(int(out[int(o["col"]), int(o["v"])]) % P if src == REC_CELL else prev[int(o["col"])] if src == PLAN_PREV
+                                else int(o["v"]) % P)
+                assert vals[0] in (0, 1)
+                row = pp.gate_row(vals[1:], vals[0])
+                out[:pp.NUM_WIRES, int(j["row"])] = np.array(row, dtype=np.uint64)
+                prev = row[pp.W_OUTPUT:pp.W_OUTPUT + 12]
+    return out
+
+
+def verifier_gateset(native=True):
+    """chain_gateset with PoseidonGate added, sorted by (degree, name)"""
+    from . import u32_gates as ug
+    from .circuit import gate_poseidon
+    return GateSet([
+        ("NoopGate", 0, gate_noop),
+        ("PoseidonMdsGate", 1, gate_poseidon_mds),
+        ("BaseSumGate", 2, gate_base_sum(BASE_SUM_LIMBS)),
+        ("ReducingExtensionGate", 2, gate_reducing_extension),
+        ("ReducingGate", 2, gate_reducing),
+        ("ArithmeticExtensionGate", 3, gate_arithmetic_extension),
+        ("ArithmeticGate", 3, gate_arithmetic),
+        ("MulExtensionGate", 3, gate_mul_extension),
+        ("ExponentiationGate", 4, gate_exponentiation),
+        ("RandomAccessGate", 5, gate_random_access),
+        ("PoseidonGate", 7, gate_poseidon),
+        ("CosetInterpolationGate", 8, ug.gate_coset_interpolation),
+    ], native=native)
+
+
+MERKLE_DEPTHS = [2, 3, 5, 1, 4]
+
+
+def verifier_plan(n, seed, paths=None, sponge=None, expected=True):
+    """A deterministic plan over n rows shaped like the Poseidon work of verify_proof, in five levels:
+      0  rec     per path one BASE_SUM row (the query index, below 2^63) and ARITHMETIC leaves (op k: 1 * a * b + 1 * c): the only
+                 per-proof immediates (drawn from `seed`); level 0's operands come first in the operand list
+      1  chains  one Merkle path per BASE_SUM row, depths MERKLE_DEPTHS in turn: row k takes the digest so far - the head four
+                 ARITHMETIC outputs as CELLs, later rows PREV 0..3 -, an immediate sibling and zeros, and its swap flag is the
+                 CELL of limb k of the path's index
+      2  chains  ONE sponge: 8 new inputs per row, IMM and CELL in turn (CELLs of ARITHMETIC leaves and of Merkle roots), the capacity
+                 PREV 8..11
+      3  rec     an ARITHMETIC and an ARITHMETIC_EXT row over CELLs of the sponge's and the paths' outputs
+      4  chains  a second generation: each head reads eight of those cells, every later row takes PREV 0..11 (a Challenger that
+                 keeps permuting)
+    paths / sponge: the number of Merkle paths and the sponge's rows (defaults: n // 24, at least 3; what is left of 7/8 of the rows).
+    The immediates of the later levels depend on n only, so two seeds give the same lists but for the first `leaves` operands.
+    Returns pack_witness_plan's namespace plus expected (the matrix [135][n] from a zero matrix; None with expected=False),
+    gate_of_row (indices into verifier_gateset()), c0, c1."""
+    rng, fixed = np.random.default_rng(seed), np.random.default_rng(0x9E1F + n)
+    npaths = max(3, n // 24) if paths is None else paths
+    depths = [MERKLE_DEPTHS[i % len(MERKLE_DEPTHS)] for i in range(npaths)]
+    second = [2 + (i & 1) for i in range(max(2, npaths // 2))]
+    leaf_rows = (4 * npaths + 8 + ARITH_OPS - 1) // ARITH_OPS   # four digest elements per path and eight cells for the sponge
+    used = npaths + leaf_rows + sum(depths) + 2 + sum(second)
+    nsponge = n - n // 8 - used if sponge is None else sponge
+    assert nsponge >= 2 and used + nsponge <= n, "the plan does not fit the rows"
+    gs = verifier_gateset()
+    G = {name: gs.index(name) for name in ("BaseSumGate", "ArithmeticGate", "ArithmeticExtensionGate", "PoseidonGate")}
+    gate_of_row = np.full(n, gs.index("NoopGate"), dtype=np.int64)
+    c0, c1 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    rows = iter(range(n))
+
+    def take(count, gate, consts=(0, 0)):
+        out = [next(rows) for _ in range(count)]
+        gate_of_row[out] = G[gate]
+        c0[out], c1[out] = consts
+        return out
+
+    def f(r):
+        return int(r.integers(0, P, dtype=np.uint64))
+
+    ZERO, ONE = IMM(0), IMM(1)
+    index_rows, arith_rows = take(npaths, "BaseSumGate"), take(leaf_rows, "ArithmeticGate", (1, 1))
+    leaf = [(arith_rows[k // ARITH_OPS], k % ARITH_OPS) for k in range(4 * npaths + 8)]   # (row, op) of every leaf value
+    leaf_cell = lambda k: CELL(leaf[k][0], 4 * leaf[k][1] + 3)   # noqa: E731
+    level0 = [(r, REC_BASE_SUM, 0, [IMM(rng.integers(0, 1 << 63, dtype=np.uint64))]) for r in index_rows]
+    level0 += [(r, REC_ARITHMETIC, op, [ONE, ONE, IMM(f(rng)), IMM(f(rng)), IMM(f(rng))]) for r, op in leaf]
+    merkle, roots = [], []
+    for p, depth in enumerate(depths):
+        chain = []
+        for k, r in enumerate(take(depth, "PoseidonGate")):
+            digest = [leaf_cell(4 * p + i) for i in range(4)] if k == 0 else [PREV(i) for i in range(4)]
+            chain.append((r, CELL(index_rows[p], 1 + k), digest + [IMM(f(fixed)) for _ in range(4)] + [ZERO] * 4))
+        merkle.append(chain)
+        roots.append(chain[-1][0])
+    sponge_rows = take(nsponge, "PoseidonGate")
+    cells = [leaf_cell(4 * npaths + i) for i in range(8)] + [CELL(r, 12 + i) for r in roots for i in range(4)]
+    sponge_chain = []
+    for k, r in enumerate(sponge_rows):
+        fresh = [cells[(8 * k + i) % len(cells)] if (k + i) & 1 else IMM(f(fixed)) for i in range(8)]
+        sponge_chain.append((r, ZERO, fresh + ([ZERO] * 4 if k == 0 else [PREV(8 + i) for i in range(4)])))
+    (arow,), (xrow,) = take(1, "ArithmeticGate", (f(fixed), f(fixed))), take(1, "ArithmeticExtensionGate", (f(fixed), f(fixed)))
+    last = sponge_rows[-1]
+    out_cell = lambda k: CELL(roots[(k // 4) % npaths], 12 + k % 4) if k % 3 else CELL(last, 12 + k % 12)   # noqa: E731
+    level3 = [(arow, REC_ARITHMETIC, op, [IMM(c0[arow]), IMM(c1[arow]), out_cell(3 * op), out_cell(3 * op + 1), out_cell(3 * op + 2)])
+              for op in range(ARITH_OPS)]
+    level3 += [(xrow, REC_ARITHMETIC_EXT, op, [IMM(c0[xrow]), IMM(c1[xrow])] + [out_cell(6 * op + i) for i in range(6)]) for op in range(ARITH_EXT_OPS)]
+    later = []
+    for g, length in enumerate(second):
+        chain = []
+        for k, r in enumerate(take(length, "PoseidonGate")):
+            head = [CELL(arow, 4 * ((8 * g + i) % ARITH_OPS) + 3) if i & 1 else CELL(xrow, 8 * ((g + i) % ARITH_EXT_OPS) + 6 + (i >> 1 & 1)) for i in range(8)]
+            chain.append((r, IMM(g & 1) if k == 0 else ZERO, head + [ZERO] * 4 if k == 0 else [PREV(i) for i in range(12)]))
+        later.append(chain)
+    plan = pack_witness_plan([(level0, []), ([], merkle), ([], [sponge_chain]), (level3, []), ([], later)])
+    plan.expected = run_witness_plan(plan, REC_ROW_COLUMNS, n) if expected else None
+    plan.gate_of_row, plan.c0, plan.c1 = gate_of_row, c0, c1
+    return plan
+
+
+def verifier_plan_circuit(params, plan, native=True):
+    """the circuit a verifier_plan fills, like chain_circuit: its rows' gates and constants over verifier_gateset(), no copy
+    constraints, no public inputs"""
+    gs = verifier_gateset(native)
+    n, NR = 1 << params.degree_bits, params.num_routed_wires
+    assert n == plan.gate_of_row.size and params.num_constants == gs.num_selectors + 2 and params.num_wires >= REC_ROW_COLUMNS and NR >= 80
+    rows = np.arange(n)
+    k_is = gl.powers(7, NR)
+    sig = sigma_values(np.tile(rows, (NR, 1)), np.tile(np.arange(NR)[:, None], (1, n)), k_is, params.degree_bits)
+    cs = np.concatenate([gs.selector_columns(plan.gate_of_row), plan.c0[None, :], plan.c1[None, :], sig])
+    return Circuit(params, gs, cs, k_is, 0), np.zeros(0, dtype=np.uint64)

@@ -301,6 +301,50 @@ int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_t njobs,
                        lcp2_mem lists_mem /* where jobs AND operands live */,
                        uint64_t *wires /* device, column-major [ncols][n] */, uint32_t ncols, uint64_t n);
 
+/* A witness plan that also holds PoseidonGate rows: rec jobs AND PoseidonGate CHAINS, level by level, without the host in between.
+ * PoseidonGate is the one gate of builder.verify_proof that lcp2_rec_gate_rows cannot run, and it is where a verifier circuit's
+ * chains are: the Challenger, every Merkle path (hash output into the next hash, swap bit from a BaseSumGate limb), the sponge over
+ * the inner proof's public inputs.  With this call the whole plan can stay in HBM; per proof only the IMM values of the leaves
+ * change.  The rec jobs, their operands and their kernel are those of lcp2_rec_gate_rows (see there).
+ * A PoseidonGate job fills all 135 cells of its row exactly as lcp2_poseidon_gate_rows does.  It takes 13 operands of the ONE
+ * operand list from operands[first_operand] on: the swap flag, then in[0..11].  An operand is LCP2_PLAN_IMM (any u64,
+ * canonicalised), LCP2_PLAN_CELL (row v, column col, canonicalised on load) or LCP2_PLAN_PREV: col = j < 12 names OUTPUT j of the
+ * PREVIOUS JOB OF THE SAME CHAIN, which the kernel carries in registers and never re-reads from the matrix.  The swap operand is
+ * IMM or CELL and its canonical value must be 0 or 1.
+ * Chains: chain g is the jobs pos_jobs[chain_ends[g-1] .. chain_ends[g]) and is walked in order inside ONE launch by one 16-lane
+ * group; empty chains are legal.  chain_ends lives with the lists (lists_mem).  A chain_ends in HBM is not validated as a list:
+ * an entry above npos is clipped and a descending one gives an empty chain.
+ * Levels: level l holds the rec jobs [rec_level_ends[l-1], rec_level_ends[l]) and the CHAINS [pos_level_ends[l-1],
+ * pos_level_ends[l]) - both tables count from the start of their list, are always host memory and have nlevels entries; a level
+ * may be empty in one family or in both.  A job of level l may read any cell the matrix held before the call or that a level
+ * BEFORE l writes, of either family.  Reading what another job of the same level writes - of the other family too - is the
+ * caller's error and is not detected.  All launches go to the context's stream in order (a level's rec jobs, then its chains);
+ * the host does not wait between levels.
+ * LCP2_MEM_HOST: the lists are validated completely - rec jobs first, then PoseidonGate jobs; structure, and the values that are
+ * IMM - before anything is written, and go up through the pinned staging buffer.  LCP2_MEM_DEVICE: the kernels validate, and no
+ * index is used before it is checked.  Values only the device sees (a CELL swap that is not 0 or 1, the four CELL value cases of
+ * the rec kinds) are found in the kernels either way.  After a refusal in level l the valid rec jobs of level l are written, of a
+ * refused chain the rows BEFORE the refused row, the other chains of level l in full, and nothing of any later level in either
+ * family.  The call returns LCP2_E_INVALID and lcp2_last_error says "plan rows: rec job N: <reason>" or "plan rows: poseidon
+ * job N: <reason>"; if both families refuse in the same level the rec job is named.
+ * Refused PoseidonGate jobs: row >= n, first_operand + 13 > noperands, an operand src above 2, PREV in the first job of a chain,
+ * PREV as the swap operand, a PREV col >= 12, a CELL with col >= ncols or v >= n, a swap value that is not 0 or 1.  PREV in a rec
+ * job is "operand src above 1".  Also LCP2_E_INVALID: a null ctx, plan or wires (checked before anything else), a lists_mem above
+ * 1, a null list with a non-zero count, ncols < 135, rec_level_ends / pos_level_ends (and, for host lists, chain_ends) not
+ * ascending or not ending at nrec / nchains / npos.  nrec = npos = 0 is LCP2_OK.  The context's stream is synchronised on return. */
+enum { LCP2_PLAN_IMM = 0, LCP2_PLAN_CELL = 1, LCP2_PLAN_PREV = 2 };   /* src of a PoseidonGate operand; IMM / CELL as LCP2_REC_* */
+typedef struct { uint32_t row, first_operand; } lcp2_pos_job;          /* 8 bytes; 13 operands: swap, then in[0..11] */
+typedef struct {
+  const lcp2_rec_job *rec_jobs;  size_t nrec;    const uint32_t *rec_level_ends;  /* host, [nlevels], as in lcp2_rec_gate_rows */
+  const lcp2_pos_job *pos_jobs;  size_t npos;
+  const uint32_t *chain_ends;    size_t nchains; /* with the lists; ascending, last == npos: chain g = pos_jobs[chain_ends[g-1] .. chain_ends[g]) */
+  const uint32_t *pos_level_ends;                /* host, [nlevels], counts CHAINS, ascending, last == nchains */
+  const lcp2_rec_operand *operands; size_t noperands;   /* one list for both families */
+  size_t nlevels;
+} lcp2_witness_plan;
+int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *plan, lcp2_mem lists_mem,
+                           uint64_t *wires /* device, column-major [ncols >= 135][n] */, uint32_t ncols, uint64_t n);
+
 /* device buffers for callers that keep the witness resident in HBM */
 int lcp2_buffer_alloc(lcp2_ctx *ctx, size_t bytes, void **dev);
 int lcp2_buffer_free(lcp2_ctx *ctx, void *dev);
