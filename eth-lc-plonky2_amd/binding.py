@@ -209,6 +209,7 @@ def load_library():
         "lcp2_quotient_buffer": (c.c_int, [c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_size_t)]),
         "lcp2_quotient_commit": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_verify": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_int)]),
+        "lcp2_verify_batch": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_size_t, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p]),
         "lcp2_last_challenges": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_gate_program_degree": (c.c_int, [c.c_void_p, c.c_size_t, c.c_uint32, c.POINTER(c.c_uint32)]),
         "lcp2_circuit_gate_tiers": (c.c_int, [c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p]),
@@ -504,6 +505,33 @@ class Context:
         plan = WitnessPlan(ptrs[0], counts[0], rends.ctypes.data if rends.size else None, ptrs[1], counts[1], ptrs[2], counts[2],
                            pends.ctypes.data if pends.size else None, ptrs[3], counts[3], rends.size)
         self._check(self.lib.lcp2_witness_plan_rows(self.handle, ctypes.byref(plan), mem, ctypes.c_void_p(wires_dev), int(ncols), int(n)))
+
+    def verify_batch(self, circuit_data, proofs, public_inputs, mem=MEM_HOST, count=None):
+        """lcp2_verify_batch: data.verify for a batch of proofs of one circuit (any CircuitData, verifier-only ones included), Merkle
+        paths and FRI queries on this context's device.  proofs: a (count, proof_words) array, or with mem=MEM_DEVICE a device pointer
+        and `count`; public_inputs: (count, num_public_inputs), host.  Returns the int32 array of failed checks (0 = accepted, 1..7 as
+        ProofRejected.check); does not raise on rejection."""
+        words = circuit_data.proof_words
+        if mem == MEM_HOST:
+            pr = _np_u64(proofs)
+            if pr.size % words:
+                raise Lcp2Error(-1, "proofs is not a whole number of this circuit's proofs")
+            count, ptr = pr.size // words, _ptr(pr)
+        else:
+            if count is None:
+                raise Lcp2Error(-1, "device proofs need count")
+            ptr = ctypes.c_void_p(proofs)
+        if count == 0:
+            return np.zeros(0, dtype=np.int32)
+        pis = _np_u64(public_inputs).ravel()
+        npi = pis.size // count
+        if npi * count != pis.size:
+            raise Lcp2Error(-1, "public_inputs is not count rows")
+        checks = np.zeros(count, dtype=np.int32)
+        rc = self.lib.lcp2_verify_batch(self.handle, circuit_data.handle, ptr, words, count, mem, _ptr(pis), npi, _ptr(checks))
+        if rc != -7:
+            self._check(rc)
+        return checks
 
     def buffer_alloc(self, words):
         p = ctypes.c_void_p()

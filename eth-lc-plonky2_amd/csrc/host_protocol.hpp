@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/lcp2.h"
 #include "poseidon.hpp"
+#include "verify_query.hpp"
 
 namespace lcp2 {
 
@@ -36,16 +37,9 @@ class HostPoseidon {
     permute(s);
     memcpy(out, s, 32);
   }
-  // verify_merkle_proof_to_cap
+  // verify_merkle_proof_to_cap (verify_query.hpp: the text the batch verifier's kernels are held to)
   bool merkle_verify(const u64 *leaf, size_t leaf_len, u64 index, const u64 *siblings, u32 nsib, const u64 *cap) const {
-    u64 cur[4], nxt[4];
-    hash_or_noop(leaf, leaf_len, cur);
-    for (u32 k = 0; k < nsib; k++) {
-      if (index & 1) two_to_one(siblings + 4 * k, cur, nxt); else two_to_one(cur, siblings + 4 * k, nxt);
-      memcpy(cur, nxt, 32);
-      index >>= 1;
-    }
-    return memcmp(cur, cap + 4 * index, 32) == 0;
+    return vq_merkle_path(leaf, (u32)leaf_len, index, siblings, nsib, cap, rc_);
   }
 
  private:

@@ -92,6 +92,9 @@ struct ProfScope {
   ~ProfScope();
 };
 
+// scratch slot `slot` of the context with at least `bytes` bytes (contents undefined); the stream orders its reuse (witness_rows.hip)
+int scratch_ensure(lcp2_ctx *ctx, int slot, size_t bytes, void **out);
+
 // ---- kernel launch wrappers (device pointers, asynchronous on `s`) ----
 void launch_poseidon_permute_batch(hipStream_t s, const u64 *in, u64 *out, size_t count, const u64 *rc);
 void launch_field_op(hipStream_t s, const u64 *a, const u64 *b, u64 *out, size_t count, u32 op);

@@ -13,7 +13,7 @@
 
 using namespace lcp2;
 
-namespace {
+namespace lcp2 {
 // scratch slot `slot` of the context with at least `bytes` bytes (contents undefined); the stream orders its reuse
 int scratch_ensure(lcp2_ctx *ctx, int slot, size_t bytes, void **out) {
   if (ctx->scratch_bytes[slot] < bytes) {
@@ -25,7 +25,9 @@ int scratch_ensure(lcp2_ctx *ctx, int slot, size_t bytes, void **out) {
   *out = ctx->scratch[slot];
   return LCP2_OK;
 }
+}  // namespace lcp2
 
+namespace {
 // Host -> device staging of one call through the context's pinned buffer (a copy out of pinned memory is a plain DMA that the
 // stream orders).  The buffer is free when a call begins: every entry point here waits for its transfers before it returns.
 struct Stage {

@@ -934,6 +934,14 @@ void CircuitData::verify(const ProofWithPublicInputs &proof) const {
   if (rc != LCP2_OK) throw std::runtime_error(std::string("lcp2_verify: ") + lcp2_status_str(rc));
 }
 
+bool CircuitData::verify_batch(const uint64_t *proofs, size_t count, const uint64_t *public_inputs, int32_t *failed_checks) const {
+  if (!impl_->gpu || !impl_->ctx) throw std::runtime_error("CircuitData::verify_batch needs a device: attach_gpu() first");
+  const int rc = lcp2_verify_batch(impl_->ctx, impl_->gpu, proofs, lcp2_proof_words(&desc_.params), count, LCP2_MEM_HOST, public_inputs,
+                                   desc_.num_public_inputs, failed_checks);
+  if (rc != LCP2_OK && rc != LCP2_E_VERIFY) throw std::runtime_error(std::string("lcp2_verify_batch: ") + lcp2_status_str(rc) + " (" + lcp2_last_error(impl_->ctx) + ")");
+  return rc == LCP2_OK;
+}
+
 }  // namespace lc
 
 // diagnostics for tools (how a circuit's witness generation is made up)

@@ -198,6 +198,14 @@ extern "C" int lch_prove(lch_session *s, uint64_t *proof, size_t proof_words, ui
   }
 }
 
+extern "C" int lch_verify_batch(const lch_session *s, const uint64_t *proofs, size_t count, const uint64_t *public_inputs, int32_t *failed_checks) {
+  if (!s || !failed_checks || (count && (!proofs || (!public_inputs && s->info.num_public_inputs)))) return fail(LCP2_E_INVALID, "null argument");
+  try {
+    return s->data->verify_batch(proofs, count, public_inputs, failed_checks) ? LCP2_OK : fail(LCP2_E_VERIFY, "at least one proof rejected");
+  } catch (const std::exception &e) {
+    return fail(LCP2_E_INVALID, e.what());
+  }
+}
 extern "C" int lch_verify(const lch_session *s, const uint64_t *proof, size_t proof_words, const uint64_t *public_inputs, size_t num_public_inputs) {
   if (!s || !proof || (!public_inputs && num_public_inputs)) return fail(LCP2_E_INVALID, "null argument");
   if (proof_words != s->info.proof_words || num_public_inputs != s->info.num_public_inputs) return fail(LCP2_E_INVALID, "buffer lengths do not match lch_get_info");

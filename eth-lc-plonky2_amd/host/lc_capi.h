@@ -44,6 +44,10 @@ int lch_get_info(const lch_session *s, lch_info *out);
 int lch_prove(lch_session *s, uint64_t *proof, size_t proof_words, uint64_t *public_inputs, size_t num_public_inputs);
 /* data.verify(proof): LCP2_OK or LCP2_E_VERIFY */
 int lch_verify(const lch_session *s, const uint64_t *proof, size_t proof_words, const uint64_t *public_inputs, size_t num_public_inputs);
+/* data.verify for `count` proofs at once, Merkle paths and FRI queries on the session's context (lcp2_verify_batch); step and wrap
+ * sessions alike.  proofs: count * info.proof_words, public_inputs: count * info.num_public_inputs, failed_checks: count (0 =
+ * accepted, 1..7 the check lcp2_verify names).  LCP2_OK if every proof is accepted, LCP2_E_VERIFY if one is not. */
+int lch_verify_batch(const lch_session *s, const uint64_t *proofs, size_t count, const uint64_t *public_inputs, int32_t *failed_checks);
 /* Shrinking a proof by recursion (plonky2's test_size_optimized_recursion): lch_wrap_create builds a circuit under the standard wire
  * shape with the given FRI config (quotient_degree_factor 8, ConstantArityBits(4, 5)) that verifies one proof of `inner` - its verifier
  * data built in as constants - and registers the inner public inputs as its own; `inner` may itself be a wrap session and must outlive

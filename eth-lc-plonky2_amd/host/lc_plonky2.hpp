@@ -169,6 +169,9 @@ class CircuitData {
   void generate_witness_gpu(const PartialWitness &pw, std::vector<F> &public_inputs);
   void read_device_witness(std::vector<uint64_t> &wires) const;   // test helper: copy of the device witness matrix
   void verify(const ProofWithPublicInputs &proof) const;          // data.verify(proof): host only
+  // data.verify for `count` proofs at once on the attached context (lcp2_verify_batch): proofs = count * proof words, public_inputs
+  // = count * the circuit's public inputs, failed_checks[i] = 0 or the check proof i fails.  Returns whether every proof is accepted
+  bool verify_batch(const uint64_t *proofs, size_t count, const uint64_t *public_inputs, int32_t *failed_checks) const;
   struct Impl;
   const Impl *impl_for_tools() const { return impl_.get(); }  // diagnostics (op_stats)
 

@@ -44,6 +44,8 @@ def load_host_library():
     lib.lch_prove.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]
     lib.lch_verify.restype = c.c_int
     lib.lch_verify.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]
+    lib.lch_verify_batch.restype = c.c_int
+    lib.lch_verify_batch.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
     lib.lch_expected_public_inputs.restype = c.c_int
     lib.lch_expected_public_inputs.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t]
     lib.lch_wrap_create.restype = c.c_int
@@ -98,6 +100,19 @@ class LightClientStep:
             raise _b.ProofRejected(self.lib.lch_last_error().decode())
         if rc:
             raise _b.Lcp2Error(rc, self.lib.lch_last_error().decode())
+
+    def verify_batch(self, proofs, pis):
+        """lch_verify_batch: the failed check of each proof of a (count, proof_words) array (0 = accepted); does not raise on rejection"""
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, self.info.proof_words)
+        pis = np.ascontiguousarray(pis, dtype=np.uint64).reshape(proofs.shape[0], -1)
+        if pis.shape[1] != self.info.num_public_inputs:
+            raise _b.Lcp2Error(-1, "public inputs do not match lch_get_info")
+        checks = np.zeros(proofs.shape[0], dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        rc = self.lib.lch_verify_batch(self.handle, vp(proofs), proofs.shape[0], vp(pis), vp(checks))
+        if rc not in (0, -7):
+            raise _b.Lcp2Error(rc, self.lib.lch_last_error().decode())
+        return checks
 
     def close(self):
         if self.handle:

@@ -626,6 +626,18 @@ int lcp2_quotient_commit(lcp2_circuit *c, uint64_t *cap);
 int lcp2_verify(const lcp2_circuit *c, const uint64_t *proof, size_t proof_words, const uint64_t *public_inputs,
                 size_t num_public_inputs, int *failed_check);
 
+/* data.verify(proof) for `count` proofs of one circuit, Merkle paths and FRI queries on the device of `ctx`.
+ * c: any handle (prover, sharded or verifier-only; a verifier-only handle has no context, which is why ctx is a parameter).
+ * proofs: count * proof_words words, proof i at proofs + i * proof_words, in host or device memory (proofs_mem).
+ * public_inputs: host, count * num_public_inputs.  failed_checks: host, count; 0 = accepted, 1..7 as lcp2_verify names them.
+ * Returns LCP2_OK if every proof is accepted, LCP2_E_VERIFY if at least one is not (failed_checks is complete either way),
+ * LCP2_E_INVALID for a length that is not the circuit's (nothing is read then), LCP2_OK for count == 0.
+ * The verdict of proof i is exactly what lcp2_verify reports for it.  Check 1 runs on the device over every word; checks 2 and 3
+ * run on the host from the words outside the query section (of device proofs only those are downloaded); checks 4 to 7 run on the
+ * device for every query of every proof at once.  The call returns when the verdicts are written. */
+int lcp2_verify_batch(lcp2_ctx *ctx, const lcp2_circuit *c, const uint64_t *proofs, size_t proof_words, size_t count, lcp2_mem proofs_mem,
+                      const uint64_t *public_inputs, size_t num_public_inputs, int32_t *failed_checks);
+
 /* ---- byte serialisation of a proof: plonky2 0.1.4 util/serialization.rs `write_proof_with_public_inputs`
  * ([RECALL] of the published format; the reference holds no serialised proof - src/main.rs:230-233 moves the object - so
  * this layout is PARITY UNPINNED).  Little-endian throughout: a field element is its canonical u64, an extension element two
