@@ -65,6 +65,10 @@ U32_JOB_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u2"), ("op", "<u2"), ("in",
 assert U32_JOB_DTYPE.itemsize == ctypes.sizeof(U32Job) == 24
 POSEIDON_ROW_DTYPE = np.dtype([("row", "<u4"), ("swap", "<u4"), ("in", "<u8", (12,))])   # lcp2_poseidon_row as a numpy record
 assert POSEIDON_ROW_DTYPE.itemsize == 104
+SHA_JOB_DTYPE = np.dtype([("first_row", "<u4"), ("in_src", "<i4", (16,))])   # lcp2_sha_job as a numpy record
+CELL_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("value", "<u8")])      # lcp2_cell as a numpy record
+assert SHA_JOB_DTYPE.itemsize == 68 and CELL_DTYPE.itemsize == 16
+SHA_ROWS, SHA_ROW_COLUMNS = 310, 108   # rows of one two_to_one_sha256, columns lcp2_sha256_witness writes in each
 
 class RecOperand(ctypes.Structure):
     """lcp2_rec_operand: an immediate value, or a cell (row v, column col) of the witness matrix (lcp2_rec_gate_rows)"""
@@ -430,6 +434,32 @@ class Context:
     # ---- device buffers
     def buffer_zero(self, dev_ptr, words):
         self._check(self.lib.lcp2_buffer_zero(self.handle, ctypes.c_void_p(dev_ptr), int(words) * 8))
+
+    def sha256_witness(self, jobs, level_start, words_in, wires_dev, n, digests=True):
+        """lcp2_sha256_witness: fills columns 0..107 of the 310 rows of every two_to_one_sha256 of `jobs` (a numpy array of
+        SHA_JOB_DTYPE records: first row, 16 sources; validated before anything runs) in the device witness matrix `wires_dev` (a
+        pointer, [>= 108][n] column-major; n need not be a power of two).  level_start: nlevels + 1 job indices, jobs of a level
+        read words_in (source s >= 0) or digest word (~s) & 7 of job (~s) >> 3 of any earlier level; a level may be empty.
+        Returns the digests [njobs][8] (u32), or None with digests=False (the library then copies nothing back)."""
+        if not isinstance(jobs, np.ndarray) or jobs.dtype != SHA_JOB_DTYPE:
+            raise Lcp2Error(-1, "jobs must be an array of SHA_JOB_DTYPE records")
+        j = np.ascontiguousarray(jobs).ravel()
+        levels = np.ascontiguousarray(level_start, dtype=np.uint32).ravel()
+        words = np.ascontiguousarray(words_in, dtype=np.uint32).ravel()
+        out = np.zeros((j.size, 8), dtype=np.uint32) if digests else None
+        self._check(self.lib.lcp2_sha256_witness(self.handle, _ptr(j) if j.size else None, j.size, _ptr(levels) if levels.size else None,
+                                                 max(levels.size, 1) - 1, _ptr(words) if words.size else None, words.size,
+                                                 ctypes.c_void_p(wires_dev), int(n), _ptr(out) if digests and j.size else None))
+        return out
+
+    def scatter_cells(self, cells, wires_dev, n):
+        """lcp2_scatter_cells: wires[col][row] = value for every record of `cells` (a numpy array of CELL_DTYPE records) in the device
+        witness matrix `wires_dev` (a pointer, column-major with n rows).  Rows are validated before anything runs; the COLUMN is
+        the caller's duty (the call does not know how many the matrix has); values are stored as given, canonical or not."""
+        if not isinstance(cells, np.ndarray) or cells.dtype != CELL_DTYPE:
+            raise Lcp2Error(-1, "cells must be an array of CELL_DTYPE records")
+        c = np.ascontiguousarray(cells).ravel()
+        self._check(self.lib.lcp2_scatter_cells(self.handle, _ptr(c) if c.size else None, c.size, ctypes.c_void_p(wires_dev), int(n)))
 
     def poseidon_gate_rows(self, rows, wires_dev, n):
         """lcp2_poseidon_gate_rows: writes all 135 cells of every PoseidonGate row of `rows` (a numpy array of POSEIDON_ROW_DTYPE

@@ -1,10 +1,11 @@
 // Witness-row entry points of liblcp2.so (K10): lcp2_sha256_witness, lcp2_scatter_cells, lcp2_poseidon_gate_rows,
 // lcp2_u32_gate_rows, lcp2_rec_gate_rows and lcp2_witness_plan_rows, with the device scratch, the host-to-device staging and the
-// refusal flag they share.  The kernels are in kernels_witness.hip; the per-row texts in sha_layout.hpp, pos_rows.hpp, u32_rows.hpp,
+// refusal flag they share.  The kernels are in kernels_witness.hip; the per-row texts in sha_rows.hpp, pos_rows.hpp, u32_rows.hpp,
 // rec_rows.hpp and pos_plan.hpp.
 #include <cstring>
 #include "internal.hpp"
 #include "sha_layout.hpp"
+#include "sha_rows.hpp"
 #include "pos_rows.hpp"
 #include "prover_kernels.hpp"
 #include "u32_rows.hpp"
@@ -92,18 +93,9 @@ extern "C" int lcp2_sha256_witness(lcp2_ctx *ctx, const lcp2_sha_job *jobs, size
                                    const uint32_t *words_in, size_t nwords, uint64_t *wires, uint64_t n, uint32_t *digests) {
   if (!ctx || !wires || (njobs && (!jobs || !level_start || nlevels == 0)) || (nwords && !words_in)) return LCP2_E_INVALID;
   if (njobs == 0) return LCP2_OK;
-  if (level_start[0] != 0 || level_start[nlevels] != njobs) return ctx->fail(LCP2_E_INVALID, "sha witness: level table does not cover the jobs");
-  // validate once so that the kernels cannot read or write out of range
-  for (uint32_t l = 0; l < nlevels; l++) {
-    if (level_start[l] > level_start[l + 1]) return ctx->fail(LCP2_E_INVALID, "sha witness: level table not monotone");
-    for (uint32_t j = level_start[l]; j < level_start[l + 1]; j++) {
-      if ((uint64_t)jobs[j].first_row + SHA_ROWS > n) return ctx->fail(LCP2_E_INVALID, "sha witness: rows out of range");
-      for (int i = 0; i < 16; i++) {
-        int32_t s = jobs[j].in_src[i];
-        if (s >= 0 ? (size_t)s >= nwords : (uint32_t)((~s) >> 3) >= level_start[l]) return ctx->fail(LCP2_E_INVALID, "sha witness: bad message source");
-      }
-    }
-  }
+  // validate once so that the kernels cannot read or write out of range (sha_rows.hpp)
+  if (const ShaProblem refused = sha_jobs_problem((const ShaJobDev *)jobs, njobs, level_start, nlevels, nwords, n); refused.problem)
+    return ctx->fail(LCP2_E_INVALID, sha_problem_str(refused.problem));
   LCP2_HIP(ctx, hipSetDevice(ctx->device));
   void *d_jobs, *d_words, *d_rec;
   LCP2_TRY(scratch_ensure(ctx, 0, njobs * sizeof(lcp2_sha_job), &d_jobs));
@@ -134,8 +126,7 @@ extern "C" int lcp2_sha256_witness(lcp2_ctx *ctx, const lcp2_sha_job *jobs, size
 extern "C" int lcp2_scatter_cells(lcp2_ctx *ctx, const lcp2_cell *cells, size_t ncells, uint64_t *wires, uint64_t n) {
   if (!ctx || !wires || (ncells && !cells)) return LCP2_E_INVALID;
   if (!ncells) return LCP2_OK;
-  for (size_t i = 0; i < ncells; i++)
-    if (cells[i].row >= n) return ctx->fail(LCP2_E_INVALID, "scatter: row out of range");
+  if (scatter_cells_problem((const CellDev *)cells, ncells, n) != ncells) return ctx->fail(LCP2_E_INVALID, "scatter: row out of range");
   LCP2_HIP(ctx, hipSetDevice(ctx->device));
   void *d;
   LCP2_TRY(scratch_ensure(ctx, 3, ncells * sizeof(lcp2_cell), &d));

@@ -174,7 +174,12 @@ int lcp2_sha256_tree(lcp2_ctx *ctx, const uint8_t *leaves, uint32_t height, size
  * the rows are filled directly in the device-resident witness matrix `wires` [num_wires][n] (column-major).
  * jobs are sorted by dependency level: jobs [level_start[l], level_start[l+1]) only read digests of earlier levels.
  * in_src[i] >= 0: message word = words_in[in_src[i]] ; in_src[i] < 0: digest word (~in_src[i]) & 7 of job (~in_src[i]) >> 3.
- * digests (host, njobs * 8 words, nullable) receives every job's digest for the host-side generators that depend on it. */
+ * digests (host, njobs * 8 words, nullable) receives every job's digest for the host-side generators that depend on it.
+ * What the tests pin (tests/test_sha_rows.py): n is the row count of the matrix and need not be a power of two; of a job's rows
+ * first_row .. first_row + 309 (first_row + 310 <= n) columns 0..107 are ALL written, unused cells with 0, and no other cell of
+ * the matrix is; a level may be empty (level_start[l] == level_start[l+1]); a source may name a job of ANY earlier level, not
+ * only the one before.  The lists are validated on the host before anything is launched: a refused call (LCP2_E_INVALID,
+ * lcp2_last_error says why) has written nothing.  njobs == 0 is LCP2_OK. */
 typedef struct {
   uint32_t first_row;
   int32_t in_src[16];
@@ -185,7 +190,9 @@ typedef struct {
 } lcp2_cell;
 int lcp2_sha256_witness(lcp2_ctx *ctx, const lcp2_sha_job *jobs, size_t njobs, const uint32_t *level_start, uint32_t nlevels,
                         const uint32_t *words_in, size_t nwords, uint64_t *wires, uint64_t n, uint32_t *digests);
-/* wires[col][row] = value for a list of cells (the non-SHA rows: constants, arithmetic glue, public inputs) */
+/* wires[col][row] = value for a list of cells (the non-SHA rows: constants, arithmetic glue, public inputs).  Only the ROWS are
+ * checked (row < n, on the host, before anything is launched: a refused list writes nothing); the call does not know how many
+ * columns the matrix has, so col is the caller's duty.  The value is stored as given, canonical or not. */
 int lcp2_scatter_cells(lcp2_ctx *ctx, const lcp2_cell *cells, size_t ncells, uint64_t *wires, uint64_t n);
 /* PoseidonGate rows generated on the device (plonky2 gates/poseidon.rs PoseidonGenerator::run_once; the reference's circuit holds
  * thousands of them inside verify_proof, eth-lc-plonky2/src/targets.rs:468-470): one job per row = the 12 input wires and the swap
