@@ -72,13 +72,7 @@ struct PlanProblem {
 };
 inline PlanProblem plan_lists_problem(const RecJobDev *rec, u64 nrec, const PosJobDev *pos, const u32 *chain_ends, u64 nchains,
                                       const RecOperandDev *operands, u64 noperands, u32 ncols, u64 n) {
-  for (u64 i = 0; i < nrec; i++) {
-    u32 problem = rec_job_problem(rec[i], operands, noperands, ncols, n);
-    const int checked = problem ? -1 : rec_value_operand(rec[i].kind, rec[i].op);
-    if (checked >= 0 && operands[(u64)rec[i].first_operand + checked].src == REC_IMM)
-      problem = rec_value_problem(rec[i].kind, gl_canon(operands[(u64)rec[i].first_operand + checked].v));
-    if (problem) return {0, problem, i};
-  }
+  if (const RecListProblem bad = rec_lists_problem(rec, nrec, operands, noperands, ncols, n); bad.problem) return {0, bad.problem, bad.job};
   for (u64 g = 0; g < nchains; g++) {
     const u64 begin = g ? chain_ends[g - 1] : 0;
     for (u64 i = begin; i < chain_ends[g]; i++) {

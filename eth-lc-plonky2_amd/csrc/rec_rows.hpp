@@ -4,7 +4,7 @@
 // ReducingExtensionGate, PoseidonMdsGate, RandomAccessGate, ExponentiationGate and CosetInterpolationGate as ONE function: job in,
 // operands through a load callback, (column, value) pairs out through a store callback.  k_rec_gate_rows (kernels_witness.hip) calls
 // it with loads from the operand list / the column-major witness matrix and stores into that matrix, lcp2_rec_gate_rows
-// (witness_rows.hip) validates a host list with rec_job_problem / rec_value_problem, and tests/emu/emu_rec.cpp compiles the same text for the CPU.
+// (witness_rows.hip) validates a host list with rec_lists_problem, and tests/emu/emu_rec.cpp compiles the same text for the CPU.
 // Layouts and values are those of the gate programs and integer generators in eth-lc-plonky2_amd/recursion_gates.py,
 // u32_gates.py (gate_coset_interpolation / row_coset_interpolation) and circuit.py (gate_arithmetic, gate_base_sum); like them the
 // layout is [RECALL] of plonky2 0.1.4 and its parity is UNPINNED.
@@ -99,6 +99,22 @@ inline const char *rec_problem_str(u32 problem) {
     case 11: return "coset-interpolation shift is zero";
     default: return "ok";
   }
+}
+// A HOST list checked completely, as lcp2_rec_gate_rows and lcp2_witness_plan_rows do before they queue anything: the structure of
+// every job, and the value condition of an operand that is IMM.  problem 0: nothing to refuse; otherwise the first refused job
+struct RecListProblem {
+  u32 problem;
+  u64 job;
+};
+inline RecListProblem rec_lists_problem(const RecJobDev *jobs, u64 njobs, const RecOperandDev *operands, u64 noperands, u32 ncols, u64 n) {
+  for (u64 i = 0; i < njobs; i++) {
+    u32 problem = rec_job_problem(jobs[i], operands, noperands, ncols, n);
+    const int checked = problem ? -1 : rec_value_operand(jobs[i].kind, jobs[i].op);
+    if (checked >= 0 && operands[(u64)jobs[i].first_operand + checked].src == REC_IMM)
+      problem = rec_value_problem(jobs[i].kind, gl_canon(operands[(u64)jobs[i].first_operand + checked].v));
+    if (problem) return {problem, i};
+  }
+  return {0, 0};
 }
 
 // the subgroup H of order 16 (u32_gates._coset_domain) and its barycentric weights 1 / prod_{j != i} (x_i - x_j)

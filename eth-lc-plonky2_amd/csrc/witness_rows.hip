@@ -63,27 +63,43 @@ struct Stage {
   }
 };
 
-// The refusal flag of a call whose kernels validate jobs (row_flag.hpp), in scratch slot 1
+// The refusal flag of a call whose kernels validate jobs (row_flag.hpp), in scratch slot 1: one word, or the two of a plan
 struct RefusalFlag {
   lcp2_ctx *ctx;
+  size_t nwords = 1;
   u64 *d = nullptr;
+  u64 words[2] = {0, 0};
   int begin() {
-    LCP2_TRY(scratch_ensure(ctx, 1, sizeof(u64), (void **)&d));
-    LCP2_HIP(ctx, hipMemsetAsync(d, 0xFF, sizeof(u64), ctx->stream));  // ROW_NO_PROBLEM
+    LCP2_TRY(scratch_ensure(ctx, 1, nwords * sizeof(u64), (void **)&d));
+    LCP2_HIP(ctx, hipMemsetAsync(d, 0xFF, nwords * sizeof(u64), ctx->stream));  // ROW_NO_PROBLEM
     return LCP2_OK;
   }
-  // after the last launch: launch errors first, then the word comes back and the stream is waited for (the caller's lists may go;
-  // every cell is written).  A refusal is LCP2_E_INVALID, "<family>: job N: <reason> (found on the device: <written>)"
-  int end(const char *family, const char *(*reason)(u32), const char *written) {
+  // after the last launch: launch errors first, then the words come back and the stream is waited for (the caller's lists may go;
+  // every cell is written)
+  int read() {
     LCP2_HIP(ctx, hipGetLastError());
-    u64 flag = 0;
-    LCP2_HIP(ctx, hipMemcpyAsync(&flag, d, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+    LCP2_HIP(ctx, hipMemcpyAsync(words, d, nwords * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (flag == ROW_NO_PROBLEM) return LCP2_OK;
-    return ctx->fail(LCP2_E_INVALID, std::string(family) + ": job " + std::to_string(flag >> 8) + ": " + reason((u32)(flag & 0xFF)) +
+    return LCP2_OK;
+  }
+  // read() of one word.  A refusal is LCP2_E_INVALID, "<family>: job N: <reason> (found on the device: <written>)"
+  int end(const char *family, const char *(*reason)(u32), const char *written) {
+    LCP2_TRY(read());
+    if (words[0] == ROW_NO_PROBLEM) return LCP2_OK;
+    return ctx->fail(LCP2_E_INVALID, std::string(family) + ": job " + std::to_string(words[0] >> 8) + ": " + reason((u32)(words[0] & 0xFF)) +
                                          " (found on the device: " + written + ")");
   }
 };
+
+// A table of ascending ends over `total` records, as level_ends, rec_level_ends, pos_level_ends and a host chain_ends must be:
+// ENDS_OK, or the first entry below the one before it or above `total`, or `count` where the table does not end at `total`
+constexpr size_t ENDS_OK = ~(size_t)0;
+size_t ends_problem(const uint32_t *ends, size_t count, size_t total) {
+  if (!total) return ENDS_OK;
+  for (size_t l = 0; l < count; l++)
+    if (ends[l] < (l ? ends[l - 1] : 0) || ends[l] > total) return l;
+  return count && ends[count - 1] == total ? ENDS_OK : count;
+}
 }  // namespace
 
 // ------------------------------------------------------------------ K10: witness generation, device buffers
@@ -206,21 +222,15 @@ extern "C" int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_
   if (lists_mem != LCP2_MEM_HOST && lists_mem != LCP2_MEM_DEVICE) return ctx->fail(LCP2_E_INVALID, "rec rows: bad lcp2_mem");
   if (!njobs) return LCP2_OK;
   if (ncols < REC_ROW_COLUMNS) return ctx->fail(LCP2_E_INVALID, "rec rows: the matrix needs at least 135 columns");
-  for (size_t l = 0; l < nlevels; l++)
-    if (level_ends[l] < (l ? level_ends[l - 1] : 0) || level_ends[l] > njobs)
-      return ctx->fail(LCP2_E_INVALID, "rec rows: level_ends is not ascending at level " + std::to_string(l));
-  if (level_ends[nlevels - 1] != njobs) return ctx->fail(LCP2_E_INVALID, "rec rows: level_ends does not end at njobs");
+  if (const size_t at = ends_problem(level_ends, nlevels, njobs); at != ENDS_OK)
+    return ctx->fail(LCP2_E_INVALID, at < nlevels ? "rec rows: level_ends is not ascending at level " + std::to_string(at)
+                                                  : std::string("rec rows: level_ends does not end at njobs"));
   const RecJobDev *list = (const RecJobDev *)jobs;
   const RecOperandDev *ops = (const RecOperandDev *)operands;
   const bool host = lists_mem == LCP2_MEM_HOST;
   if (host)
-    for (size_t i = 0; i < njobs; i++) {
-      u32 problem = rec_job_problem(list[i], ops, noperands, ncols, n);
-      const int checked = problem ? -1 : rec_value_operand(list[i].kind, list[i].op);
-      if (checked >= 0 && ops[(size_t)list[i].first_operand + checked].src == REC_IMM)
-        problem = rec_value_problem(list[i].kind, gl_canon(ops[(size_t)list[i].first_operand + checked].v));
-      if (problem) return ctx->fail(LCP2_E_INVALID, "rec rows: job " + std::to_string(i) + ": " + rec_problem_str(problem));
-    }
+    if (const RecListProblem bad = rec_lists_problem(list, njobs, ops, noperands, ncols, n); bad.problem)
+      return ctx->fail(LCP2_E_INVALID, "rec rows: job " + std::to_string(bad.job) + ": " + rec_problem_str(bad.problem));
   LCP2_HIP(ctx, hipSetDevice(ctx->device));
   RefusalFlag flag{ctx};
   LCP2_TRY(flag.begin());
@@ -270,19 +280,14 @@ extern "C" int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *pl
   if (p.nrec > 0xFFFFFFFFull || p.npos > 0xFFFFFFFFull || p.nchains > 0xFFFFFFFFull)
     return ctx->fail(LCP2_E_INVALID, "plan rows: more than 2^32 - 1 jobs or chains");
   const bool host = lists_mem == LCP2_MEM_HOST;
-  auto ends_problem = [&](const uint32_t *ends, size_t count, size_t total, const char *name) -> std::string {
-    if (!total) return "";
-    for (size_t l = 0; l < count; l++)
-      if (ends[l] < (l ? ends[l - 1] : 0) || ends[l] > total) return std::string("plan rows: ") + name + " is not ascending at entry " + std::to_string(l);
-    if (!count || ends[count - 1] != total) return std::string("plan rows: ") + name + " does not end at its count";
-    return "";
+  auto ends_text = [](const uint32_t *ends, size_t count, size_t total, const char *name) -> std::string {
+    const size_t at = ends_problem(ends, count, total);
+    if (at == ENDS_OK) return "";
+    return std::string("plan rows: ") + name + (at < count ? " is not ascending at entry " + std::to_string(at) : " does not end at its count");
   };
-  std::string bad = ends_problem(p.rec_level_ends, p.nlevels, p.nrec, "rec_level_ends");
-  if (bad.empty()) bad = ends_problem(p.pos_level_ends, p.nlevels, p.nchains, "pos_level_ends");
-  if (bad.empty() && host) {
-    bad = ends_problem(p.chain_ends, p.nchains, p.npos, "chain_ends");
-    if (bad.empty() && p.npos && !p.nchains) bad = "plan rows: chain_ends does not end at its count";
-  }
+  std::string bad = ends_text(p.rec_level_ends, p.nlevels, p.nrec, "rec_level_ends");
+  if (bad.empty()) bad = ends_text(p.pos_level_ends, p.nlevels, p.nchains, "pos_level_ends");
+  if (bad.empty() && host) bad = ends_text(p.chain_ends, p.nchains, p.npos, "chain_ends");
   if (!bad.empty()) return ctx->fail(LCP2_E_INVALID, bad);
   const RecJobDev *rec = (const RecJobDev *)p.rec_jobs;
   const PosJobDev *pos = (const PosJobDev *)p.pos_jobs;
@@ -292,9 +297,8 @@ extern "C" int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *pl
       return ctx->fail(LCP2_E_INVALID, std::string("plan rows: ") + (bad_job.family ? "poseidon job " : "rec job ") + std::to_string(bad_job.job) + ": " +
                                            (bad_job.family ? pos_plan_problem_str(bad_job.problem) : rec_problem_str(bad_job.problem)));
   LCP2_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *flags;
-  LCP2_TRY(scratch_ensure(ctx, 1, 2 * sizeof(u64), (void **)&flags));
-  LCP2_HIP(ctx, hipMemsetAsync(flags, 0xFF, 2 * sizeof(u64), ctx->stream));  // ROW_NO_PROBLEM twice
+  RefusalFlag flag{ctx, 2};
+  LCP2_TRY(flag.begin());
   const u32 *chain_ends = p.chain_ends;
   if (host) {
     void *d_rec, *d_ops, *d_pos;
@@ -314,15 +318,13 @@ extern "C" int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *pl
   }
   for (size_t l = 0; l < p.nlevels; l++) {
     const u64 rec_begin = p.nrec && l ? p.rec_level_ends[l - 1] : 0, rec_end = p.nrec ? p.rec_level_ends[l] : 0, shift = plan_shift(l);
-    launch_rec_gate_rows(ctx->stream, rec, shift, rec_begin + shift, rec_end + shift, ops, p.noperands, (u64 *)wires, ncols, n, flags, !host);
+    launch_rec_gate_rows(ctx->stream, rec, shift, rec_begin + shift, rec_end + shift, ops, p.noperands, (u64 *)wires, ncols, n, flag.d, !host);
     if (p.nchains)
       launch_pos_plan_chains(ctx->stream, pos, p.npos, chain_ends, l ? p.pos_level_ends[l - 1] : 0, p.pos_level_ends[l], ops, p.noperands,
-                             (u64 *)wires, ncols, n, ctx->d_rc, flags, plan_gate(rec_begin, l), rec_end + shift);
+                             (u64 *)wires, ncols, n, ctx->d_rc, flag.d, plan_gate(rec_begin, l), rec_end + shift);
   }
-  LCP2_HIP(ctx, hipGetLastError());
-  u64 words[2] = {0, 0};
-  LCP2_HIP(ctx, hipMemcpyAsync(words, flags, sizeof words, hipMemcpyDeviceToHost, ctx->stream));
-  LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's lists may go; every cell is written
+  LCP2_TRY(flag.read());
+  const u64 *words = flag.words;
   if (words[0] == ROW_NO_PROBLEM) return LCP2_OK;
   const char *written = " (found on the device: the valid rec jobs of its level, the rows of its chain before it, the other chains of its level and all "
                         "earlier levels are written, later levels are not)";

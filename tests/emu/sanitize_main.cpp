@@ -1,8 +1,8 @@
 // TEST HARNESS (not product code): emu_pos.cpp and emu_u32.cpp under ASan + UBSan as a stand-alone program
 // (tests/checks/emu_sanitize.sh): the Poseidon edge rows one by one and as a grid on a tagged matrix, and a u32 job list with two
-// refused jobs.  Exits non-zero on a wrong value; the sanitizers abort on a bad access or undefined arithmetic.
-#include <cstdio>
+// refused jobs.
 #include <vector>
+#include "sanitize_common.hpp"
 #include "../../eth-lc-plonky2_amd/csrc/pos_rows.hpp"
 #include "../../eth-lc-plonky2_amd/csrc/u32_rows.hpp"
 
@@ -15,8 +15,6 @@ void emu_pos_gate_rows(const PoseidonRowDev *rows, unsigned long long nrows, uns
 void emu_u32_gate_rows(const U32JobDev *jobs, unsigned long long njobs, unsigned long long *wires, unsigned long long n, unsigned long long *flag,
                        unsigned blocks, unsigned threads);
 }
-
-#define CHECK(cond) do { if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
 
 int main() {
   static u64 rc[POS_ROUNDS * POS_W];

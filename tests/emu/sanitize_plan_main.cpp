@@ -1,19 +1,11 @@
-// TEST HARNESS (not product code): emu_plan.cpp under ASan + UBSan as a stand-alone program, linked against nothing else:
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -o sanitize_plan tests/emu/sanitize_plan_main.cpp && ./sanitize_plan
+// TEST HARNESS (not product code): emu_plan.cpp under ASan + UBSan as a stand-alone program, linked against nothing else
+// (tests/checks/emu_sanitize.sh).
 // Random PoseidonGate chains with operands of all three sources against pos_row_cells row by row, and the refusals: every
 // structural reason (the lists sized exactly, so a read past a refused index is a heap overflow), a CELL swap of 2 in the middle of
-// a chain, and both families in one level.  Exits non-zero on a wrong value; the sanitizers abort on a bad access or undefined arithmetic.
-#include <cstdio>
+// a chain, and both families in one level.
 #include <vector>
 #include "emu_plan.cpp"
-
-#define CHECK(cond) do { if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
-
-static u64 rng_state = 0x9E3779B97F4A7C15ull;
-static u64 rnd() {
-  rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
-  return rng_state;
-}
+#include "sanitize_common.hpp"
 
 struct Plan {
   std::vector<RecJobDev> rec;

@@ -1,23 +1,13 @@
 // TEST HARNESS (not product code): emu_sha.cpp (csrc/sha_rows.hpp on the CPU) under ASan + UBSan as a stand-alone program, linked
-// against nothing else:
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -o sanitize_sha tests/emu/sanitize_sha_main.cpp && ./sanitize_sha
+// against nothing else (tests/checks/emu_sanitize.sh).
 // Random jobs in three levels (sources: words_in, digests one and two levels back) into a matrix of exactly [108][n] with a job
 // flush against its end, so one store too far is a heap overflow; every list is sized exactly, so a read behind a refused index is
 // one too.  The digests are held to a plain SHA-256 written here, the owned cells must all be written and no other, and the
-// validation cases of the entry point are refused with nothing written.  Exits non-zero on a wrong value; the sanitizers abort on a
-// bad access or undefined arithmetic.  Prints one summary line.
-#include <cstdio>
+// validation cases of the entry point are refused with nothing written.  Prints one summary line.
 #include <cstring>
 #include <vector>
 #include "emu_sha.cpp"
-
-#define CHECK(cond) do { if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
-
-static u64 rng_state = 0x9E3779B97F4A7C15ull;
-static u64 rnd() {
-  rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
-  return rng_state;
-}
+#include "sanitize_common.hpp"
 
 // SHA-256 of a 64-byte message given as 16 big-endian words, the textbook way (FIPS 180-4 section 6.2), constants recomputed from
 // the primes so that nothing is shared with the tables of sha_rows.hpp

@@ -1,21 +1,15 @@
-// TEST HARNESS (not product code): emu_verify.cpp under ASan + UBSan as a stand-alone program, linked against nothing else:
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -o sanitize_verify tests/emu/sanitize_verify_main.cpp && ./sanitize_verify
+// TEST HARNESS (not product code): emu_verify.cpp under ASan + UBSan as a stand-alone program, linked against nothing else
+// (tests/checks/emu_sanitize.sh).
 // A small layout (16 leaves, two FRI layers of arity 2, cap height 1, three queries) and every job of the two query kernels over:
 // a GENERATED proof - real Merkle trees over random leaves, the fold chain of query 0 made consistent down to the final polynomial -
 // whose paths must all hold and whose query 0 must pass; then proofs filled with p - 1, with zeros and with random words, whose jobs
 // must run to a verdict without leaving the proof.  Every proof lives in a heap block of exactly proof_words words, so a read past it
-// is a heap overflow.  Exits non-zero on a wrong value; the sanitizers abort on a bad access or undefined arithmetic.
-#include <cstdio>
+// is a heap overflow.
 #include <vector>
 #include "emu_verify.cpp"
+#include "sanitize_common.hpp"
 
-#define CHECK(cond) do { if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
-
-static u64 rng_state = 0x9E3779B97F4A7C15ull;
-static u64 rnd() {
-  rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
-  return rng_state % GL_P;
-}
+static u64 rnd_gl() { return rnd() % GL_P; }  // a canonical field element
 
 // a Merkle tree over nleaves leaves of leaf_len words: level 0 = leaf digests ... the cap level
 struct Tree {
@@ -52,18 +46,18 @@ int main() {
   std::vector<u64> cs_cap(L.capw);
   VqChallenge c;
   memset(&c, 0, sizeof c);
-  c.zeta = gl2_make(rnd(), rnd()); c.g_zeta = gl2_scale(c.zeta, gl_root_of_unity(p.degree_bits)); c.fri_alpha = gl2_make(rnd(), rnd());
-  c.alpha_ch = gl2_pow(c.fri_alpha, p.num_challenges); c.red0 = gl2_make(rnd(), rnd()); c.red1 = gl2_make(rnd(), rnd());
-  c.fri_betas[0] = gl2_make(rnd(), rnd()); c.fri_betas[1] = gl2_make(rnd(), rnd());
+  c.zeta = gl2_make(rnd_gl(), rnd_gl()); c.g_zeta = gl2_scale(c.zeta, gl_root_of_unity(p.degree_bits)); c.fri_alpha = gl2_make(rnd_gl(), rnd_gl());
+  c.alpha_ch = gl2_pow(c.fri_alpha, p.num_challenges); c.red0 = gl2_make(rnd_gl(), rnd_gl()); c.red1 = gl2_make(rnd_gl(), rnd_gl());
+  c.fri_betas[0] = gl2_make(rnd_gl(), rnd_gl()); c.fri_betas[1] = gl2_make(rnd_gl(), rnd_gl());
   c.x_index[0] = 3; c.x_index[1] = 12; c.x_index[2] = 9;  // distinct cosets in both layers
   c.live = 1;
 
   // ---- the generated proof
   std::vector<u64> proof(L.total);
-  for (u64 &w : proof) w = rnd();
+  for (u64 &w : proof) w = rnd_gl();
   std::vector<u64> leaves[6];
-  for (u32 t = 0; t < 4; t++) { leaves[t].resize((size_t)N * V.tree[t].leaf_len); for (u64 &w : leaves[t]) w = rnd(); }
-  for (u32 l = 0; l < 2; l++) { leaves[4 + l].resize((size_t)(N >> V.tree[4 + l].index_shift) * 4); for (u64 &w : leaves[4 + l]) w = rnd(); }
+  for (u32 t = 0; t < 4; t++) { leaves[t].resize((size_t)N * V.tree[t].leaf_len); for (u64 &w : leaves[t]) w = rnd_gl(); }
+  for (u32 l = 0; l < 2; l++) { leaves[4 + l].resize((size_t)(N >> V.tree[4 + l].index_shift) * 4); for (u64 &w : leaves[4 + l]) w = rnd_gl(); }
   {  // query 0's fold chain: each layer's leaf holds the value carried so far at `within`, the final polynomial the last one
     u64 *R = &proof[L.queries];
     for (u32 t = 0; t < 4; t++) for (u32 j = 0; j < V.tree[t].leaf_len; j++) R[V.tree[t].leaf_off + j] = leaves[t][(size_t)c.x_index[0] * V.tree[t].leaf_len + j];
@@ -119,10 +113,10 @@ int main() {
   u32 fills = 0;
   for (int kind = 0; kind < 5; kind++, fills++) {
     std::vector<u64> f(L.total);
-    for (u64 &w : f) w = kind == 0 ? GL_P - 1 : kind == 1 ? 0 : rnd();
+    for (u64 &w : f) w = kind == 0 ? GL_P - 1 : kind == 1 ? 0 : rnd_gl();
     VqChallenge cc = c;
     if (kind == 1) { memset(&cc, 0, sizeof cc); cc.live = 1; }                                         // zero challenges: inverses of zero
-    if (kind >= 2) for (u32 q = 0; q < Q; q++) cc.x_index[q] = (u32)(rnd() % N);
+    if (kind >= 2) for (u32 q = 0; q < Q; q++) cc.x_index[q] = (u32)(rnd_gl() % N);
     if (kind == 4) for (u32 q = 0; q < Q; q++) cc.x_index[q] = N - 1;                                  // the last leaf, the last cap entry
     std::vector<u64> cap(L.capw, kind == 0 ? GL_P - 1 : 0);
     emu_query_jobs(V, cc, f.data(), cap.data(), status);

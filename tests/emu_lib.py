@@ -1,54 +1,23 @@
-"""Builds/loads tests/emu/libemu.so: CPU emulation of the device kernels' phases (test harness only)."""
-import ctypes
-import os
-import subprocess
+"""Loads tests/emu/libemu.so and libemu_gates.so: CPU emulation of the device kernels' phases (test harness only), built by
+rows_lib.build_emu."""
+import ctypes as c
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu.cpp")
-LIB = os.path.join(HERE, "emu", "libemu.so")
-CSRC = os.path.join(HERE, "..", "eth-lc-plonky2_amd", "csrc")
+from rows_lib import build_emu
+
+V = c.c_void_p
 
 
 def load():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    E = ctypes.CDLL(LIB)
-    c = ctypes
-    V = c.c_void_p
-    E.emu_poseidon_permute.argtypes = [V]
-    E.emu_poseidon_permute_grouped.argtypes = [V]
-    E.emu_poseidon_partial_max_entry.restype = c.c_uint32
-    E.emu_gl_mul.restype = c.c_uint64
-    E.emu_gl_mul.argtypes = [c.c_uint64, c.c_uint64]
-    E.emu_gl_shl.restype = c.c_uint64
-    E.emu_gl_shl.argtypes = [c.c_uint64, c.c_uint]
-    E.emu_ntt_forward.restype = c.c_int
-    E.emu_ntt_forward.argtypes = [V, V, c.c_uint32, c.c_uint32, c.c_uint64, c.c_uint32]
-    E.emu_ntt_inverse_natural.argtypes = [V, V, c.c_uint32, c.c_uint32]
-    E.emu_ntt_inverse_bitrev.argtypes = [V, V, c.c_uint32, c.c_uint32, c.c_uint64]
-    return E
-
-
-GATES_SRC = os.path.join(HERE, "emu", "emu_gates.cpp")
-GATES_LIB = os.path.join(HERE, "emu", "libemu_gates.so")
+    return build_emu("emu", (
+        ("emu_poseidon_permute", None, [V]), ("emu_poseidon_permute_grouped", None, [V]), ("emu_poseidon_partial_max_entry", c.c_uint32, []),
+        ("emu_gl_mul", c.c_uint64, [c.c_uint64, c.c_uint64]), ("emu_gl_shl", c.c_uint64, [c.c_uint64, c.c_uint]),
+        ("emu_ntt_forward", c.c_int, [V, V, c.c_uint32, c.c_uint32, c.c_uint64, c.c_uint32]),
+        ("emu_ntt_inverse_natural", None, [V, V, c.c_uint32, c.c_uint32]), ("emu_ntt_inverse_bitrev", None, [V, V, c.c_uint32, c.c_uint32, c.c_uint64])))
 
 
 def load_gates():
     """tests/emu/libemu_gates.so: the generated gate evaluators (csrc/generated_gates_*.hpp) compiled for the CPU"""
-    deps = [GATES_SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.startswith("generated_gates") or f in ("gate_helpers.hpp", "gl64.hpp")]
-    if not os.path.exists(GATES_LIB) or any(os.path.getmtime(d) > os.path.getmtime(GATES_LIB) for d in deps):
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-o", GATES_LIB, GATES_SRC], check=True)
-    E = ctypes.CDLL(GATES_LIB)
-    c = ctypes
-    V = c.c_void_p
-    E.emu_generated_count.restype = c.c_uint
-    E.emu_generated_waves.restype = c.c_uint
-    E.emu_generated_waves.argtypes = [c.c_uint]
-    E.emu_generated_gate.restype = c.c_int
-    E.emu_generated_gate.argtypes = [c.c_uint, V, V, V, c.c_uint, c.c_uint64, V, V]
-    E.emu_gl_mul_u32.restype = c.c_uint64
-    E.emu_gl_mul_u32.argtypes = [c.c_uint64, c.c_uint32]
-    E.emu_gl_shl_nc.restype = c.c_uint64
-    E.emu_gl_shl_nc.argtypes = [c.c_uint64, c.c_uint]
-    return E
+    return build_emu("emu_gates", (
+        ("emu_generated_count", c.c_uint, []), ("emu_generated_waves", c.c_uint, [c.c_uint]),
+        ("emu_generated_gate", c.c_int, [c.c_uint, V, V, V, c.c_uint, c.c_uint64, V, V]),
+        ("emu_gl_mul_u32", c.c_uint64, [c.c_uint64, c.c_uint32]), ("emu_gl_shl_nc", c.c_uint64, [c.c_uint64, c.c_uint])), opt="-O1")

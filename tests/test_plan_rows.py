@@ -6,24 +6,13 @@ CPU (tests/emu/emu_plan.cpp) against poseidon_py.gate_row, recursion_gates.run_w
 and the null check of the entry point.  On the GPU: the same through the library (k_pos_plan_chains walks a chain with a 16-lane
 group), exact equality of whole matrices, the refusals, and a proof from a device-filled matrix."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import gate_program_ref as ref
+import rows_lib
+from rows_lib import INVALID, MAX, NONE, NW, P, TAG, DeviceMatrix, build_emu, check_null_context, gate_constraints, upload
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_plan.cpp")
-LIB = os.path.join(HERE, "emu", "libemu_plan.so")
-CSRC = os.path.join(HERE, "..", "eth-lc-plonky2_amd", "csrc")
-P = 0xFFFFFFFF00000001
-MAX = (1 << 64) - 1
-INVALID = -1
-NW = 135
-NONE = MAX       # a flag word while nothing is refused
-TAG = MAX - 1    # not a canonical field element: no cell a job writes holds it
 ARITH, BSUM, RA = 0, 1, 7
 REASONS = {1: "row out of range", 2: "operands run past", 3: "src above 2", 4: "first job of a chain", 5: "PREV as the swap", 6: "column of 12 or more",
            7: "cell operand column", 8: "cell operand row", 9: "swap value not 0 or 1"}
@@ -36,22 +25,17 @@ def rg():
 
 @pytest.fixture(scope="module")
 def emul():
-    """tests/emu/libemu_plan.so, built with g++ the way test_rec_rows.py::emur builds its library"""
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("pos_plan.hpp", "pos_rows.hpp", "poseidon.hpp", "rec_rows.hpp", "row_flag.hpp", "gl64.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    E = ctypes.CDLL(LIB)
+    """tests/emu/libemu_plan.so"""
     c, V, U = ctypes, ctypes.c_void_p, ctypes.c_uint64
-    for name, res, args in (("emu_plan_pos_job_bytes", c.c_uint, []), ("emu_plan_operand_bytes", c.c_uint, []), ("emu_plan_pos_operands", c.c_uint, []),
+    return build_emu("emu_plan", (("emu_plan_pos_job_bytes", c.c_uint, []), ("emu_plan_operand_bytes", c.c_uint, []), ("emu_plan_pos_operands", c.c_uint, []),
                             ("emu_plan_problem_str", c.c_char_p, [c.c_uint]), ("emu_plan_pos_problem", c.c_uint, [V, c.c_int, V, U, c.c_uint, U]),
                             ("emu_plan_lists_problem", c.c_uint, [V, U, V, V, U, V, U, c.c_uint, U, V, V]),
-                            ("emu_plan_level", None, [V, U, U, V, U, V, U, U, V, U, V, c.c_uint, U, V, U, c.c_uint])):
-        getattr(E, name).restype, getattr(E, name).argtypes = res, args
-    return E
+                            ("emu_plan_level", None, [V, U, U, V, U, V, U, U, V, U, V, c.c_uint, U, V, U, c.c_uint])))
 
 
 def vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p) if a.size else None
+    """(an empty list of a plan goes in as a null pointer)"""
+    return rows_lib.vp(a) if a.size else None
 
 
 def level_bounds(plan):
@@ -91,14 +75,6 @@ def lists_problem(E, plan, n, noperands=None):
     code = E.emu_plan_lists_problem(vp(plan.rec_jobs), plan.rec_jobs.size, vp(plan.pos_jobs), vp(plan.chain_ends), plan.chain_ends.size,
                                     vp(plan.operands), plan.operands.size if noperands is None else noperands, NW, n, ctypes.byref(family), ctypes.byref(job))
     return (("rec", "poseidon")[family.value], job.value, code) if code else None
-
-
-def gate_constraints(gs, name, row, consts):
-    g = gs.gates[gs.index(name)]
-    code = gs.code[2 * g.code_offset:2 * (g.code_offset + g.code_len)]
-    emitted = ref.emitted_constraints(code, gs.imm, row, consts, None)
-    assert len(emitted) == g.num_constraints
-    return emitted
 
 
 def arith(row, op, v, c=(1, 0)):
@@ -326,43 +302,15 @@ def test_entry_point_checks_its_pointers_first():
     import eth_lc_plonky2_amd as m
     g = rg()
     lib = m.load_library()
-    buf = np.zeros(NW * 64, dtype=np.uint64)
     good = g.pack_witness_plan(refusal_levels(False)[0])
     bad = g.pack_witness_plan([([], [reason_cases()[4]])])
     empty = g.pack_witness_plan([])
-    for mem in (m.MEM_HOST, m.MEM_DEVICE):
-        for plan in (good, bad, empty):
-            s, keep = plan_struct(m, plan)
-            assert lib.lcp2_witness_plan_rows(None, ctypes.byref(s), mem, buf.ctypes.data_as(ctypes.c_void_p), NW, 64) == INVALID
-        assert lib.lcp2_witness_plan_rows(None, None, mem, buf.ctypes.data_as(ctypes.c_void_p), NW, 64) == INVALID
-    assert not buf.any()
+    structs = [plan_struct(m, plan) for plan in (good, bad, empty)]
+    check_null_context(lambda a, mem, w: lib.lcp2_witness_plan_rows(None, *a, mem, w, NW, 64), [(ctypes.byref(s),) for s, keep in structs] + [(None,)],
+                       (m.MEM_HOST, m.MEM_DEVICE))
 
 
 # ------------------------------------------------------------------ on the GPU
-class DeviceMatrix:
-    """a [columns][n] matrix in HBM"""
-
-    def __init__(self, ctx, host):
-        self.ctx, self.shape = ctx, host.shape
-        self.ptr = ctx.buffer_alloc(host.size)
-        ctx.buffer_write(self.ptr, host)
-
-    def read(self):
-        return self.ctx.buffer_read(self.ptr, self.shape[0] * self.shape[1]).reshape(self.shape)
-
-    def free(self):
-        self.ctx.buffer_free(self.ptr)
-
-
-def upload(ctx, records):
-    """records of 4, 8 or 16 bytes -> a device pointer (padded to whole words)"""
-    raw = np.frombuffer(np.ascontiguousarray(records).tobytes() + b"\0" * (-records.nbytes % 8), dtype=np.uint64)
-    ptr = ctx.buffer_alloc(max(raw.size, 1))
-    if raw.size:
-        ctx.buffer_write(ptr, raw)
-    return ptr
-
-
 class Resident:
     """the four lists of a plan in HBM"""
 

@@ -5,44 +5,20 @@ loop - compiled for the CPU (tests/emu/emu_pos.cpp) against poseidon_py.gate_row
 point.  (The host row generator with its AVX2 MDS layer against the same text: tests/cpp test_poseidon_gate_outputs_match_rows.)
 On the GPU: the same through the library, against the emulation's matrix."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_pos.cpp")
-LIB = os.path.join(HERE, "emu", "libemu_pos.so")
-CSRC = os.path.join(HERE, "..", "eth-lc-plonky2_amd", "csrc")
-P = 0xFFFFFFFF00000001
-MAX = (1 << 64) - 1
-INVALID = -1
-NW = 135
-TAG = MAX - 1   # not a canonical field element: no cell a job writes holds it
+from rows_lib import INVALID, MAX, NW, P, TAG, DeviceMatrix, build_emu, check_null_context, vp
 
 
 @pytest.fixture(scope="module")
 def emup():
-    """tests/emu/libemu_pos.so, built with g++ the way test_u32_rows builds its library"""
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("pos_rows.hpp", "poseidon.hpp", "gl64.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    E = ctypes.CDLL(LIB)
+    """tests/emu/libemu_pos.so"""
     c, V = ctypes, ctypes.c_void_p
-    E.emu_pos_row_bytes.restype = c.c_uint
-    E.emu_pos_gate_wires.restype = c.c_uint
-    E.emu_pos_row_problem.restype = c.c_uint
-    E.emu_pos_row_problem.argtypes = [V, c.c_uint64]
-    E.emu_pos_row_cells.restype = c.c_uint
-    E.emu_pos_row_cells.argtypes = [V, V, V, c.c_uint]
-    E.emu_pos_gate_rows.restype = None
-    E.emu_pos_gate_rows.argtypes = [V, c.c_uint64, V, c.c_uint64, c.c_uint, c.c_uint]
-    return E
-
-
-def vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
+    return build_emu("emu_pos", (("emu_pos_row_bytes", c.c_uint, []), ("emu_pos_gate_wires", c.c_uint, []), ("emu_pos_row_problem", c.c_uint, [V, c.c_uint64]),
+                                 ("emu_pos_row_cells", c.c_uint, [V, V, V, c.c_uint]),
+                                 ("emu_pos_gate_rows", None, [V, c.c_uint64, V, c.c_uint64, c.c_uint, c.c_uint])))
 
 
 def make_rows(items):
@@ -157,30 +133,11 @@ def test_grid_writes_its_rows_and_nothing_else(emup, count):
 def test_entry_point_checks_its_pointers_first():
     import eth_lc_plonky2_amd as m
     lib = m.load_library()
-    buf = np.zeros(NW * 64, dtype=np.uint64)
     good, bad = make_rows([(0, 0, [1] * 12)]), make_rows([(64, 0, [1] * 12)])
-    assert lib.lcp2_poseidon_gate_rows(None, vp(good), 1, vp(buf), 64) == INVALID
-    assert lib.lcp2_poseidon_gate_rows(None, vp(bad), 1, vp(buf), 64) == INVALID
-    assert lib.lcp2_poseidon_gate_rows(None, None, 0, vp(buf), 64) == INVALID
-    assert not buf.any()
+    check_null_context(lambda a, mem, w: lib.lcp2_poseidon_gate_rows(None, *a, w, 64), [(vp(good), 1), (vp(bad), 1), (None, 0)])
 
 
 # ------------------------------------------------------------------ on the GPU
-class DeviceMatrix:
-    """a [columns][n] matrix in HBM"""
-
-    def __init__(self, ctx, host):
-        self.ctx, self.shape = ctx, host.shape
-        self.ptr = ctx.buffer_alloc(host.size)
-        ctx.buffer_write(self.ptr, host)
-
-    def read(self):
-        return self.ctx.buffer_read(self.ptr, self.shape[0] * self.shape[1]).reshape(self.shape)
-
-    def free(self):
-        self.ctx.buffer_free(self.ptr)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("count", [1, 63, 64, 65, 257])
 def test_device_rows_equal_the_emulation(gpu_ctx, emup, count):

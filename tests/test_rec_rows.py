@@ -8,23 +8,12 @@ lanes - compiled for the CPU (tests/emu/emu_rec.cpp) against the integer generat
 the argument checks of the entry point.  On the GPU: the same through the library, and a proof from a device-filled matrix
 against the host matrix' and the oracle's."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import gate_program_ref as ref
+from rows_lib import INVALID, MAX, NONE, NW, P, DeviceMatrix, build_emu, check_null_context, gate_constraints, upload, vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_rec.cpp")
-LIB = os.path.join(HERE, "emu", "libemu_rec.so")
-CSRC = os.path.join(HERE, "..", "eth-lc-plonky2_amd", "csrc")
-P = 0xFFFFFFFF00000001
-MAX = (1 << 64) - 1
-INVALID = -1
-NW = 135
-NONE = MAX   # the flag word while nothing is refused
 ARITH, BSUM, AEXT, MEXT, RED, REDX, PMDS, RA, EXP, COSET = range(10)
 OPS = {ARITH: 20, BSUM: 1, AEXT: 10, MEXT: 13, RED: 1, REDX: 1, PMDS: 1, RA: 5, EXP: 1, COSET: 1}
 COUNT = {ARITH: 5, BSUM: 1, AEXT: 8, MEXT: 5, RED: 47, REDX: 68, PMDS: 24, RA: 17, EXP: 3, COSET: 35}   # (RA op 4: 2)
@@ -37,24 +26,14 @@ def rg():
 
 @pytest.fixture(scope="module")
 def emur():
-    """tests/emu/libemu_rec.so, built with g++ the way emu32 builds libemu_u32.so"""
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("rec_rows.hpp", "row_flag.hpp", "gl64.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    E = ctypes.CDLL(LIB)
+    """tests/emu/libemu_rec.so"""
     c, V, U = ctypes, ctypes.c_void_p, ctypes.c_uint64
-    for name, res, args in (("emu_rec_job_bytes", c.c_uint, []), ("emu_rec_operand_bytes", c.c_uint, []), ("emu_rec_row_columns", c.c_uint, []),
+    return build_emu("emu_rec", (("emu_rec_job_bytes", c.c_uint, []), ("emu_rec_operand_bytes", c.c_uint, []), ("emu_rec_row_columns", c.c_uint, []),
                             ("emu_rec_kind_ops", c.c_uint, [c.c_uint]), ("emu_rec_kind_operands", c.c_uint, [c.c_uint, c.c_uint]),
                             ("emu_rec_coset_domain", U, [c.c_uint]), ("emu_rec_coset_weight", U, [c.c_uint]),
                             ("emu_rec_job_problem", c.c_uint, [V, V, U, c.c_uint, U]), ("emu_rec_value_problem", c.c_uint, [V, V]),
                             ("emu_rec_job_cells", c.c_uint, [V, V, V, V, c.c_uint]),
-                            ("emu_rec_level", None, [V, U, U, V, U, V, c.c_uint, U, V, c.c_uint])):
-        getattr(E, name).restype, getattr(E, name).argtypes = res, args
-    return E
-
-
-def vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
+                            ("emu_rec_level", None, [V, U, U, V, U, V, c.c_uint, U, V, c.c_uint])))
 
 
 def imm_job(kind, op, vals, row=0):
@@ -82,14 +61,6 @@ def emu_run(E, jobs, ops, ends, n, threads, start=None, order=None):
     for begin, end in (bounds if order is None else [bounds[l] for l in order]):
         E.emu_rec_level(vp(jobs), begin, end, vp(ops), ops.size, vp(got), NW, n, vp(flag), threads)
     return got, int(flag[0])
-
-
-def gate_constraints(gs, name, row, consts):
-    g = gs.gates[gs.index(name)]
-    code = gs.code[2 * g.code_offset:2 * (g.code_offset + g.code_len)]
-    emitted = ref.emitted_constraints(code, gs.imm, row, consts, None)
-    assert len(emitted) == g.num_constraints
-    return emitted
 
 
 # ------------------------------------------------------------------ the edge jobs (tests 3 and 7)
@@ -368,42 +339,15 @@ def test_entry_point_checks_its_pointers_first():
     hold (a valid job, refused ones, nothing), for both lists_mem values, never a crash or another status"""
     import eth_lc_plonky2_amd as m
     lib = m.load_library()
-    buf = np.zeros(NW * 64, dtype=np.uint64)
     good_jobs, good_ops = imm_job(ARITH, 0, [1, 2, 3, 4, 5])
     bad_jobs, bad_ops = raw_job(64, 10, 99, [(1, 0, 2)])
     one, none = np.array([1], dtype=np.uint32), None
-    for mem in (m.MEM_HOST, m.MEM_DEVICE):
-        assert lib.lcp2_rec_gate_rows(None, vp(good_jobs), 1, vp(good_ops), 5, vp(one), 1, mem, vp(buf), NW, 64) == INVALID
-        assert lib.lcp2_rec_gate_rows(None, vp(bad_jobs), 1, vp(bad_ops), 1, vp(one), 1, mem, vp(buf), NW, 64) == INVALID
-        assert lib.lcp2_rec_gate_rows(None, none, 0, none, 0, none, 0, mem, vp(buf), NW, 64) == INVALID
-        assert lib.lcp2_rec_gate_rows(None, none, 1, none, 0, none, 1, mem, None, NW, 64) == INVALID
-    assert not buf.any()
+    check_null_context(lambda a, mem, w: lib.lcp2_rec_gate_rows(None, *a, mem, w, NW, 64),
+                       [(vp(good_jobs), 1, vp(good_ops), 5, vp(one), 1), (vp(bad_jobs), 1, vp(bad_ops), 1, vp(one), 1), (none, 0, none, 0, none, 0)],
+                       (m.MEM_HOST, m.MEM_DEVICE), null_wires=(none, 1, none, 0, none, 1))
 
 
 # ------------------------------------------------------------------ on the GPU
-class DeviceMatrix:
-    """a [columns][n] matrix in HBM"""
-
-    def __init__(self, ctx, host):
-        self.ctx, self.shape = ctx, host.shape
-        self.ptr = ctx.buffer_alloc(host.size)
-        ctx.buffer_write(self.ptr, host)
-
-    def read(self):
-        return self.ctx.buffer_read(self.ptr, self.shape[0] * self.shape[1]).reshape(self.shape)
-
-    def free(self):
-        self.ctx.buffer_free(self.ptr)
-
-
-def upload(ctx, records):
-    """16-byte records -> a device pointer"""
-    ptr = ctx.buffer_alloc(max(records.size, 1) * 2)
-    if records.size:
-        ctx.buffer_write(ptr, np.ascontiguousarray(records).view(np.uint64))
-    return ptr
-
-
 def run_on_device(ctx, jobs, ops, ends, start, device_lists=False):
     n = start.shape[1]
     dm = DeviceMatrix(ctx, start)

@@ -21,15 +21,10 @@ import pytest
 import gate_program_ref
 import sha_rows_ref as ref
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "emu", "emu_sha.cpp")
-LIB = os.path.join(HERE, "emu", "libemu_sha.so")
-CSRC = os.path.join(ROOT, "eth-lc-plonky2_amd", "csrc")
+from rows_lib import HERE, INVALID, NW, ROOT, build_emu
+
 HOST = os.path.join(ROOT, "eth-lc-plonky2_amd", "host")
 SENTINEL = 0xA5A5A5A5A5A5A5A5
-NW = 135
-INVALID = -1
 M32 = 0xFFFFFFFF
 PIN_BYTES = 4 << 20   # lcp2_ctx::PIN_BYTES (csrc/internal.hpp)
 T_COVER, T_MONOTONE, T_ROWS, T_SOURCE = ("sha witness: level table does not cover the jobs", "sha witness: level table not monotone",
@@ -44,23 +39,12 @@ def vp(a):
 
 @pytest.fixture(scope="module")
 def emus():
-    """tests/emu/libemu_sha.so, built with g++ the way test_u32_rows.py builds its harness"""
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("sha_rows.hpp", "sha_layout.hpp", "gl64.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    E = ctypes.CDLL(LIB)
-    c, V = ctypes, ctypes.c_void_p
-    for name in ("emu_sha_job_bytes", "emu_sha_cell_bytes", "emu_sha_rows", "emu_sha_row_columns"):
-        getattr(E, name).restype = c.c_uint
-    E.emu_sha_problem_str.restype = c.c_char_p
-    E.emu_sha_problem_str.argtypes = [c.c_uint]
-    E.emu_sha_jobs_problem.restype = c.c_uint
-    E.emu_sha_jobs_problem.argtypes = [V, c.c_uint64, V, c.c_uint, c.c_uint64, c.c_uint64, V]
-    E.emu_sha256_witness.restype = c.c_uint
-    E.emu_sha256_witness.argtypes = [V, c.c_uint64, V, c.c_uint, V, c.c_uint64, V, c.c_uint64, V]
-    E.emu_scatter_cells.restype = c.c_uint
-    E.emu_scatter_cells.argtypes = [V, c.c_uint64, V, c.c_uint64]
-    return E
+    """tests/emu/libemu_sha.so"""
+    c, V, U = ctypes, ctypes.c_void_p, ctypes.c_uint64
+    return build_emu("emu_sha", (("emu_sha_job_bytes", c.c_uint, []), ("emu_sha_cell_bytes", c.c_uint, []), ("emu_sha_rows", c.c_uint, []),
+                                 ("emu_sha_row_columns", c.c_uint, []), ("emu_sha_problem_str", c.c_char_p, [c.c_uint]),
+                                 ("emu_sha_jobs_problem", c.c_uint, [V, U, V, c.c_uint, U, U, V]),
+                                 ("emu_sha256_witness", c.c_uint, [V, U, V, c.c_uint, V, U, V, U, V]), ("emu_scatter_cells", c.c_uint, [V, U, V, U])))
 
 
 @pytest.fixture(scope="module")

@@ -6,54 +6,27 @@ Without a GPU: csrc/u32_rows.hpp - the per-job function the kernel runs, and the
 integers and against the gates' own constraint programs, witness_jobs / job_columns, and the argument checks of the entry point.
 On the GPU: the same through the library, and a proof from a device-filled matrix against the host witness' and the oracle's."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import gate_program_ref as ref
+from rows_lib import INVALID, NONE, NW, P, DeviceMatrix, build_emu, check_null_context, upload, vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_u32.cpp")
-LIB = os.path.join(HERE, "emu", "libemu_u32.so")
-CSRC = os.path.join(HERE, "..", "eth-lc-plonky2_amd", "csrc")
-P = 0xFFFFFFFF00000001
 M = 0xFFFFFFFF
-INVALID = -1
-NONE = (1 << 64) - 1   # the flag word while nothing is refused
 ARITH, ADD, SUB, RANGE, CMP = range(5)
 OPS = {ARITH: 3, ADD: 5, SUB: 6, RANGE: 7, CMP: 1}
 GATE = {ARITH: "U32ArithmeticGate", ADD: "U32AddManyGate", SUB: "U32SubtractionGate", RANGE: "U32RangeCheckGate", CMP: "ComparisonGate"}
-NW = 135
 
 
 @pytest.fixture(scope="module")
 def emu32():
-    """tests/emu/libemu_u32.so, built with g++ the way emu_lib builds libemu.so"""
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("u32_rows.hpp", "row_flag.hpp", "gl64.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    E = ctypes.CDLL(LIB)
+    """tests/emu/libemu_u32.so"""
     c, V = ctypes, ctypes.c_void_p
-    E.emu_u32_job_bytes.restype = c.c_uint
-    E.emu_u32_row_columns.restype = c.c_uint
-    E.emu_u32_kind_ops.restype = c.c_uint
-    E.emu_u32_kind_ops.argtypes = [c.c_uint]
-    E.emu_u32_job_problem.restype = c.c_uint
-    E.emu_u32_job_problem.argtypes = [V, c.c_uint64]
-    E.emu_u32_job_cells.restype = c.c_uint
-    E.emu_u32_job_cells.argtypes = [V, V, V, c.c_uint]
-    E.emu_u32_no_problem.restype = c.c_uint64
-    E.emu_u32_problem_str.restype = c.c_char_p
-    E.emu_u32_problem_str.argtypes = [c.c_uint]
-    E.emu_u32_gate_rows.restype = None
-    E.emu_u32_gate_rows.argtypes = [V, c.c_uint64, V, c.c_uint64, V, c.c_uint, c.c_uint]
-    return E
-
-
-def vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
+    return build_emu("emu_u32", (("emu_u32_job_bytes", c.c_uint, []), ("emu_u32_row_columns", c.c_uint, []), ("emu_u32_kind_ops", c.c_uint, [c.c_uint]),
+                                 ("emu_u32_job_problem", c.c_uint, [V, c.c_uint64]), ("emu_u32_job_cells", c.c_uint, [V, V, V, c.c_uint]),
+                                 ("emu_u32_no_problem", c.c_uint64, []), ("emu_u32_problem_str", c.c_char_p, [c.c_uint]),
+                                 ("emu_u32_gate_rows", None, [V, c.c_uint64, V, c.c_uint64, V, c.c_uint, c.c_uint])))
 
 
 def make_jobs(items):
@@ -323,38 +296,12 @@ def test_entry_point_checks_its_pointers_first():
     holds (a valid job, a refused one, nothing), never a crash or another status"""
     import eth_lc_plonky2_amd as m
     lib = m.load_library()
-    buf = np.zeros(NW * 64, dtype=np.uint64)
     good, bad = make_jobs([(0, RANGE, 0, (1,))]), make_jobs(BAD_JOBS)
-    for mem in (m.MEM_HOST, m.MEM_DEVICE):
-        assert lib.lcp2_u32_gate_rows(None, vp(good), 1, mem, vp(buf), 64) == INVALID
-        assert lib.lcp2_u32_gate_rows(None, vp(bad), bad.size, mem, vp(buf), 64) == INVALID
-        assert lib.lcp2_u32_gate_rows(None, None, 0, mem, vp(buf), 64) == INVALID
-        assert lib.lcp2_u32_gate_rows(None, None, 1, mem, None, 64) == INVALID
-    assert not buf.any()
+    check_null_context(lambda a, mem, w: lib.lcp2_u32_gate_rows(None, *a, mem, w, 64), [(vp(good), 1), (vp(bad), bad.size), (None, 0)],
+                       (m.MEM_HOST, m.MEM_DEVICE), null_wires=(None, 1))
 
 
 # ------------------------------------------------------------------ on the GPU
-class DeviceMatrix:
-    """a [columns][n] matrix in HBM"""
-
-    def __init__(self, ctx, host):
-        self.ctx, self.shape = ctx, host.shape
-        self.ptr = ctx.buffer_alloc(host.size)
-        ctx.buffer_write(self.ptr, host)
-
-    def read(self):
-        return self.ctx.buffer_read(self.ptr, self.shape[0] * self.shape[1]).reshape(self.shape)
-
-    def free(self):
-        self.ctx.buffer_free(self.ptr)
-
-
-def upload_jobs(ctx, jobs):
-    ptr = ctx.buffer_alloc(jobs.size * 3)
-    ctx.buffer_write(ptr, np.ascontiguousarray(jobs).view(np.uint64))
-    return ptr
-
-
 @pytest.mark.gpu
 def test_refill_of_a_mix_circuit(gpu_ctx):
     """256 rows, every gate of the mix at least 16 times: from the witness with its u32 / comparison rows zeroed, one call with the
@@ -366,7 +313,7 @@ def test_refill_of_a_mix_circuit(gpu_ctx):
     assert all(int((gate_of_row == G[name]).sum()) >= 16 for name in GATE.values())
     jobs = ug.witness_jobs(wires, gate_of_row, G)
     zeroed, owned = zeroed_and_owned(wires, gate_of_row, G)
-    d_jobs = upload_jobs(gpu_ctx, jobs)
+    d_jobs = upload(gpu_ctx, jobs)
     for device_list in (False, True):
         dm = DeviceMatrix(gpu_ctx, zeroed)
         if device_list:
@@ -465,7 +412,7 @@ def test_refusals_on_the_device(gpu_ctx):
             gpu_ctx.u32_gate_rows(mixed, dm.ptr, n)
         assert e.value.status == INVALID
         # the same list in HBM: refused after the fact, the valid jobs are written and the bad one wrote nothing
-        d_jobs = upload_jobs(gpu_ctx, mixed)
+        d_jobs = upload(gpu_ctx, mixed)
         assert lib.lcp2_u32_gate_rows(gpu_ctx.handle, ctypes.c_void_p(d_jobs), mixed.size, m.MEM_DEVICE, ctypes.c_void_p(dm.ptr), n) == INVALID
         assert b"job %d" % at in lib.lcp2_last_error(gpu_ctx.handle)
         assert (dm.read() == want).all()
@@ -499,7 +446,7 @@ def test_two_refused_jobs_in_a_device_list(gpu_ctx, emu32):
         mixed = np.concatenate([good[:lo], first, good[lo:hi - 1], second, good[hi - 1:]])
         assert mixed.size == 600 and emu32.emu_u32_job_problem(vp(mixed[lo:lo + 1]), n) == 4 and emu32.emu_u32_job_problem(vp(mixed[hi:hi + 1]), n) == 1
         dm = DeviceMatrix(gpu_ctx, np.zeros((NW, n), dtype=np.uint64))
-        d_jobs = upload_jobs(gpu_ctx, mixed)
+        d_jobs = upload(gpu_ctx, mixed)
         assert lib.lcp2_u32_gate_rows(gpu_ctx.handle, ctypes.c_void_p(d_jobs), mixed.size, m.MEM_DEVICE, ctypes.c_void_p(dm.ptr), n) == INVALID
         reason = lib.lcp2_last_error(gpu_ctx.handle)
         assert b"job %d:" % lo in reason and emu32.emu_u32_problem_str(4) in reason and b"job %d:" % hi not in reason, reason

@@ -2,40 +2,25 @@
 reference of k_verify_paths, the FRI query k_verify_fri runs) and csrc/verify_head.hpp compiled for the CPU (tests/emu/emu_verify.cpp)
 and run over the jobs of the kernels.  Proofs come from the oracle prover, and the expected code of every case is orc_verify's."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib
 import verify_batch_cases as vc
+from rows_lib import build_emu, vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_verify.cpp")
-LIB = os.path.join(HERE, "emu", "libemu_verify.so")
-CSRC = os.path.join(HERE, "..", "eth-lc-plonky2_amd", "csrc")
-NONE = 0xFFFFFFFF
+NONE = 0xFFFFFFFF   # VQ_STATUS_NONE: a query without a status
 
 
 @pytest.fixture(scope="module")
 def emuv():
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("verify_query.hpp", "verify_head.hpp", "host_protocol.hpp", "gate_program.hpp", "poseidon.hpp", "gl64.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    E = ctypes.CDLL(LIB)
     c, V, U = ctypes, ctypes.c_void_p, ctypes.c_uint64
-    for name, res, args in (("emu_verify_status", c.c_uint, [c.c_uint, c.c_uint]), ("emu_verify_status_none", c.c_uint, []),
+    return build_emu("emu_verify", (("emu_verify_status", c.c_uint, [c.c_uint, c.c_uint]), ("emu_verify_status_none", c.c_uint, []),
                             ("emu_verify_ordinal", c.c_uint, [c.c_uint, c.c_uint]), ("emu_verify_reduce", c.c_uint, [V, c.c_uint]),
                             ("emu_verify_tree_status", c.c_uint, [V, c.c_uint]), ("emu_verify_num_trees", c.c_uint, [V]),
                             ("emu_merkle_path", c.c_int, [V, c.c_uint, U, V, c.c_uint, V]),
-                            ("emu_verify_batch", c.c_int, [V, V, V, V, U, U, V, U, V, V])):
-        getattr(E, name).restype, getattr(E, name).argtypes = res, args
-    return E
-
-
-def vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
+                            ("emu_verify_batch", c.c_int, [V, V, V, V, U, U, V, U, V, V])))
 
 
 def run_emu(E, m, name):

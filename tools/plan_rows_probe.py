@@ -13,22 +13,19 @@ Prints ONE JSON line and writes it to profiles/plan_rows_probe.json.
 import ctypes
 import json
 import os
-import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))   # rows_lib: the builder of the CPU emulations
 NW = 135
 
 
 def emulation():
-    src, lib = os.path.join(ROOT, "tests", "emu", "emu_plan.cpp"), os.path.join(ROOT, "tests", "emu", "libemu_plan.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, src], check=True)
-    E = ctypes.CDLL(lib)
+    from rows_lib import build_emu
     V, U = ctypes.c_void_p, ctypes.c_uint64
-    E.emu_plan_level.restype, E.emu_plan_level.argtypes = None, [V, U, U, V, U, V, U, U, V, U, V, ctypes.c_uint, U, V, U, ctypes.c_uint]
-    return E
+    return build_emu("emu_plan", [("emu_plan_level", None, [V, U, U, V, U, V, U, U, V, U, V, ctypes.c_uint, U, V, U, ctypes.c_uint])])
 
 
 def host_walk(E, plan, n):

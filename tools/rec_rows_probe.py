@@ -7,23 +7,20 @@ in Python integers (recursion_gates.run_plan) and in C++ (csrc/rec_rows.hpp comp
 import ctypes
 import json
 import os
-import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))   # rows_lib: the builder of the CPU emulations
 
 
 def host_cpp_ms(plan, n, reps):
     """the plan through rec_rows.hpp on one host thread, level by level (best of reps), and whether it gives the expected matrix"""
     import numpy as np
-    src, lib = os.path.join(ROOT, "tests", "emu", "emu_rec.cpp"), os.path.join(ROOT, "tests", "emu", "libemu_rec.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, src], check=True)
-    E = ctypes.CDLL(lib)
+    from rows_lib import build_emu, vp
     V, U = ctypes.c_void_p, ctypes.c_uint64
-    E.emu_rec_level.restype, E.emu_rec_level.argtypes = None, [V, U, U, V, U, V, ctypes.c_uint, U, V, ctypes.c_uint]
-    vp = lambda a: a.ctypes.data_as(V)   # noqa: E731
+    E = build_emu("emu_rec", [("emu_rec_level", None, [V, U, U, V, U, V, ctypes.c_uint, U, V, ctypes.c_uint])])
     best, same = None, True
     for _ in range(reps):
         got, flag = np.zeros((135, n), dtype=np.uint64), np.full(1, (1 << 64) - 1, dtype=np.uint64)
