@@ -74,19 +74,11 @@ __global__ __launch_bounds__(HASH_THREADS, 5) void k_hash_leaves(const u64 *__re
 #pragma unroll
   for (int j = 0; j < 12; j++) s[j] = 0;
   if (leaf_len <= 4) {  // hash_or_noop: short leaves are padded, not hashed
-    for (u32 c = 0; c < leaf_len; c++) s[c] = gl_canon(row[c * col_stride]);
-  } else {
-    for (u32 c0 = 0; c0 < leaf_len; c0 += 8) {
-      if (c0 + 8 <= leaf_len) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) s[j] = gl_canon(row[(u64)(c0 + j) * col_stride]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-          if (c0 + j < leaf_len) s[j] = gl_canon(row[(u64)(c0 + j) * col_stride]);
-      }
-      pos_permute(s, rc);
-    }
+    for (int c = 0; c < 4; c++)  // (static indices: the state stays in registers)
+      if (c < (int)leaf_len) s[c] = gl_canon(row[c * col_stride]);
+  } else {  // the lazy arithmetic of the permutation takes any u64: the words go in as they are
+    pos_sponge_absorb(s, leaf_len, rc, true, true, [&](u32 c0, int j) { return row[(u64)(c0 + j) * col_stride]; });
   }
   ulonglong2 *d = (ulonglong2 *)(digests + 4 * i);
   d[0] = make_ulonglong2(s[0], s[1]);
@@ -105,17 +97,7 @@ __global__ __launch_bounds__(HASH_THREADS, 5) void k_hash_leaves_absorb(const u6
   u64 s[12];
 #pragma unroll
   for (int j = 0; j < 12; j++) s[j] = first ? 0 : state[(u64)j * nleaves + i];
-  for (u32 c0 = 0; c0 < ncols; c0 += 8) {
-    if (c0 + 8 <= ncols) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) s[j] = gl_canon(row[(u64)(c0 + j) * col_stride]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        if (c0 + j < ncols) s[j] = gl_canon(row[(u64)(c0 + j) * col_stride]);
-    }
-    pos_permute(s, rc);
-  }
+  pos_sponge_absorb(s, ncols, rc, first != 0, last != 0, [&](u32 c0, int j) { return row[(u64)(c0 + j) * col_stride]; });
   if (last) {
     ulonglong2 *d = (ulonglong2 *)(digests + 4 * i);
     d[0] = make_ulonglong2(s[0], s[1]);
@@ -137,14 +119,11 @@ __global__ __launch_bounds__(HASH_THREADS, 5) void k_hash_ext_leaves(const u64 *
   for (int j = 0; j < 12; j++) s[j] = 0;
   u32 len = 2 * arity;
   if (len <= 4) {
-    for (u32 e = 0; e < arity; e++) { s[2 * e] = a[e]; s[2 * e + 1] = b[e]; }
-  } else {
-    for (u32 e0 = 0; e0 < arity; e0 += 4) {
 #pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (e0 + j < arity) { s[2 * j] = a[e0 + j]; s[2 * j + 1] = b[e0 + j]; }
-      pos_permute(s, rc);
-    }
+    for (int e = 0; e < 2; e++)
+      if (e < (int)arity) { s[2 * e] = a[e]; s[2 * e + 1] = b[e]; }
+  } else {
+    pos_sponge_absorb(s, len, rc, true, true, [&](u32 c0, int j) { return (j & 1) ? b[(c0 >> 1) + (j >> 1)] : a[(c0 >> 1) + (j >> 1)]; });
   }
   ulonglong2 *d = (ulonglong2 *)(digests + 4 * i);
   d[0] = make_ulonglong2(s[0], s[1]);
@@ -158,7 +137,8 @@ __global__ __launch_bounds__(HASH_THREADS) void k_merkle_level(const u64 *__rest
   const ulonglong2 *c = (const ulonglong2 *)(children + 8 * i);
   ulonglong2 c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
   u64 s[12] = {c0.x, c0.y, c1.x, c1.y, c2.x, c2.y, c3.x, c3.y, 0, 0, 0, 0};
-  pos_permute(s, rc);
+  pos_permute_body(s, rc, true);
+  pos_permute_tail<POS_TAIL_FINAL>(s);
   ulonglong2 *d = (ulonglong2 *)(parents + 4 * i);
   d[0] = make_ulonglong2(s[0], s[1]);
   d[1] = make_ulonglong2(s[2], s[3]);

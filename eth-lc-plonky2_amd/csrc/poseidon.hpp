@@ -38,7 +38,8 @@ constexpr int POS_ROUNDS = 30;
 constexpr int POS_GROUP = 3;                        // partial rounds per group
 constexpr int POS_GROUPS = POS_PARTIAL / POS_GROUP;  // 7 groups = 21 rounds, the 22nd runs as a plain round
 constexpr int POS_GROUP_CONSTS = 3 + 11;            // k1, k2, k3, kv[11]
-constexpr int POS_RC_WORDS = POS_ROUNDS * POS_W + POS_GROUPS * POS_GROUP_CONSTS;  // the device table: round constants, then the group constants
+constexpr int POS_RC_ZERO_CAP = POS_ROUNDS * POS_W + POS_GROUPS * POS_GROUP_CONSTS;  // offset of the four zero-capacity constants (below)
+constexpr int POS_RC_WORDS = POS_RC_ZERO_CAP + 4;  // the device table: round constants, the group constants, the zero-capacity constants
 
 struct PosPartialTables {
   u32 m00, ab, aAb;
@@ -185,16 +186,32 @@ inline void pos_extend_round_constants(u64 rc[POS_RC_WORDS]) {
     }
     k[0] = c1[0]; k[1] = k2; k[2] = k3;
   }
+  // A sponge starts with capacity words 8..11 equal to zero: what leaves their S-boxes in round 0 is rc[8..11]^7, whatever is absorbed
+  for (int i = 0; i < POS_W - POS_RATE; i++) rc[POS_RC_ZERO_CAP + i] = gl_canon(pos_sbox(rc[POS_RATE + i]));
 }
 
-// The grouped form in portable arithmetic (what the gfx950 form computes, on canonical values): tests/emu checks it against the
-// plain definition above and the oracle.  rc: POS_RC_WORDS words (pos_derive_round_constants + pos_extend_round_constants).
-LCP2_HD void pos_permute_grouped_portable(u64 s[12], const u64 *__restrict__ rc) {
+// ---- The permutation in two parts, for the sponges --------------------------------------------------------------------------
+// Every sponge here is plonky2's overwrite-mode sponge: the next absorption overwrites state words 0..m-1 (m <= 8) and only the
+// rest of the state survives; after the last permutation words 0..3 are squeezed.  So the permutation is cut after its last S-box
+// layer: the body is shared, and the last linear layer (the tail) computes, folds and canonicalises only the rows of a
+// compile-time mask (bit r = row r).  Rows outside the mask hold nothing the caller may read.
+constexpr u32 POS_TAIL_FINAL = 0x00F;     // the last permutation of a sponge: rows 0..3 are squeezed
+constexpr u32 POS_TAIL_CAPACITY = 0xF00;  // the next absorption overwrites all 8 rate words: rows 8..11 survive
+constexpr u32 POS_TAIL_FULL = 0xFFF;      // the next chunk is ragged (m < 8 words): some rate rows survive too
+// zero_cap (body): state words 8..11 are zero on entry (the first permutation of a sponge), so round 0 takes the outputs of their
+// four S-boxes from the table (POS_RC_ZERO_CAP).
+
+// The two parts in portable arithmetic, on the grouped form below: what the CPU emulation of the sponge kernels runs.  Compiled
+// for the CPU the tail sets the rows outside its mask to a poison word, so a sponge that read one would give a wrong digest.
+constexpr u64 POS_POISON = 0xFFFFFFFF5EEDDEADull;
+// rc: POS_RC_WORDS words (pos_derive_round_constants + pos_extend_round_constants).  s: any u64 values in; on return what leaves the
+// last S-box layer.
+LCP2_HD void pos_permute_body_portable(u64 s[12], const u64 *__restrict__ rc, bool zero_cap) {
   constexpr PosPartialTables T = pos_partial_tables();
   for (int i = 0; i < 12; i++) s[i] = gl_add(gl_canon(s[i]), rc[i]);
   int round = 0;
   for (int r = 0; r < POS_FULL_HALF; r++, round++) {
-    for (int i = 0; i < 12; i++) s[i] = gl_canon(pos_sbox(s[i]));
+    for (int i = 0; i < 12; i++) s[i] = zero_cap && r == 0 && i >= POS_RATE ? rc[POS_RC_ZERO_CAP + i - POS_RATE] : gl_canon(pos_sbox(s[i]));
     pos_mds(s);
     for (int i = 0; i < 12; i++) s[i] = gl_add(gl_canon(s[i]), rc[(round + 1) * 12 + i]);
   }
@@ -226,11 +243,31 @@ LCP2_HD void pos_permute_grouped_portable(u64 s[12], const u64 *__restrict__ rc)
     pos_mds(s);
     for (int i = 0; i < 12; i++) s[i] = gl_add(gl_canon(s[i]), rc[(round + 1) * 12 + i]);
   }
-  for (int r = 0; r < POS_FULL_HALF; r++, round++) {
+  for (int r = 0; r < POS_FULL_HALF - 1; r++, round++) {
     for (int i = 0; i < 12; i++) s[i] = gl_canon(pos_sbox(s[i]));
     pos_mds(s);
-    for (int i = 0; i < 12; i++) s[i] = round + 1 < POS_ROUNDS ? gl_add(gl_canon(s[i]), rc[(round + 1) * 12 + i]) : gl_canon(s[i]);
+    for (int i = 0; i < 12; i++) s[i] = gl_add(gl_canon(s[i]), rc[(round + 1) * 12 + i]);
   }
+  for (int i = 0; i < 12; i++) s[i] = gl_canon(pos_sbox(s[i]));
+}
+template <u32 MASK>
+LCP2_HD void pos_mds_tail_portable(u64 s[12]) {
+  u64 t[12];
+  for (int i = 0; i < 12; i++) t[i] = s[i];
+  pos_mds(t);
+  for (int r = 0; r < 12; r++) {
+    if ((MASK >> r) & 1) s[r] = gl_canon(t[r]);
+#if !defined(__HIPCC__)
+    else s[r] = POS_POISON;
+#endif
+  }
+}
+
+// The grouped form in portable arithmetic (what the gfx950 form computes, on canonical values): tests/emu checks it against the
+// plain definition above and the oracle.  rc: POS_RC_WORDS words (pos_derive_round_constants + pos_extend_round_constants).
+LCP2_HD void pos_permute_grouped_portable(u64 s[12], const u64 *__restrict__ rc) {
+  pos_permute_body_portable(s, rc, false);
+  pos_mds_tail_portable<POS_TAIL_FULL>(s);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -485,8 +522,10 @@ __device__ __forceinline__ void pos_partial3_h(u32 lo[12], u32 hi[12], const u64
   pos_partial3_core(lo, hi, kc, [&](int, u32 &ul, u32 &uh) { pos_sbox_h(ul, uh); });
 }
 
-// rc: POS_RC_WORDS words (the 360 round constants, then the group constants of the partial rounds)
-__device__ __forceinline__ void pos_permute_gfx950(u64 s[12], const u64 *__restrict__ rc) {
+// The body: everything up to and including the last S-box layer.  rc: POS_RC_WORDS words (the 360 round constants, the group constants
+// of the partial rounds, the zero-capacity constants).  s: any u64 values in; on return the lazy outputs of the last S-box layer.
+// zero_cap is wave-uniform: one scalar branch in round 0 skips the S-boxes of lanes 8..11.
+__device__ __forceinline__ void pos_permute_body_gfx950(u64 s[12], const u64 *__restrict__ rc, bool zero_cap) {
   u32 lo[12], hi[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) { u64 v = gl_add_nc(s[i], rc[i]); lo[i] = (u32)v; hi[i] = (u32)(v >> 32); }
@@ -494,7 +533,14 @@ __device__ __forceinline__ void pos_permute_gfx950(u64 s[12], const u64 *__restr
 #pragma unroll 1
   for (int r = 0; r < POS_FULL_HALF; r++, round++) {
 #pragma unroll
-    for (int i = 0; i < 12; i++) pos_sbox_h(lo[i], hi[i]);
+    for (int i = 0; i < POS_RATE; i++) pos_sbox_h(lo[i], hi[i]);
+    if (zero_cap && r == 0) {
+#pragma unroll
+      for (int i = POS_RATE; i < 12; i++) { const u64 k = rc[POS_RC_ZERO_CAP + i - POS_RATE]; lo[i] = (u32)k; hi[i] = (u32)(k >> 32); }
+    } else {
+#pragma unroll
+      for (int i = POS_RATE; i < 12; i++) pos_sbox_h(lo[i], hi[i]);
+    }
     pos_mds_h(lo, hi, rc + (round + 1) * 12);
   }
 #pragma unroll 1
@@ -511,10 +557,31 @@ __device__ __forceinline__ void pos_permute_gfx950(u64 s[12], const u64 *__restr
     pos_mds_h(lo, hi, rc + (round + 1) * 12);
   }
 #pragma unroll
-  for (int i = 0; i < 12; i++) pos_sbox_h(lo[i], hi[i]);
-  pos_mds_h(lo, hi, nullptr);
+  for (int i = 0; i < 12; i++) { pos_sbox_h(lo[i], hi[i]); s[i] = ((u64)hi[i] << 32) | lo[i]; }
+}
+// The tail: the rows of the last linear layer that MASK names, canonical; the other words of s are left as they are.
+template <u32 MASK>
+__device__ __forceinline__ void pos_mds_tail(u64 s[12]) {
+  u32 lo[12], hi[12];
 #pragma unroll
-  for (int i = 0; i < 12; i++) s[i] = gl_canon(((u64)hi[i] << 32) | lo[i]);
+  for (int i = 0; i < 12; i++) { lo[i] = (u32)s[i]; hi[i] = (u32)(s[i] >> 32); }
+  pos_static_for<12>([&](auto rr) {
+    constexpr int r = decltype(rr)::value;
+    if constexpr ((MASK >> r) & 1) {
+      u32 l[12], h[12], nl, nh;
+#pragma unroll
+      for (int i = 0; i < 12; i++) { l[i] = lo[(i + r) % 12]; h[i] = hi[(i + r) % 12]; }
+      u64 al, ah;
+      pos_mds_row<r == 0>(l, h, 0, 0, al, ah);
+      pos_fold_h(al, ah, nl, nh);
+      s[r] = gl_canon(((u64)nh << 32) | nl);
+    }
+  });
+}
+// The whole permutation: any u64 values in, canonical out
+__device__ __forceinline__ void pos_permute_gfx950(u64 s[12], const u64 *__restrict__ rc) {
+  pos_permute_body_gfx950(s, rc, false);
+  pos_mds_tail<POS_TAIL_FULL>(s);
 }
 
 // ---- lane-cooperative permutation: a 16-lane group holds one state, lane j < 12 owns element j (lanes 12..15 ride
@@ -589,6 +656,51 @@ LCP2_HD void pos_permute(u64 s[12], const u64 *__restrict__ rc) {
 #else
   pos_permute_portable(s, rc);
 #endif
+}
+LCP2_HD void pos_permute_body(u64 s[12], const u64 *__restrict__ rc, bool zero_cap) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  pos_permute_body_gfx950(s, rc, zero_cap);
+#else
+  pos_permute_body_portable(s, rc, zero_cap);
+#endif
+}
+template <u32 MASK>
+LCP2_HD void pos_permute_tail(u64 s[12]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  pos_mds_tail<MASK>(s);
+#else
+  pos_mds_tail_portable<MASK>(s);
+#endif
+}
+
+// The overwrite-mode sponge of the leaf kernels over the words load(c0, j) = word c0 + j of the input (c0 a multiple of 8, j < 8),
+// len >= 1 of them: s is the state on entry (zero_cap: all zero, the sponge starts here) and, on return, rows 0..3 after the last
+// permutation if the sponge ends with these words (finish), the whole state if more words follow (len is then a multiple of 8).
+// One call site of the body, so the kernel holds the rolled rounds once; each tail stands in a branch of its own with the loads
+// of the next chunk, which overwrite exactly the rows that tail left out.  All arguments but load's words are wave-uniform.
+template <class Load>
+LCP2_HD void pos_sponge_absorb(u64 s[12], u32 len, const u64 *__restrict__ rc, bool zero_cap, bool finish, Load load) {
+#pragma unroll
+  for (int j = 0; j < POS_RATE; j++)
+    if (len >= POS_RATE || j < (int)len) s[j] = load(0u, j);
+  for (u32 c0 = POS_RATE;; c0 += POS_RATE) {
+    pos_permute_body(s, rc, zero_cap && c0 == POS_RATE);
+    if (c0 >= len && finish) {
+      pos_permute_tail<POS_TAIL_FINAL>(s);
+      return;
+    }
+    if (c0 + POS_RATE <= len) {
+      pos_permute_tail<POS_TAIL_CAPACITY>(s);
+#pragma unroll
+      for (int j = 0; j < POS_RATE; j++) s[j] = load(c0, j);
+    } else {  // a ragged chunk follows, or (c0 >= len) nothing in this call
+      pos_permute_tail<POS_TAIL_FULL>(s);
+#pragma unroll
+      for (int j = 0; j < POS_RATE; j++)
+        if (c0 + j < len) s[j] = load(c0, j);
+      if (c0 >= len) return;
+    }
+  }
 }
 
 // ---- round-constant derivation (host side; uploaded to the device once) ----
