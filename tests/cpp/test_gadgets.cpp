@@ -830,15 +830,21 @@ static void test_wrap_chain_tampered_inner_panics() { wrap_chain(wrap_first(), w
 // the outputs-only generator of a PoseidonGate row (what generate_witness_gpu runs on the host; the row itself is filled on the device)
 // against the full row generator and the oracle's permutation, swap included, non-canonical inputs included; and the full row
 // generator (the AVX2 MDS layer where the CPU has it) against the text it shares with the device (csrc/pos_rows.hpp) run with the
-// portable layer pos_mds, every one of the 135 cells
+// portable layer pos_mds, every one of the 135 cells.  Six statements of the permutation must agree word for word: the host's grouped
+// walk with the portable layers and with the AVX2 layers, the plain definition pos_permute_portable, the row text, poseidon_gate_row,
+// the oracle.  Inputs: the edge words rotated through all 12 positions, all 2^64 - 1, all zero (each with both
+// swap flags), then the random draws.
 static void test_poseidon_gate_outputs_match_rows() {
   static lcp2::u64 rc[lcp2::POS_ROUNDS * lcp2::POS_W];
   lcp2::pos_derive_round_constants(rc);
   uint64_t seed = 12345;
   auto rnd = [&]() { seed = seed * 6364136223846793005ull + 1442695040888963407ull; uint64_t z = seed; z ^= z >> 29; z *= 0xBF58476D1CE4E5B9ull; return z ^ (z >> 32); };
-  for (int t = 0; t < 500; t++) {
+  const F P = GOLDILOCKS_P, edge[8] = {0, 1, P - 1, P, P + 1, 0xFFFFFFFFull, 1ull << 32, ~0ull};
+  const int edge_cases = 2 * (12 + 2);
+  for (int t = -edge_cases; t < 500; t++) {
     F in[12], row[POS_GATE_WIRES], out[12];
-    for (auto &x : in) x = t < 4 ? (t == 0 ? 0 : t == 1 ? GOLDILOCKS_P - 1 : ~0ull) : rnd();
+    const int e = (t + edge_cases) / 2;  // edge case e < 14 with swap = 0 and 1
+    for (int i = 0; i < 12; i++) in[i] = t < 0 ? (e < 12 ? edge[(i + e) % 8] : e == 12 ? ~0ull : 0) : t < 4 ? (t == 0 ? 0 : t == 1 ? P - 1 : ~0ull) : rnd();
     const bool swap = t & 1;
     F out_portable[12];
     poseidon_gate_row(in, swap, row);
@@ -850,15 +856,19 @@ static void test_poseidon_gate_outputs_match_rows() {
     if (stores != POS_GATE_WIRES) throw std::runtime_error("pos_row_cells does not store 135 cells");
     for (uint32_t c = 0; c < POS_GATE_WIRES; c++)
       if (row[c] != shared[c]) throw std::runtime_error("poseidon_gate_row differs from the shared row text at case " + std::to_string(t) + ", column " + std::to_string(c));
-    poseidon_gate_outputs(in, swap, out);                         // AVX2 linear layers where the CPU has them
-    poseidon_gate_outputs_impl(in, swap, out_portable, true);     // 128-bit multiply-accumulates
-    for (int i = 0; i < 12; i++) if (out[i] != out_portable[i]) throw std::runtime_error("poseidon_gate_outputs: AVX2 and portable paths differ");
+    poseidon_gate_outputs(in, swap, out);                         // the grouped walk, AVX2 layers where the CPU has them
+    poseidon_gate_outputs_impl(in, swap, out_portable, true);     // the grouped walk, 128-bit multiply-accumulates
+    for (int i = 0; i < 12; i++) if (out[i] != out_portable[i]) throw std::runtime_error("poseidon_gate_outputs: AVX2 and portable paths differ at case " + std::to_string(t));
     uint64_t s[12];
+    lcp2::u64 plain[12];
     for (int i = 0; i < 12; i++) s[i] = in[i] % GOLDILOCKS_P;
     if (swap) for (int i = 0; i < 4; i++) std::swap(s[i], s[i + 4]);
+    for (int i = 0; i < 12; i++) plain[i] = s[i];
+    lcp2::pos_permute_portable(plain, rc);                        // the plain definition
     orc_poseidon_permute(s);
     for (int i = 0; i < 12; i++)
-      if (row[POS_WIRE_OUTPUT + i] != out[i] || out[i] != s[i]) throw std::runtime_error("poseidon_gate_outputs differs from the row generator / the oracle at case " + std::to_string(t));
+      if (row[POS_WIRE_OUTPUT + i] != out[i] || out[i] != s[i] || plain[i] != s[i])
+        throw std::runtime_error("poseidon_gate_outputs differs from the row generator / the plain definition / the oracle at case " + std::to_string(t));
   }
 }
 

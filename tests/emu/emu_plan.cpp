@@ -3,15 +3,9 @@
 // one-lane-per-chain reference form of k_pos_plan_chains) as loops over lanes, with the two flag words of row_flag.hpp.
 // Built by tests/test_plan_rows.py with g++ and included by tests/emu/sanitize_plan_main.cpp; never loaded by the package.
 #include "../../eth-lc-plonky2_amd/csrc/pos_plan.hpp"
+#include "emu_rc.hpp"
 
 using namespace lcp2;
-
-static const u64 *plan_round_constants() {
-  static u64 rc[POS_ROUNDS * POS_W];
-  static bool ready = false;
-  if (!ready) { pos_derive_round_constants(rc); ready = true; }
-  return rc;
-}
 
 extern "C" {
 
@@ -54,7 +48,7 @@ void emu_plan_level(const RecJobDev *rec, unsigned long long rec_begin, unsigned
     }
   for (u64 c = chain_begin; c < chain_end; c++) {
     const u64 refusal = pos_plan_chain_lane(pos, npos, chain_ends, chain_begin, chain_end, c, operands, noperands, wires, ncols, n,
-                                            plan_round_constants(), flags, gate);
+                                            emu_round_constants(), flags, gate);
     if (!refusal) continue;
     if (refusal < flags[1]) flags[1] = refusal;
     if (row_refusal(rec_end + shift, ROW_OTHER_FAMILY) < flags[0]) flags[0] = row_refusal(rec_end + shift, ROW_OTHER_FAMILY);

@@ -2,15 +2,9 @@
 // (lcp2_poseidon_gate_rows), the validation of the entry point, and the kernel's grid as a loop over lanes.
 // Built by tests/test_pos_rows.py with g++; never loaded by the package.
 #include "../../eth-lc-plonky2_amd/csrc/pos_rows.hpp"
+#include "emu_rc.hpp"
 
 using namespace lcp2;
-
-static const u64 *round_constants() {
-  static u64 rc[POS_ROUNDS * POS_W];
-  static bool ready = false;
-  if (!ready) { pos_derive_round_constants(rc); ready = true; }
-  return rc;
-}
 
 extern "C" {
 
@@ -21,7 +15,7 @@ unsigned emu_pos_row_problem(const PoseidonRowDev *job, unsigned long long n) { 
 // the cells of one job in the order the kernel stores them: returns their number (at most `cap` are recorded)
 unsigned emu_pos_row_cells(const PoseidonRowDev *job, unsigned *cols, unsigned long long *vals, unsigned cap) {
   unsigned count = 0;
-  pos_row_cells(job->in, job->swap != 0, round_constants(), [](u64 *s) { pos_mds(s); }, [&](u32 col, u64 v) {
+  pos_row_cells(job->in, job->swap != 0, emu_round_constants(), [](u64 *s) { pos_mds(s); }, [&](u32 col, u64 v) {
     if (count < cap) { cols[count] = col; vals[count] = v; }
     count++;
   });
@@ -32,7 +26,7 @@ unsigned emu_pos_row_cells(const PoseidonRowDev *job, unsigned *cols, unsigned l
 void emu_pos_gate_rows(const PoseidonRowDev *rows, unsigned long long nrows, unsigned long long *wires, unsigned long long n,
                        unsigned blocks, unsigned threads) {
   for (unsigned b = 0; b < blocks; b++)
-    for (unsigned t = 0; t < threads; t++) pos_rows_lane(rows, nrows, (u64)b * threads + t, wires, n, round_constants());
+    for (unsigned t = 0; t < threads; t++) pos_rows_lane(rows, nrows, (u64)b * threads + t, wires, n, emu_round_constants());
 }
 
 }  // extern "C"

@@ -2,27 +2,20 @@
 // pos_permute_tail) compiled for the CPU, each kernel of csrc/kernels_hash.hip as a loop over its lanes.  In this build a tail sets
 // the rows outside its mask to POS_POISON, so a sponge that read a row its tail left out gives a wrong digest here.
 // Built by tests/test_sponge_tails.py with g++; never loaded by the package.
-#include "../../eth-lc-plonky2_amd/csrc/poseidon.hpp"
+#include "emu_rc.hpp"
 
 using namespace lcp2;
 
-static const u64 *sponge_round_constants() {
-  static u64 rc[POS_RC_WORDS];
-  static bool ready = false;
-  if (!ready) { pos_derive_round_constants(rc); pos_extend_round_constants(rc); ready = true; }
-  return rc;
-}
-
 extern "C" {
 
-const unsigned long long *emu_sponge_round_constants() { return sponge_round_constants(); }
+const unsigned long long *emu_sponge_round_constants() { return emu_round_constants(); }
 unsigned emu_sponge_rc_words() { return POS_RC_WORDS; }
 unsigned emu_sponge_rc_zero_cap() { return POS_RC_ZERO_CAP; }
 
 // k_hash_leaves
 void emu_hash_leaves(const unsigned long long *data, unsigned long long leaf_stride, unsigned long long col_stride, unsigned leaf_len,
                      unsigned long long nleaves, unsigned long long *digests) {
-  const u64 *rc = sponge_round_constants();
+  const u64 *rc = emu_round_constants();
   for (u64 i = 0; i < nleaves; i++) {
     const u64 *row = data + i * leaf_stride;
     u64 s[12] = {0};
@@ -38,7 +31,7 @@ void emu_hash_leaves(const unsigned long long *data, unsigned long long leaf_str
 // k_hash_leaves_absorb: one chunk of the columns, the state [12][nleaves] kept between calls
 void emu_hash_leaves_absorb(const unsigned long long *data, unsigned long long col_stride, unsigned ncols, unsigned long long nleaves,
                             unsigned long long *state, unsigned first, unsigned last, unsigned long long *digests) {
-  const u64 *rc = sponge_round_constants();
+  const u64 *rc = emu_round_constants();
   for (u64 i = 0; i < nleaves; i++) {
     const u64 *row = data + i;
     u64 s[12];
@@ -52,7 +45,7 @@ void emu_hash_leaves_absorb(const unsigned long long *data, unsigned long long c
 // k_hash_ext_leaves
 void emu_hash_ext_leaves(const unsigned long long *p0, const unsigned long long *p1, unsigned arity, unsigned long long nleaves,
                          unsigned long long *digests) {
-  const u64 *rc = sponge_round_constants();
+  const u64 *rc = emu_round_constants();
   for (u64 i = 0; i < nleaves; i++) {
     const u64 *a = p0 + i * arity, *b = p1 + i * arity;
     u64 s[12] = {0};
@@ -68,7 +61,7 @@ void emu_hash_ext_leaves(const unsigned long long *p0, const unsigned long long 
 
 // k_merkle_level
 void emu_merkle_level(const unsigned long long *children, unsigned long long *parents, unsigned long long nparents) {
-  const u64 *rc = sponge_round_constants();
+  const u64 *rc = emu_round_constants();
   for (u64 i = 0; i < nparents; i++) {
     u64 s[12] = {0};
     for (int j = 0; j < 8; j++) s[j] = children[8 * i + j];

@@ -5,15 +5,9 @@
 // tests/emu/sanitize_verify_main.cpp; never loaded by the package.
 #include <vector>
 #include "../../eth-lc-plonky2_amd/csrc/verify_head.hpp"
+#include "emu_rc.hpp"
 
 using namespace lcp2;
-
-static const u64 *verify_round_constants() {
-  static u64 rc[POS_ROUNDS * POS_W];
-  static bool ready = false;
-  if (!ready) { pos_derive_round_constants(rc); ready = true; }
-  return rc;
-}
 
 // the jobs of the two query kernels for one proof whose challenge block is `c`: status[num_queries]
 static void emu_query_jobs(const VqLayout &V, const VqChallenge &c, const u64 *proof, const u64 *cs_cap, u32 *status) {
@@ -21,7 +15,7 @@ static void emu_query_jobs(const VqLayout &V, const VqChallenge &c, const u64 *p
   if (!c.live) return;
   for (u32 t = 0; t < V.num_trees; t++)  // tree-major, as the kernel numbers its groups
     for (u32 q = 0; q < V.num_queries; q++) {
-      const u32 s = vq_path_job(V, c, proof, cs_cap, q, t, verify_round_constants());
+      const u32 s = vq_path_job(V, c, proof, cs_cap, q, t, emu_round_constants());
       if (s < status[q]) status[q] = s;
     }
   for (u32 q = 0; q < V.num_queries; q++) {
@@ -45,7 +39,7 @@ unsigned emu_verify_num_trees(const lcp2_params *p) { return vq_make_layout(Proo
 
 int emu_merkle_path(const unsigned long long *leaf, unsigned leaf_len, unsigned long long index, const unsigned long long *siblings, unsigned nsib,
                     const unsigned long long *cap) {
-  return vq_merkle_path(leaf, leaf_len, index, siblings, nsib, cap, verify_round_constants()) ? 1 : 0;
+  return vq_merkle_path(leaf, leaf_len, index, siblings, nsib, cap, emu_round_constants()) ? 1 : 0;
 }
 
 // lcp2_verify_batch on the CPU: failed_checks[count], and (nullable) the status words [count][num_query_rounds] of the proofs that

@@ -3,6 +3,7 @@
 // refused jobs.
 #include <vector>
 #include "sanitize_common.hpp"
+#include "emu_rc.hpp"
 #include "../../eth-lc-plonky2_amd/csrc/pos_rows.hpp"
 #include "../../eth-lc-plonky2_amd/csrc/u32_rows.hpp"
 
@@ -17,8 +18,7 @@ void emu_u32_gate_rows(const U32JobDev *jobs, unsigned long long njobs, unsigned
 }
 
 int main() {
-  static u64 rc[POS_ROUNDS * POS_W];
-  pos_derive_round_constants(rc);
+  const u64 *rc = emu_round_constants();
   const u64 TAG = ~0ull - 1, edge[4] = {0, GL_P - 1, GL_P, ~0ull};
   std::vector<PoseidonRowDev> rows;
   for (u32 swap = 0; swap < 2; swap++)

@@ -26,7 +26,7 @@ static void level(const Plan &p, u64 rb, u64 re, u64 cb, u64 ce, std::vector<u64
 
 int main() {
   const u64 n = 64, NONE = ROW_NO_PROBLEM, edge[5] = {0, GL_P - 1, ~0ull, GL_P, 1};
-  const u64 *rc = plan_round_constants();
+  const u64 *rc = emu_round_constants();
   // ---- random chains on rows 8.., CELL sources in rows 0..7
   std::vector<u64> w(POS_GATE_WIRES * n);
   for (u64 c = 0; c < POS_GATE_WIRES; c++)

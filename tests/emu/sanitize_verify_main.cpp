@@ -15,7 +15,7 @@ static u64 rnd_gl() { return rnd() % GL_P; }  // a canonical field element
 struct Tree {
   std::vector<std::vector<u64>> levels;
   void build(const std::vector<u64> &leaves, u32 nleaves, u32 leaf_len, u32 cap_height) {
-    const u64 *rc = verify_round_constants();
+    const u64 *rc = emu_round_constants();
     levels.assign(1, std::vector<u64>(4 * nleaves));
     for (u32 i = 0; i < nleaves; i++) vq_hash_or_noop(&leaves[(size_t)i * leaf_len], leaf_len, &levels[0][4 * i], rc);
     for (u32 n = nleaves; n > (1u << cap_height); n >>= 1) {
@@ -89,7 +89,7 @@ int main() {
   u32 status[3];
   u32 paths = 0;
   for (u32 t = 0; t < V.num_trees; t++)
-    for (u32 q = 0; q < Q; q++, paths++) CHECK(vq_path_job(V, c, proof.data(), cs_cap.data(), q, t, verify_round_constants()) == VQ_STATUS_NONE);
+    for (u32 q = 0; q < Q; q++, paths++) CHECK(vq_path_job(V, c, proof.data(), cs_cap.data(), q, t, emu_round_constants()) == VQ_STATUS_NONE);
   emu_query_jobs(V, c, proof.data(), cs_cap.data(), status);
   CHECK(status[0] == VQ_STATUS_NONE);  // query 0 is consistent down to the final polynomial
   CHECK(status[1] == vq_status(vq_ord_consistency(0), VQ_CHECK_CONSISTENCY) && status[2] == status[1] && vq_reduce_statuses(status, Q) == 5);
