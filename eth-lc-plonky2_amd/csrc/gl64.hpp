@@ -126,6 +126,41 @@ __device__ __forceinline__ void gl_mul_halves(u32 a0, u32 a1, u32 b0, u32 b1, u3
   r0 = (u32)q;
   r1 = (u32)(q >> 32);
 }
+// The same multiply WITHOUT the borrow correction of t = lo - hi1, for callers that can repeat their work.  The borrow needs
+// lo < hi1 < 2^32 (lo1 = 0 and p0 < hi1): one random operand pair in 2^32, yet the select and the multiply-add that apply it are 2 of
+// the 12 heavy instructions of every multiply.  Here the borrow leaves v_subbrev_co (VOP3 encoding) in an SGPR pair instead: one
+// bit per lane, zero for inactive lanes.  borrow == 0: (r1:r0) is what gl_mul_halves gives, bit for bit.  borrow != 0: the lanes
+// of the mask hold a wrong number (nothing can fault) and the caller recomputes with gl_mul_halves; see pos_sbox_h (poseidon.hpp),
+// which tests the OR of four masks with one scalar branch.  10 heavy instructions and 2 moves.  The mask is read by scalar
+// instructions only, which the hardware interlocks against the VALU write (hipcc pads nothing between a v_cmp that writes an SGPR
+// pair and the s_cmp / s_or that reads it).
+__device__ __forceinline__ void gl_mul_halves_spec(u32 a0, u32 a1, u32 b0, u32 b1, u32 &r0, u32 &r1, u64 &borrow /* wave-uniform */) {
+  const u64 p = (u64)a0 * b0;
+  const u64 t = (u64)a0 * b1 + (p >> 32);
+  u64 u;
+  u32 c;
+  asm("v_mad_u64_u32 %0, vcc, %2, %3, %4\n\t"
+      "s_nop 1\n\t"
+      "v_cndmask_b32_e64 %1, 0, 1, vcc"
+      : "=&v"(u), "=&v"(c) : "v"(a1), "v"(b0), "v"(t) : "vcc");
+  const u64 v = (u64)a1 * b1 + (((u64)c << 32) | (u32)(u >> 32));
+  const u32 p0 = (u32)p, lo1 = (u32)u, hi0 = (u32)v, hi1 = (u32)(v >> 32);
+  u32 t0, t1;
+  asm("v_sub_co_u32 %0, vcc, %3, %4\n\t"
+      "s_nop 1\n\t"
+      "v_subbrev_co_u32_e64 %1, %2, 0, %5, vcc"
+      : "=&v"(t0), "=&v"(t1), "=s"(borrow) : "v"(p0), "v"(hi1), "v"(lo1) : "vcc");
+  u64 r = ((u64)t1 << 32) | t0;
+  u32 c2;
+  asm("v_mad_u64_u32 %0, vcc, %2, -1, %0\n\t"
+      "s_nop 1\n\t"
+      "v_cndmask_b32_e64 %1, 0, 1, vcc"
+      : "+v"(r), "=&v"(c2) : "v"(hi0) : "vcc");
+  u64 q;
+  asm("v_mad_u64_u32 %0, vcc, %1, -1, %2" : "=v"(q) : "v"(c2), "v"(r) : "vcc");
+  r0 = (u32)q;
+  r1 = (u32)(q >> 32);
+}
 #endif
 
 LCP2_HD u64 gl_mul_nc(u64 a, u64 b) {

@@ -277,15 +277,35 @@ LCP2_HD void pos_permute_grouped_portable(u64 s[12], const u64 *__restrict__ rc)
 // products and conditional corrections are v_mad_u64_u32 / v_mad_i64_i32 (gl_mul_halves, gl64.hpp: 12 + 2 moves per multiply; the
 // compiler's own lowering of a 64x64 multiply + reduction is 27).  hipcc pads nothing inside an asm string, so the wait states it
 // emits itself for the same pairs on gfx950 (a VALU write of vcc -> any VALU read of it: 2) are written out as s_nop 1 here;
-// tools/check_hazards.py checks the built library.
+// tools/check_hazards.py checks the built library.  The S-box multiplies with gl_mul_halves_spec (10 + 2 moves: the 2^-32 borrow of the
+// reduction is tested once per S-box by a scalar branch, not corrected in every lane: pos_sbox_h).
 // All values are lazy (any u64 congruent to the element); the final state is canonicalised.
 
-__device__ __forceinline__ void pos_sbox_h(u32 &x0, u32 &x1) {
+__device__ __forceinline__ void pos_sbox_exact_h(u32 &x0, u32 &x1) {
   u32 a0, a1, b0, b1, c0, c1;
   gl_mul_halves(x0, x1, x0, x1, a0, a1);  // x^2
   gl_mul_halves(a0, a1, a0, a1, b0, b1);  // x^4
   gl_mul_halves(x0, x1, a0, a1, c0, c1);  // x^3
   gl_mul_halves(c0, c1, b0, b1, x0, x1);  // x^7
+}
+// The S-box of every kernel: the four multiplies run without the borrow correction of their reduction (gl_mul_halves_spec: 10 heavy
+// instructions instead of 12), their borrow masks are OR-ed by scalar instructions, and ONE scalar branch per S-box guards the cold
+// path, which recomputes the S-box from its kept input with the exact multiply for the whole wave.  A lane borrows in one multiply
+// of 2^32, so the cold path runs about once in 2^24 S-boxes of a wave; the result is bit for bit that of pos_sbox_exact_h whichever
+// lanes take it (tests/test_rare_borrow.py plants them).  The price: the input stays live to the end (2 VGPRs) and an SGPR pair.
+__device__ __forceinline__ void pos_sbox_h(u32 &x0, u32 &x1) {
+  u32 a0, a1, b0, b1, c0, c1, d0, d1;
+  u64 m0, m1, m2, m3;
+  gl_mul_halves_spec(x0, x1, x0, x1, a0, a1, m0);  // x^2
+  gl_mul_halves_spec(a0, a1, a0, a1, b0, b1, m1);  // x^4
+  gl_mul_halves_spec(x0, x1, a0, a1, c0, c1, m2);  // x^3
+  gl_mul_halves_spec(c0, c1, b0, b1, d0, d1, m3);  // x^7
+  if (__builtin_expect((m0 | m1 | m2 | m3) != 0, 0)) {
+    pos_sbox_exact_h(x0, x1);
+  } else {
+    x0 = d0;
+    x1 = d1;
+  }
 }
 
 // al + ah * 2^32 (al, ah < 2^42) -> lazy 64-bit value:  t = al + ah_hi * (2^64 mod p) ;  v = t + (ah_lo << 32), on carry += 2^32 - 1

@@ -4,6 +4,9 @@ tools/ubench/int_rates (profiles/r02_ubench_int_rates.txt): the opcode-weighted 
 
 The permutation inside k_poseidon_permute_batch is three rolled loops (4 full rounds, 7 groups of three partial rounds, 3 full rounds), one peeled partial round and an
 unrolled last round; the loops are found as backward s_cbranch edges and their bodies are multiplied by the trip counts.
+The cold paths of the S-boxes (pos_sbox_h: the exact recomputation after a borrow, one wave-multiply in 2^26) are laid out behind the
+loops and behind s_endpgm: a block that ends in a backward s_branch and can only be entered by a forward conditional branch is not
+counted.
     python tools/poseidon_census.py [liblcp2.so] > profiles/r02_poseidon_census.json"""
 import json
 import os
@@ -61,6 +64,16 @@ def census(lib):
             if tgt < a and tgt in addr:
                 loops.append((addr.index(tgt), k))
     loops.sort()
+    cold, start = 0, None  # start: the first instruction after the last unconditional transfer (not reachable by falling through)
+    for k, (a, mn, ops) in enumerate(ins):
+        if mn == "s_branch":
+            off = int(ops.split()[0], 0)
+            off = off - 0x10000 if off >= 0x8000 else off
+            if off < 0 and start is not None:
+                for j in range(start, k + 1):
+                    weight[j] = 0
+                cold += k + 1 - start
+            start = k + 1
     assert len(loops) == len(TRIPS), "expected %d rolled loops in the permutation, found %d" % (len(TRIPS), len(loops))
     for (lo, hi), trips in zip(loops, TRIPS):
         for k in range(lo, hi + 1):
@@ -71,6 +84,7 @@ def census(lib):
         counts[c] = counts.get(c, 0) + w
         if mn == "s_nop":
             counts["s_nop_wait_states"] = counts.get("s_nop_wait_states", 0) + w * (int(ops.split()[0], 0) + 1)
+    counts["cold_path_instructions_not_counted"] = cold
     return counts, [(hi - lo + 1) for lo, hi in loops]
 
 
