@@ -3,8 +3,9 @@
 // SimpleGenerator::run_once of ArithmeticGate, BaseSumGate<2>, ArithmeticExtensionGate, MulExtensionGate, ReducingGate,
 // ReducingExtensionGate, PoseidonMdsGate, RandomAccessGate, ExponentiationGate and CosetInterpolationGate as ONE function: job in,
 // operands through a load callback, (column, value) pairs out through a store callback.  k_rec_gate_rows (kernels_witness.hip) calls
-// it with loads from the operand list / the column-major witness matrix and stores into that matrix, lcp2_rec_gate_rows
-// (witness_rows.hip) validates a host list with rec_lists_problem, and tests/emu/emu_rec.cpp compiles the same text for the CPU.
+// it with loads from the operand list / the column-major witness matrix and stores into that matrix, the level runner of
+// witness_rows.hip validates a host list with rec_lists_problem, and tests/emu/emu_rec.cpp (the per-job functions) and emu_plan.cpp
+// (a level's launch) compile the same text for the CPU.
 // Layouts and values are those of the gate programs and integer generators in eth-lc-plonky2_amd/recursion_gates.py,
 // u32_gates.py (gate_coset_interpolation / row_coset_interpolation) and circuit.py (gate_arithmetic, gate_base_sum); like them the
 // layout is [RECALL] of plonky2 0.1.4 and its parity is UNPINNED.

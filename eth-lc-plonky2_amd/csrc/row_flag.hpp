@@ -1,10 +1,10 @@
 // The refusal flag of the row generators that validate a job list on the device (lcp2_u32_gate_rows, lcp2_rec_gate_rows,
 // lcp2_witness_plan_rows).
 //
-// One 64-bit word per call.  The entry point sets it to ROW_NO_PROBLEM before the first launch; a lane whose job is refused writes
-// no cell and folds row_refusal(index, problem) into the word with a minimum (the kernels: atomicMin; tests/emu: a compare), so
-// after the last launch the word names the FIRST refused job of the list and why (u32_problem_str / rec_problem_str), whatever
-// the order the lanes ran in.  The entry point reads it back once (witness_rows.hip RefusalFlag).
+// One 64-bit word per call, two for a plan.  The entry point sets it to ROW_NO_PROBLEM before the first launch; a lane whose job is
+// refused writes no cell and folds row_refusal(index, problem) into the word with a minimum (the kernels: atomicMin; tests/emu: a
+// compare), so after the last launch the word names the FIRST refused job of the list and why (u32_problem_str / rec_problem_str),
+// whatever the order the lanes ran in.  The entry point reads it back once (witness_rows.hip RefusalFlag).
 #pragma once
 #include "gl64.hpp"
 
@@ -14,11 +14,11 @@ constexpr u64 ROW_NO_PROBLEM = ~0ull;  // no job of the call has been refused
 LCP2_HD u64 row_refusal(u64 index, u64 problem) { return index << 8 | problem; }  // problem in [1, 255]
 
 
-// lcp2_witness_plan_rows runs TWO families level by level - rec jobs (k_rec_gate_rows, unchanged) and PoseidonGate chains
-// (k_pos_plan_chains) - and a refusal in either must stop every later level of both.  The choice: a family bit folded into ONE word,
-// and a second word that only names the PoseidonGate job.
-//   flags[0]  the word k_rec_gate_rows already folds its refusals into and tests before it runs.  Level l is launched with its job
-//             indices shifted by plan_shift(l) = l + 1, so the key of level l, plan_gate(begin_l, l) = begin_l + l + 1, grows
+// A plan (lcp2_rec_gate_rows is one without chains) runs TWO families level by level - rec jobs (k_rec_gate_rows) and PoseidonGate
+// chains (k_pos_plan_chains) - and a refusal in either must stop every later level of both.  The choice: a family bit folded into ONE
+// word, and a second word that only names the PoseidonGate job.
+//   flags[0]  the word k_rec_gate_rows folds its refusals into and tests before it runs.  Level l of EVERY call is launched with its
+//             job indices shifted by plan_shift(l) = l + 1, so the key of level l, plan_gate(begin_l, l) = begin_l + l + 1, grows
 //             strictly from level to level even where a level holds no rec job.  A refused rec job i of level l folds
 //             row_refusal(i + l + 1, problem); a refused chain of level l folds row_refusal(end_l + l + 1, ROW_OTHER_FAMILY): above
 //             every rec refusal of its own level - the minimum keeps the rec job, which is the one the error names when both
@@ -28,5 +28,21 @@ LCP2_HD u64 row_refusal(u64 index, u64 problem) { return index << 8 | problem; }
 constexpr u64 ROW_OTHER_FAMILY = 0xFF;  // the problem byte of flags[0] when the refusal is the other family's: above every reason
 LCP2_HD u64 plan_shift(u64 level) { return level + 1; }
 LCP2_HD u64 plan_gate(u64 rec_begin, u64 level) { return rec_begin + plan_shift(level); }
+
+// What the two words say after the last level.  problem 0: nothing refused; else the family (0 rec, 1 PoseidonGate), the index of
+// the job in its list and why.  A rec job's level is the one whose shifted range holds the index
+struct PlanRefusal {
+  u32 family, problem;
+  u64 job;
+};
+inline PlanRefusal plan_refusal(const u64 *words, const uint32_t *rec_level_ends, size_t nlevels) {
+  if (words[0] == ROW_NO_PROBLEM) return {0, 0, 0};
+  const u32 problem = (u32)(words[0] & 0xFF);
+  if (problem == ROW_OTHER_FAMILY) return {1, (u32)(words[1] & 0xFF), words[1] >> 8};
+  const u64 shifted = words[0] >> 8;
+  for (size_t l = 0; l < nlevels; l++)
+    if (shifted >= plan_gate(l ? rec_level_ends[l - 1] : 0, l) && shifted < rec_level_ends[l] + plan_shift(l)) return {0, problem, shifted - plan_shift(l)};
+  return {0, problem, 0};
+}
 
 }  // namespace lcp2

@@ -1,7 +1,8 @@
 // Witness-row entry points of liblcp2.so (K10): lcp2_sha256_witness, lcp2_scatter_cells, lcp2_poseidon_gate_rows,
 // lcp2_u32_gate_rows, lcp2_rec_gate_rows and lcp2_witness_plan_rows, with the device scratch, the host-to-device staging and the
-// refusal flag they share.  The kernels are in kernels_witness.hip; the per-row texts in sha_rows.hpp, pos_rows.hpp, u32_rows.hpp,
-// rec_rows.hpp and pos_plan.hpp.
+// refusal flag they share.  The last two check their arguments and run one level runner (run_plan_rows): a rec-gate call is a plan
+// without PoseidonGate chains.  The kernels are in kernels_witness.hip; the per-row texts in sha_rows.hpp, pos_rows.hpp,
+// u32_rows.hpp, rec_rows.hpp and pos_plan.hpp.
 #include <cstring>
 #include "internal.hpp"
 #include "sha_layout.hpp"
@@ -203,12 +204,67 @@ extern "C" int lcp2_u32_gate_rows(lcp2_ctx *ctx, const lcp2_u32_job *jobs, size_
   return flag.end("u32 rows", u32_problem_str, "the valid jobs are written");
 }
 
-// Recursion-gate rows, level by level.  A host list is validated here before anything is queued (structure of every job, and the
-// value conditions of the operands that are IMM); its operands go up whole, before any job, and its jobs in pieces of the pinned
-// staging buffer's size.  A piece may end inside a level: the jobs of a level do not depend on one another, so the level is then two
-// launches, and a piece that holds the end of one level and the start of the next launches them apart, in order.  A device list is
-// validated by the kernel.  Either way the value conditions of CELL operands can only be seen on the device: the flag word is
-// read once, after the last level, because a level that begins after a refused job writes nothing (rec_rows_lane).
+namespace {
+// What a refusal says: "<label>: <rec_job or "poseidon job ">N: <reason>", and for one found on the device what is written
+struct PlanTexts {
+  const char *label, *rec_job, *written;
+};
+
+// A recorded plan of BOTH families, level by level, behind lcp2_rec_gate_rows (a plan without chains) and lcp2_witness_plan_rows,
+// which have checked the arguments: the rec jobs of a level through k_rec_gate_rows (its job indices shifted per level,
+// row_flag.hpp), then the level's PoseidonGate chains through k_pos_plan_chains, all on the context's stream with no host wait in
+// between.  Host lists are validated completely first (rec jobs, then PoseidonGate jobs: structure, and the values that are IMM)
+// and go up whole through the pinned staging buffer, in pieces of its size: operands into scratch slot 2, rec jobs into slot 0,
+// PoseidonGate jobs and chain_ends into slot 3.  Device lists are validated by the kernels.  Either way the value conditions of
+// CELL operands can only be seen on the device: the two flag words are in slot 1 and come back once, after the last level,
+// because a level that begins after a refused job writes nothing (rec_rows_lane, pos_plan_chain_lane).
+int run_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan &p, lcp2_mem lists_mem, uint64_t *wires, uint32_t ncols, uint64_t n, const PlanTexts &text) {
+  const bool host = lists_mem == LCP2_MEM_HOST;
+  const RecJobDev *rec = (const RecJobDev *)p.rec_jobs;
+  const PosJobDev *pos = (const PosJobDev *)p.pos_jobs;
+  const RecOperandDev *ops = (const RecOperandDev *)p.operands;
+  const u32 *chain_ends = p.chain_ends;
+  auto refused = [&](u32 family, u64 job, u32 problem, bool on_device) {
+    return ctx->fail(LCP2_E_INVALID, std::string(text.label) + ": " + (family ? "poseidon job " : text.rec_job) + std::to_string(job) + ": " +
+                                         (family ? pos_plan_problem_str(problem) : rec_problem_str(problem)) +
+                                         (on_device ? std::string(" (found on the device: ") + text.written + ")" : std::string()));
+  };
+  if (host)
+    if (const PlanProblem bad = plan_lists_problem(rec, p.nrec, pos, chain_ends, p.nchains, ops, p.noperands, ncols, n); bad.problem)
+      return refused(bad.family, bad.job, bad.problem, false);
+  LCP2_HIP(ctx, hipSetDevice(ctx->device));
+  RefusalFlag flag{ctx, 2};
+  LCP2_TRY(flag.begin());
+  if (host) {
+    void *d_rec, *d_ops, *d_pos = nullptr;
+    const size_t pos_bytes = (p.npos * sizeof(lcp2_pos_job) + 15) & ~(size_t)15;
+    LCP2_TRY(scratch_ensure(ctx, 0, std::max<size_t>(p.nrec, 1) * sizeof(lcp2_rec_job), &d_rec));
+    LCP2_TRY(scratch_ensure(ctx, 2, std::max<size_t>(p.noperands, 1) * sizeof(lcp2_rec_operand), &d_ops));
+    if (p.npos || p.nchains) LCP2_TRY(scratch_ensure(ctx, 3, pos_bytes + std::max<size_t>(p.nchains, 1) * sizeof(uint32_t), &d_pos));
+    Stage stage{ctx};
+    if (p.noperands) LCP2_TRY(stage.whole(d_ops, ops, p.noperands * sizeof(lcp2_rec_operand)));
+    if (p.nrec) LCP2_TRY(stage.whole(d_rec, rec, p.nrec * sizeof(lcp2_rec_job)));
+    if (p.npos) LCP2_TRY(stage.whole(d_pos, pos, p.npos * sizeof(lcp2_pos_job)));
+    if (p.nchains) LCP2_TRY(stage.whole((char *)d_pos + pos_bytes, chain_ends, p.nchains * sizeof(uint32_t)));
+    rec = (const RecJobDev *)d_rec;
+    ops = (const RecOperandDev *)d_ops;
+    pos = (const PosJobDev *)d_pos;
+    chain_ends = (const u32 *)((char *)d_pos + pos_bytes);
+  }
+  for (size_t l = 0; l < p.nlevels; l++) {
+    const u64 rec_begin = p.nrec && l ? p.rec_level_ends[l - 1] : 0, rec_end = p.nrec ? p.rec_level_ends[l] : 0, shift = plan_shift(l);
+    launch_rec_gate_rows(ctx->stream, rec, shift, rec_begin + shift, rec_end + shift, ops, p.noperands, (u64 *)wires, ncols, n, flag.d, !host);
+    if (p.nchains)
+      launch_pos_plan_chains(ctx->stream, pos, p.npos, chain_ends, l ? p.pos_level_ends[l - 1] : 0, p.pos_level_ends[l], ops, p.noperands,
+                             (u64 *)wires, ncols, n, ctx->d_rc, flag.d, plan_gate(rec_begin, l), rec_end + shift);
+  }
+  LCP2_TRY(flag.read());
+  const PlanRefusal r = plan_refusal(flag.words, p.rec_level_ends, p.nlevels);
+  return r.problem ? refused(r.family, r.job, r.problem, true) : LCP2_OK;
+}
+}  // namespace
+
+// Recursion-gate rows, level by level: the plan that holds these rec jobs and no PoseidonGate job.
 extern "C" int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_t njobs, const lcp2_rec_operand *operands, size_t noperands,
                                   const uint32_t *level_ends, size_t nlevels, lcp2_mem lists_mem, uint64_t *wires, uint32_t ncols, uint64_t n) {
   static_assert(sizeof(lcp2_rec_job) == 16 && sizeof(lcp2_rec_job) == sizeof(RecJobDev) && sizeof(lcp2_rec_operand) == 16 &&
@@ -225,46 +281,11 @@ extern "C" int lcp2_rec_gate_rows(lcp2_ctx *ctx, const lcp2_rec_job *jobs, size_
   if (const size_t at = ends_problem(level_ends, nlevels, njobs); at != ENDS_OK)
     return ctx->fail(LCP2_E_INVALID, at < nlevels ? "rec rows: level_ends is not ascending at level " + std::to_string(at)
                                                   : std::string("rec rows: level_ends does not end at njobs"));
-  const RecJobDev *list = (const RecJobDev *)jobs;
-  const RecOperandDev *ops = (const RecOperandDev *)operands;
-  const bool host = lists_mem == LCP2_MEM_HOST;
-  if (host)
-    if (const RecListProblem bad = rec_lists_problem(list, njobs, ops, noperands, ncols, n); bad.problem)
-      return ctx->fail(LCP2_E_INVALID, "rec rows: job " + std::to_string(bad.job) + ": " + rec_problem_str(bad.problem));
-  LCP2_HIP(ctx, hipSetDevice(ctx->device));
-  RefusalFlag flag{ctx};
-  LCP2_TRY(flag.begin());
-  if (!host) {
-    for (size_t l = 0; l < nlevels; l++)
-      launch_rec_gate_rows(ctx->stream, list, 0, l ? level_ends[l - 1] : 0, level_ends[l], ops, noperands, (u64 *)wires, ncols, n, flag.d, true);
-  } else {
-    constexpr size_t PIECE = lcp2_ctx::PIN_BYTES / sizeof(lcp2_rec_job);  // jobs
-    void *d_jobs, *d_ops;
-    LCP2_TRY(scratch_ensure(ctx, 0, std::min(njobs, PIECE) * sizeof(lcp2_rec_job), &d_jobs));
-    LCP2_TRY(scratch_ensure(ctx, 2, std::max<size_t>(noperands, 1) * sizeof(lcp2_rec_operand), &d_ops));
-    Stage stage{ctx};
-    if (noperands) LCP2_TRY(stage.whole(d_ops, ops, noperands * sizeof(lcp2_rec_operand)));  // before the jobs that use them
-    size_t level = 0;
-    for (size_t at = 0; at < njobs; at += PIECE) {
-      const size_t stop = std::min(njobs, at + PIECE);
-      LCP2_TRY(stage.whole(d_jobs, list + at, (stop - at) * sizeof(lcp2_rec_job)));  // (waits for the launches of the piece before)
-      for (; level < nlevels; level++) {  // the part of every level that lies in [at, stop)
-        const size_t begin = std::max<size_t>(level ? level_ends[level - 1] : 0, at), end = std::min<size_t>(level_ends[level], stop);
-        launch_rec_gate_rows(ctx->stream, (const RecJobDev *)d_jobs, at, begin, end, (const RecOperandDev *)d_ops, noperands, (u64 *)wires, ncols, n,
-                             flag.d, false);
-        if (level_ends[level] > stop) break;  // the level goes on in the next piece
-      }
-    }
-  }
-  return flag.end("rec rows", rec_problem_str, "the valid jobs of its level and of the levels before are written, later levels are not");
+  const lcp2_witness_plan plan = {jobs, njobs, level_ends, nullptr, 0, nullptr, 0, nullptr, operands, noperands, nlevels};
+  return run_plan_rows(ctx, plan, lists_mem, wires, ncols, n,
+                       {"rec rows", "job ", "the valid jobs of its level and of the levels before are written, later levels are not"});
 }
 
-// A recorded plan of BOTH families, level by level: the rec jobs of a level through k_rec_gate_rows (the kernel of
-// lcp2_rec_gate_rows, unchanged: its job indices are shifted per level, row_flag.hpp), then the level's PoseidonGate chains through
-// k_pos_plan_chains, all on the context's stream with no host wait in between.  Host lists are validated completely first (rec
-// jobs, then PoseidonGate jobs: structure, and the values that are IMM) and go up whole through the pinned staging buffer, in
-// pieces of its size: operands into scratch slot 2, rec jobs into slot 0, PoseidonGate jobs and chain_ends into slot 3.  The two flag
-// words are in slot 1 and come back once, after the last level.
 extern "C" int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *plan, lcp2_mem lists_mem, uint64_t *wires, uint32_t ncols, uint64_t n) {
   static_assert(sizeof(lcp2_pos_job) == 8 && sizeof(lcp2_pos_job) == sizeof(PosJobDev), "record layouts must agree");
   static_assert(LCP2_PLAN_IMM == PLAN_IMM && LCP2_PLAN_CELL == PLAN_CELL && LCP2_PLAN_PREV == PLAN_PREV && LCP2_PLAN_IMM == LCP2_REC_IMM &&
@@ -279,7 +300,6 @@ extern "C" int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *pl
   if (ncols < POS_GATE_WIRES) return ctx->fail(LCP2_E_INVALID, "plan rows: the matrix needs at least 135 columns");
   if (p.nrec > 0xFFFFFFFFull || p.npos > 0xFFFFFFFFull || p.nchains > 0xFFFFFFFFull)
     return ctx->fail(LCP2_E_INVALID, "plan rows: more than 2^32 - 1 jobs or chains");
-  const bool host = lists_mem == LCP2_MEM_HOST;
   auto ends_text = [](const uint32_t *ends, size_t count, size_t total, const char *name) -> std::string {
     const size_t at = ends_problem(ends, count, total);
     if (at == ENDS_OK) return "";
@@ -287,53 +307,9 @@ extern "C" int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *pl
   };
   std::string bad = ends_text(p.rec_level_ends, p.nlevels, p.nrec, "rec_level_ends");
   if (bad.empty()) bad = ends_text(p.pos_level_ends, p.nlevels, p.nchains, "pos_level_ends");
-  if (bad.empty() && host) bad = ends_text(p.chain_ends, p.nchains, p.npos, "chain_ends");
+  if (bad.empty() && lists_mem == LCP2_MEM_HOST) bad = ends_text(p.chain_ends, p.nchains, p.npos, "chain_ends");
   if (!bad.empty()) return ctx->fail(LCP2_E_INVALID, bad);
-  const RecJobDev *rec = (const RecJobDev *)p.rec_jobs;
-  const PosJobDev *pos = (const PosJobDev *)p.pos_jobs;
-  const RecOperandDev *ops = (const RecOperandDev *)p.operands;
-  if (host)
-    if (const PlanProblem bad_job = plan_lists_problem(rec, p.nrec, pos, p.chain_ends, p.nchains, ops, p.noperands, ncols, n); bad_job.problem)
-      return ctx->fail(LCP2_E_INVALID, std::string("plan rows: ") + (bad_job.family ? "poseidon job " : "rec job ") + std::to_string(bad_job.job) + ": " +
-                                           (bad_job.family ? pos_plan_problem_str(bad_job.problem) : rec_problem_str(bad_job.problem)));
-  LCP2_HIP(ctx, hipSetDevice(ctx->device));
-  RefusalFlag flag{ctx, 2};
-  LCP2_TRY(flag.begin());
-  const u32 *chain_ends = p.chain_ends;
-  if (host) {
-    void *d_rec, *d_ops, *d_pos;
-    const size_t pos_bytes = (p.npos * sizeof(lcp2_pos_job) + 15) & ~(size_t)15;
-    LCP2_TRY(scratch_ensure(ctx, 0, std::max<size_t>(p.nrec, 1) * sizeof(lcp2_rec_job), &d_rec));
-    LCP2_TRY(scratch_ensure(ctx, 2, std::max<size_t>(p.noperands, 1) * sizeof(lcp2_rec_operand), &d_ops));
-    LCP2_TRY(scratch_ensure(ctx, 3, pos_bytes + std::max<size_t>(p.nchains, 1) * sizeof(uint32_t), &d_pos));
-    Stage stage{ctx};
-    if (p.noperands) LCP2_TRY(stage.whole(d_ops, ops, p.noperands * sizeof(lcp2_rec_operand)));
-    if (p.nrec) LCP2_TRY(stage.whole(d_rec, rec, p.nrec * sizeof(lcp2_rec_job)));
-    if (p.npos) LCP2_TRY(stage.whole(d_pos, pos, p.npos * sizeof(lcp2_pos_job)));
-    if (p.nchains) LCP2_TRY(stage.whole((char *)d_pos + pos_bytes, p.chain_ends, p.nchains * sizeof(uint32_t)));
-    rec = (const RecJobDev *)d_rec;
-    ops = (const RecOperandDev *)d_ops;
-    pos = (const PosJobDev *)d_pos;
-    chain_ends = (const u32 *)((char *)d_pos + pos_bytes);
-  }
-  for (size_t l = 0; l < p.nlevels; l++) {
-    const u64 rec_begin = p.nrec && l ? p.rec_level_ends[l - 1] : 0, rec_end = p.nrec ? p.rec_level_ends[l] : 0, shift = plan_shift(l);
-    launch_rec_gate_rows(ctx->stream, rec, shift, rec_begin + shift, rec_end + shift, ops, p.noperands, (u64 *)wires, ncols, n, flag.d, !host);
-    if (p.nchains)
-      launch_pos_plan_chains(ctx->stream, pos, p.npos, chain_ends, l ? p.pos_level_ends[l - 1] : 0, p.pos_level_ends[l], ops, p.noperands,
-                             (u64 *)wires, ncols, n, ctx->d_rc, flag.d, plan_gate(rec_begin, l), rec_end + shift);
-  }
-  LCP2_TRY(flag.read());
-  const u64 *words = flag.words;
-  if (words[0] == ROW_NO_PROBLEM) return LCP2_OK;
-  const char *written = " (found on the device: the valid rec jobs of its level, the rows of its chain before it, the other chains of its level and all "
-                        "earlier levels are written, later levels are not)";
-  if ((words[0] & 0xFF) != ROW_OTHER_FAMILY) {  // a rec job: its level is the one whose shifted range holds the index
-    const u64 shifted = words[0] >> 8;
-    u64 job = 0;
-    for (size_t l = 0; l < p.nlevels; l++)
-      if (shifted >= plan_gate(l ? p.rec_level_ends[l - 1] : 0, l) && shifted < p.rec_level_ends[l] + plan_shift(l)) job = shifted - plan_shift(l);
-    return ctx->fail(LCP2_E_INVALID, "plan rows: rec job " + std::to_string(job) + ": " + rec_problem_str((u32)(words[0] & 0xFF)) + written);
-  }
-  return ctx->fail(LCP2_E_INVALID, "plan rows: poseidon job " + std::to_string(words[1] >> 8) + ": " + pos_plan_problem_str((u32)(words[1] & 0xFF)) + written);
+  return run_plan_rows(ctx, p, lists_mem, wires, ncols, n,
+                       {"plan rows", "rec job ", "the valid rec jobs of its level, the rows of its chain before it, the other chains of its level and all "
+                                                 "earlier levels are written, later levels are not"});
 }

@@ -519,22 +519,9 @@ CELL = lambda row, col: (int(row), int(col), REC_CELL)   # noqa: E731
 
 def pack_plan(levels):
     """levels: [[(row, kind, op, [IMM(..) / CELL(..), ..]), ..], ..] -> (jobs, operands, level_ends) as record arrays, every level
-    sorted by (kind, op, row): the order in which lcp2_rec_gate_rows stores contiguously"""
-    items = [sorted(level, key=lambda it: (it[1], it[2], it[0])) for level in levels]
-    jobs = np.zeros(sum(len(level) for level in items), dtype=REC_JOB_DTYPE)
-    ops = np.zeros(sum(len(it[3]) for level in items for it in level), dtype=REC_OPERAND_DTYPE)
-    at = k = 0
-    ends = []
-    for level in items:
-        for row, kind, op, operands in level:
-            assert len(operands) == REC_JOB_KINDS[kind][2](op), (kind, op, len(operands))
-            jobs[k] = (row, kind, op, at, 0)
-            for v, col, src in operands:
-                ops[at] = (v % (1 << 64), col, src)
-                at += 1
-            k += 1
-        ends.append(k)
-    return jobs, ops, np.array(ends, dtype=np.uint32)
+    sorted by (kind, op, row): the order in which lcp2_rec_gate_rows stores contiguously.  The witness plan without chains"""
+    plan = pack_witness_plan([(level, []) for level in levels])
+    return plan.rec_jobs, plan.operands, plan.rec_level_ends
 
 
 def run_plan(jobs, operands, level_ends, ncols, n, start=None):
@@ -700,7 +687,7 @@ POS_PLAN_OPERANDS = 13
 def pack_witness_plan(levels):
     """levels: [(rec items, chains), ..]: rec items as in pack_plan, a chain a list of (row, swap operand, [12 input operands])
     -> a namespace of the six lists of lcp2_witness_plan_rows: rec_jobs, pos_jobs, chain_ends, operands, rec_level_ends,
-    pos_level_ends.  The operands of a level follow those of the level before (rec jobs, sorted as pack_plan sorts them, then the
+    pos_level_ends.  The operands of a level follow those of the level before (rec jobs, sorted by (kind, op, row), then the
     chains in order), so level 0's operands come first; `leaves` is their number."""
     rec_items = [sorted(rec, key=lambda it: (it[1], it[2], it[0])) for rec, _ in levels]
     rec_jobs = np.zeros(sum(len(rec) for rec in rec_items), dtype=REC_JOB_DTYPE)

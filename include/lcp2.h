@@ -271,13 +271,14 @@ int lcp2_u32_gate_rows(lcp2_ctx *ctx, const lcp2_u32_job *jobs, size_t njobs, lc
  * Operand values are canonicalised when read (an IMM may be any u64, a cell is reduced after the load) and every value written is
  * canonical.  The two power words of EXPONENTIATION are bit strings, not field elements: an IMM word is used as it stands.
  * Cells outside the operation are NOT touched.
- * Levels: level l is the jobs [level_ends[l-1], level_ends[l]); each level is one launch (a host list: one per staged piece) on
- * the context's stream, in order.  A CELL operand may name any cell the matrix held before the call or that a job of an EARLIER
+ * Levels: level l is the jobs [level_ends[l-1], level_ends[l]); each level is one launch on the context's stream, in order.  A CELL operand may name any cell the matrix held before the call or that a job of an EARLIER
  * level writes.  A reference to a cell written in the SAME level is the caller's error and is NOT detected, like two jobs for one
  * slot or two kinds on one row.  Inside a level any order is correct; the FAST order is (kind, op, row).
  * lists_mem says where jobs AND operands live; level_ends is always host memory.  LCP2_MEM_HOST: the lists are validated before
- * anything is launched - a refused list writes nothing - the operands go up before the jobs, the jobs in pieces.
- * LCP2_MEM_DEVICE: the kernel validates.
+ * anything is launched - a refused list writes nothing - and go up whole through the pinned staging buffer before the first
+ * launch, the operands before the jobs: the context's job scratch holds the whole host job list, 16 bytes per job, as its
+ * operand scratch holds the whole operand list.  LCP2_MEM_DEVICE: the kernel validates.  The call is lcp2_witness_plan_rows
+ * (below) for a plan without PoseidonGate chains.
  * Refused (LCP2_E_INVALID; lcp2_last_error names "job <index>" and the reason): row >= n, an unknown kind, op out of range,
  * first_operand + count > noperands, an operand src above 1, a CELL operand with col >= ncols or v >= n; also ncols < 135,
  * level_ends not ascending or not ending at njobs, a lists_mem above 1, a null ctx, wires, or (njobs > 0) jobs / level_ends, or

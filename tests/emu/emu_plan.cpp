@@ -1,7 +1,8 @@
 // TEST HARNESS (not product code): csrc/pos_plan.hpp compiled for the CPU - the validation of lcp2_witness_plan_rows, the portable
-// PoseidonGate job and chain texts, and one level's two launches (k_rec_gate_rows with its shifted indices, then the chains in the
-// one-lane-per-chain reference form of k_pos_plan_chains) as loops over lanes, with the two flag words of row_flag.hpp.
-// Built by tests/test_plan_rows.py with g++ and included by tests/emu/sanitize_plan_main.cpp; never loaded by the package.
+// PoseidonGate job and chain texts, one level's two launches as lcp2_rec_gate_rows (no chains) and lcp2_witness_plan_rows make them
+// (k_rec_gate_rows with its shifted indices, then the chains in the one-lane-per-chain reference form of k_pos_plan_chains) as
+// loops over lanes, and the two flag words of row_flag.hpp with the entry points' decode of them.
+// Built by tests/rows_lib.py with g++ and included by tests/emu/sanitize_plan_main.cpp; never loaded by the package.
 #include "../../eth-lc-plonky2_amd/csrc/pos_plan.hpp"
 #include "emu_rc.hpp"
 
@@ -53,6 +54,15 @@ void emu_plan_level(const RecJobDev *rec, unsigned long long rec_begin, unsigned
     if (refusal < flags[1]) flags[1] = refusal;
     if (row_refusal(rec_end + shift, ROW_OTHER_FAMILY) < flags[0]) flags[0] = row_refusal(rec_end + shift, ROW_OTHER_FAMILY);
   }
+}
+
+// what the flag words name after the last level, as the entry points decode them: 0, or the problem with *family and *job
+unsigned emu_plan_refusal(const unsigned long long *flags, const unsigned *rec_level_ends, unsigned long long nlevels, unsigned *family,
+                          unsigned long long *job) {
+  const PlanRefusal r = plan_refusal(flags, rec_level_ends, nlevels);
+  *family = r.family;
+  *job = r.job;
+  return r.problem;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // TEST HARNESS (not product code): csrc/rec_rows.hpp compiled for the CPU - the per-job function of k_rec_gate_rows
-// (lcp2_rec_gate_rows), the validation it shares with the host entry point, and one level's launch as a loop over lanes.
+// (lcp2_rec_gate_rows) and the validation it shares with the host entry point.  A level's launch is emu_plan.cpp's.
 // Built by tests/test_rec_rows.py with g++; never loaded by the package.
 #include "../../eth-lc-plonky2_amd/csrc/rec_rows.hpp"
 
@@ -33,20 +33,6 @@ unsigned emu_rec_job_cells(const RecJobDev *job, const RecOperandDev *operands, 
                   count++;
                 });
   return count;
-}
-
-// k_rec_gate_rows for the jobs [begin, end) of one level over a grid of blocks of `threads` lanes, lane by lane; *flag as the
-// kernel keeps it (ROW_NO_PROBLEM = ~0 before the first level)
-void emu_rec_level(const RecJobDev *jobs, unsigned long long begin, unsigned long long end, const RecOperandDev *operands,
-                   unsigned long long noperands, unsigned long long *wires, unsigned ncols, unsigned long long n, unsigned long long *flag,
-                   unsigned threads) {
-  const unsigned long long blocks = (end - begin + threads - 1) / threads;
-  for (unsigned long long b = 0; b < blocks; b++)
-    for (unsigned t = 0; t < threads; t++) {
-      const u64 i = begin + b * threads + t;
-      const u64 problem = rec_rows_lane(jobs, 0, begin, end, i, operands, noperands, wires, ncols, n, flag, true);
-      if (problem && row_refusal(i, problem) < *flag) *flag = row_refusal(i, problem);
-    }
 }
 
 }  // extern "C"

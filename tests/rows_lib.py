@@ -1,10 +1,12 @@
 """What the tests of the witness-row and verifier families share (test harness only): the one builder of the CPU emulations
-tests/emu/<name>.cpp -> tests/emu/lib<name>.so, the constants of the row texts, a matrix and a record list in HBM, a gate's own
-constraint program on one row, and the null-context walk of the entry points.  tools/*_probe.py build their emulation here too."""
+tests/emu/<name>.cpp -> tests/emu/lib<name>.so, the constants of the row texts, a plan's levels through the emulated launches and
+the decode of its flag words, a matrix and a record list in HBM, a gate's own constraint program on one row, and the null-context
+walk of the entry points.  tools/*_probe.py build their emulation here too."""
 import ctypes
 import glob
 import os
 import subprocess
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -37,6 +39,47 @@ def build_emu(name, signatures, opt="-O2"):
 
 def vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+# ------------------------------------------------------------------ a plan's levels through tests/emu/emu_plan.cpp
+def emu_plan():
+    """tests/emu/libemu_plan.so"""
+    c, V, U = ctypes, ctypes.c_void_p, ctypes.c_uint64
+    return build_emu("emu_plan", (("emu_plan_pos_job_bytes", c.c_uint, []), ("emu_plan_operand_bytes", c.c_uint, []), ("emu_plan_pos_operands", c.c_uint, []),
+                                  ("emu_plan_problem_str", c.c_char_p, [c.c_uint]), ("emu_plan_pos_problem", c.c_uint, [V, c.c_int, V, U, c.c_uint, U]),
+                                  ("emu_plan_lists_problem", c.c_uint, [V, U, V, V, U, V, U, c.c_uint, U, V, V]),
+                                  ("emu_plan_level", None, [V, U, U, V, U, V, U, U, V, U, V, c.c_uint, U, V, U, c.c_uint]),
+                                  ("emu_plan_refusal", c.c_uint, [V, V, U, V, V])))
+
+
+def vpn(a):
+    """(an empty list of a plan goes in as a null pointer)"""
+    return vp(a) if a.size else None
+
+
+def rec_plan(jobs, operands, level_ends):
+    """the witness plan a rec-gate call is: these rec jobs, no PoseidonGate job, no chain"""
+    none = np.zeros(0, dtype=np.uint32)
+    return SimpleNamespace(rec_jobs=jobs, pos_jobs=none, chain_ends=none, operands=operands, rec_level_ends=np.asarray(level_ends, dtype=np.uint32),
+                           pos_level_ends=np.zeros(len(level_ends), dtype=np.uint32))
+
+
+def run_levels(E, plan, n, start=None, order=None, threads=64):
+    """the plan through the emulated launches, level by level (`order`: these levels, in this order): (matrix, the two flag words)"""
+    got = np.zeros((NW, n), dtype=np.uint64) if start is None else start.copy()
+    flags = np.full(2, NONE, dtype=np.uint64)
+    rec_ends, pos_ends = [0] + plan.rec_level_ends.tolist(), [0] + plan.pos_level_ends.tolist()
+    for l in (range(len(rec_ends) - 1) if order is None else order):
+        E.emu_plan_level(vpn(plan.rec_jobs), rec_ends[l], rec_ends[l + 1], vpn(plan.pos_jobs), plan.pos_jobs.size, vpn(plan.chain_ends), pos_ends[l],
+                         pos_ends[l + 1], vpn(plan.operands), plan.operands.size, vp(got), NW, n, vp(flags), l, threads)
+    return got, [int(f) for f in flags]
+
+
+def refusal(E, flags, plan):
+    """(family, job, reason code) the two flag words name, as the entry points decode them; None while nothing is refused"""
+    family, job = ctypes.c_uint(0), ctypes.c_uint64(0)
+    code = E.emu_plan_refusal(vp(np.array(flags, dtype=np.uint64)), vpn(plan.rec_level_ends), plan.rec_level_ends.size, ctypes.byref(family), ctypes.byref(job))
+    return (("rec", "poseidon")[family.value], job.value, code) if code else None
 
 
 def gate_constraints(gs, name, row, consts):

@@ -11,7 +11,10 @@ import numpy as np
 import pytest
 
 import rows_lib
-from rows_lib import INVALID, MAX, NONE, NW, P, TAG, DeviceMatrix, build_emu, check_null_context, gate_constraints, upload
+from rows_lib import INVALID, MAX, NONE, NW, P, TAG, DeviceMatrix, check_null_context, gate_constraints, upload
+from rows_lib import refusal as named
+from rows_lib import run_levels as emu_run
+from rows_lib import vpn as vp
 
 ARITH, BSUM, RA = 0, 1, 7
 REASONS = {1: "row out of range", 2: "operands run past", 3: "src above 2", 4: "first job of a chain", 5: "PREV as the swap", 6: "column of 12 or more",
@@ -25,48 +28,8 @@ def rg():
 
 @pytest.fixture(scope="module")
 def emul():
-    """tests/emu/libemu_plan.so"""
-    c, V, U = ctypes, ctypes.c_void_p, ctypes.c_uint64
-    return build_emu("emu_plan", (("emu_plan_pos_job_bytes", c.c_uint, []), ("emu_plan_operand_bytes", c.c_uint, []), ("emu_plan_pos_operands", c.c_uint, []),
-                            ("emu_plan_problem_str", c.c_char_p, [c.c_uint]), ("emu_plan_pos_problem", c.c_uint, [V, c.c_int, V, U, c.c_uint, U]),
-                            ("emu_plan_lists_problem", c.c_uint, [V, U, V, V, U, V, U, c.c_uint, U, V, V]),
-                            ("emu_plan_level", None, [V, U, U, V, U, V, U, U, V, U, V, c.c_uint, U, V, U, c.c_uint])))
-
-
-def vp(a):
-    """(an empty list of a plan goes in as a null pointer)"""
-    return rows_lib.vp(a) if a.size else None
-
-
-def level_bounds(plan):
-    nl = len(plan.rec_level_ends)
-    return [((int(plan.rec_level_ends[l - 1]) if l else 0, int(plan.rec_level_ends[l])),
-             (int(plan.pos_level_ends[l - 1]) if l else 0, int(plan.pos_level_ends[l]))) for l in range(nl)]
-
-
-def emu_run(E, plan, n, start=None, order=None, threads=64):
-    """the plan through the emulated launches, level by level: (matrix, the two flag words)"""
-    got = np.zeros((NW, n), dtype=np.uint64) if start is None else start.copy()
-    flags = np.full(2, NONE, dtype=np.uint64)
-    bounds = level_bounds(plan)
-    for l in (range(len(bounds)) if order is None else order):
-        (rb, re), (cb, ce) = bounds[l]
-        E.emu_plan_level(vp(plan.rec_jobs), rb, re, vp(plan.pos_jobs), plan.pos_jobs.size, vp(plan.chain_ends), cb, ce, vp(plan.operands),
-                         plan.operands.size, vp(got), NW, n, vp(flags), l, threads)
-    return got, [int(f) for f in flags]
-
-
-def named(flags, plan):
-    """(family, job, reason code) the two flag words name, as the entry point decodes them; None while nothing is refused"""
-    if flags[0] == NONE:
-        return None
-    if flags[0] & 0xFF != 0xFF:
-        shifted = flags[0] >> 8
-        for l, ((rb, re), _) in enumerate(level_bounds(plan)):
-            if rb + l + 1 <= shifted < re + l + 1:
-                return ("rec", shifted - l - 1, flags[0] & 0xFF)
-        raise AssertionError("flags[0] names no rec job")
-    return ("poseidon", flags[1] >> 8, flags[1] & 0xFF)
+    """tests/emu/libemu_plan.so; emu_run(E, plan, n, ..) runs a plan's levels through it, named(E, flags, plan) decodes its flag words"""
+    return rows_lib.emu_plan()
 
 
 def lists_problem(E, plan, n, noperands=None):
@@ -266,7 +229,7 @@ def test_a_cell_swap_of_two_stops_its_chain_and_later_levels(emul):
     plan = g.pack_witness_plan(levels)
     assert lists_problem(emul, plan, 64) is None, "only the device can see the value"
     got, flags = emu_run(emul, plan, 64)
-    assert named(flags, plan) == ("poseidon", 4, 9)
+    assert named(emul, flags, plan) == ("poseidon", 4, 9)
     want = g.run_witness_plan(g.pack_witness_plan(kept), NW, 64)
     assert (got == want).all()
     assert want[:, [10, 11, 12, 13, 16, 17]].any(axis=0).all() and not got[:, [14, 15, 40, 41]].any()
@@ -278,13 +241,29 @@ def test_both_families_refuse_in_one_level_the_rec_job_is_named(emul):
     plan = g.pack_witness_plan(levels)
     got, flags = emu_run(emul, plan, 64)
     bad_at = int(plan.rec_level_ends[0]) + plan.rec_jobs["kind"][plan.rec_level_ends[0]:plan.rec_level_ends[1]].tolist().index(RA)
-    assert named(flags, plan) == ("rec", bad_at, 9) and flags[1] == (4 << 8 | 9)
+    assert named(emul, flags, plan) == ("rec", bad_at, 9) and flags[1] == (4 << 8 | 9)
     assert (got == g.run_witness_plan(g.pack_witness_plan(kept), NW, 64)).all() and not got[:, [14, 15, 30, 40, 41]].any()
     levels, kept = refusal_levels(bad_swap=False, bad_rec=True)   # the rec family alone: the chains of its level run in full
     plan = g.pack_witness_plan(levels)
     got, flags = emu_run(emul, plan, 64)
-    assert named(flags, plan) == ("rec", bad_at, 9) and flags[1] == NONE
+    assert named(emul, flags, plan) == ("rec", bad_at, 9) and flags[1] == NONE
     assert (got == g.run_witness_plan(g.pack_witness_plan(kept), NW, 64)).all() and got[:, 15].any() and not got[:, [30, 40, 41]].any()
+
+
+def test_the_decode_of_hand_built_flag_words(emul):
+    """plan_refusal (row_flag.hpp), the decode both entry points use, on flag words built by hand for rec_level_ends = [4, 4, 7] -
+    level 1 holds no rec job, so its key (6) and level 2's first index (7) are what plan_gate keeps apart.  The expected triples are
+    what the Python loop this export replaced returned"""
+    plan = rows_lib.rec_plan(None, None, [4, 4, 7])
+    assert named(emul, [NONE, NONE], plan) is None
+    assert named(emul, [0x101, NONE], plan) == ("rec", 0, 1)        # level 0: index job + 1
+    assert named(emul, [0x409, NONE], plan) == ("rec", 3, 9)
+    assert named(emul, [0x90B, NONE], plan) == ("rec", 6, 11)       # the last level: index job + 3
+    assert named(emul, [0x708, NONE], plan) == ("rec", 4, 8)        # the first job after the empty level: index 7, above level 1's key
+    assert named(emul, [0x708, 0x509], plan) == ("rec", 4, 8)       # both families refused in level 2: the rec job
+    assert named(emul, [0x6FF, 0x509], plan) == ("poseidon", 5, 9)  # a chain of the empty level (marker 4 + 2): the family bit
+    assert named(emul, [0xAFF, 0x004], plan) == ("poseidon", 0, 4)  # a chain of the last level (marker 7 + 3)
+    assert named(emul, [0x30A, NONE], rows_lib.rec_plan(None, None, [3])) == ("rec", 2, 10)   # a rec-gate call of one level
 
 
 def plan_struct(m, plan, counts=None):

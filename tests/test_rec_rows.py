@@ -2,16 +2,17 @@
 ReducingGate, ReducingExtensionGate, PoseidonMdsGate, RandomAccessGate, ExponentiationGate, CosetInterpolationGate) generated on the
 device from a recorded plan: jobs whose operands are immediates or cells of the witness matrix, run level by level.
 
-Without a GPU: csrc/rec_rows.hpp - the per-job function the kernel runs, the validation, and one level's launch as a loop over
-lanes - compiled for the CPU (tests/emu/emu_rec.cpp) against the integer generators row_*, against Python integers
-(recursion_gates.job_cells) and against the gates' own constraint programs (gate_program_ref), a chained plan level by level, and
-the argument checks of the entry point.  On the GPU: the same through the library, and a proof from a device-filled matrix
+Without a GPU: csrc/rec_rows.hpp - the per-job function the kernel runs and the validation (tests/emu/emu_rec.cpp), and one
+level's launch as a loop over lanes (tests/emu/emu_plan.cpp: the launch of a plan without chains) - compiled for the CPU against
+the integer generators row_*, against Python integers (recursion_gates.job_cells) and against the gates' own constraint programs
+(gate_program_ref), a chained plan level by level, and the argument checks of the entry point.  On the GPU: the same through the library, and a proof from a device-filled matrix
 against the host matrix' and the oracle's."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import rows_lib
 from rows_lib import INVALID, MAX, NONE, NW, P, DeviceMatrix, build_emu, check_null_context, gate_constraints, upload, vp
 
 ARITH, BSUM, AEXT, MEXT, RED, REDX, PMDS, RA, EXP, COSET = range(10)
@@ -32,8 +33,13 @@ def emur():
                             ("emu_rec_kind_ops", c.c_uint, [c.c_uint]), ("emu_rec_kind_operands", c.c_uint, [c.c_uint, c.c_uint]),
                             ("emu_rec_coset_domain", U, [c.c_uint]), ("emu_rec_coset_weight", U, [c.c_uint]),
                             ("emu_rec_job_problem", c.c_uint, [V, V, U, c.c_uint, U]), ("emu_rec_value_problem", c.c_uint, [V, V]),
-                            ("emu_rec_job_cells", c.c_uint, [V, V, V, V, c.c_uint]),
-                            ("emu_rec_level", None, [V, U, U, V, U, V, c.c_uint, U, V, c.c_uint])))
+                            ("emu_rec_job_cells", c.c_uint, [V, V, V, V, c.c_uint])))
+
+
+@pytest.fixture(scope="module")
+def emul():
+    """tests/emu/libemu_plan.so: a level's launch"""
+    return rows_lib.emu_plan()
 
 
 def imm_job(kind, op, vals, row=0):
@@ -54,13 +60,13 @@ def emu_cells(E, kind, op, vals):
 
 
 def emu_run(E, jobs, ops, ends, n, threads, start=None, order=None):
-    """the plan through the emulated launches, one per level: (matrix, flag)"""
-    got = np.zeros((NW, n), dtype=np.uint64) if start is None else start.copy()
-    flag = np.full(1, NONE, dtype=np.uint64)
-    bounds = [(int(ends[l - 1]) if l else 0, int(ends[l])) for l in range(len(ends))]
-    for begin, end in (bounds if order is None else [bounds[l] for l in order]):
-        E.emu_rec_level(vp(jobs), begin, end, vp(ops), ops.size, vp(got), NW, n, vp(flag), threads)
-    return got, int(flag[0])
+    """the plan through the emulated launches, one per level, as the witness plan without chains it is: (matrix, flag), the flag
+    as the entry point decodes it: NONE, or job << 8 | reason"""
+    plan = rows_lib.rec_plan(jobs, ops, ends)
+    got, flags = rows_lib.run_levels(E, plan, n, start, order, threads)
+    named = rows_lib.refusal(E, flags, plan)
+    assert flags[1] == NONE and (named is None or named[0] == "rec")
+    return got, NONE if named is None else named[1] << 8 | named[2]
 
 
 # ------------------------------------------------------------------ the edge jobs (tests 3 and 7)
@@ -247,7 +253,7 @@ def test_edge_jobs_equal_python_integers_and_satisfy_their_gates(emur):
         assert any(gate_constraints(gs, name, row, consts)), (name, op, tag)
 
 
-def test_chain_plan_level_by_level(emur):
+def test_chain_plan_level_by_level(emul):
     """chain_plan(64, seed) through the emulated launches from a zero matrix, at 64 and 256 lanes per block: the expected matrix,
     nothing outside the owned cells; the levels in reverse order do NOT give it (a level reads what the level before wrote)"""
     g = rg()
@@ -260,14 +266,31 @@ def test_chain_plan_level_by_level(emur):
         owned[g.job_columns(int(j["kind"]), int(j["op"])), int(j["row"])] = True
     assert not plan.expected[~owned].any() and (plan.expected < np.uint64(P)).all()
     for threads in (64, 256):
-        got, flag = emu_run(emur, plan.jobs, plan.operands, plan.level_ends, 64, threads)
+        got, flag = emu_run(emul, plan.jobs, plan.operands, plan.level_ends, 64, threads)
         assert flag == NONE
         assert (got == plan.expected).all()
-    got, _ = emu_run(emur, plan.jobs, plan.operands, plan.level_ends, 64, 64, order=list(reversed(range(len(plan.level_ends)))))
+    got, _ = emu_run(emul, plan.jobs, plan.operands, plan.level_ends, 64, 64, order=list(reversed(range(len(plan.level_ends)))))
     assert not (got == plan.expected).all()
     other = g.chain_plan(64, seed=5)
     assert (other.jobs == plan.jobs).all() and (other.operands[other.operands["src"] == 1] == plan.operands[plan.operands["src"] == 1]).all()
     assert not (other.expected == plan.expected).all()
+
+
+def test_pack_plan_is_the_witness_plan_without_chains():
+    """pack_plan(levels) and pack_witness_plan with empty chain lists give the same rec jobs, operands and level ends byte for
+    byte, and no PoseidonGate job, chain or chain level: three levels of 30 ARITHMETIC jobs, and one job of every kind"""
+    g = rg()
+    good = arithmetic_jobs(90, 64, np.random.default_rng(12))
+    every_kind = {kind: (row, kind, 0, [g.IMM(v) for v in vals]) for row, (kind, vals, _) in reversed(list(enumerate(edge_jobs())))}
+    assert sorted(every_kind) == list(range(10))
+    for levels in ([good[:30], good[30:60], good[60:]], [list(every_kind.values())]):
+        jobs, ops, ends = g.pack_plan(levels)
+        plan = g.pack_witness_plan([(level, []) for level in levels])
+        assert jobs.size == sum(len(level) for level in levels) == ends[-1] and ops.size == sum(len(it[3]) for level in levels for it in level)
+        assert (jobs.tobytes(), ops.tobytes(), ends.tobytes()) == (plan.rec_jobs.tobytes(), plan.operands.tobytes(), plan.rec_level_ends.tobytes())
+        assert (jobs.dtype, ops.dtype, ends.dtype) == (plan.rec_jobs.dtype, plan.operands.dtype, plan.rec_level_ends.dtype)
+        assert plan.pos_jobs.size == 0 and plan.chain_ends.size == 0 and not plan.pos_level_ends.any()
+        assert (g.run_plan(jobs, ops, ends, NW, 64) == g.run_witness_plan(plan, NW, 64)).all()
 
 
 def structural_cases():
@@ -294,7 +317,7 @@ VALUE_CASES = [(8, BSUM, [1 << 63], [(1 << 63) - 1]), (9, RA, [16] + [1] * 16, [
                (11, COSET, [0] + [1] * 34, [1] * 35), (11, COSET, [P] + [1] * 34, [P + 1] + [1] * 34)]
 
 
-def test_refused_jobs(emur):
+def test_refused_jobs(emur, emul):
     """every structural reason and every value reason as IMM through the shared validation; the limits are accepted; as CELL the
     flag names the job, that job's cells stay untouched, the rest of its level is written and later levels are not run"""
     g = rg()
@@ -314,7 +337,7 @@ def test_refused_jobs(emur):
         keep = np.ones(jobs.size, dtype=bool)
         keep[bad_at] = False
         want = g.run_plan(jobs[keep], ops, [ends[0], ends[1] - 1], NW, 64)   # the levels up to the refused job's, without it
-        got, flag = emu_run(emur, jobs, ops, ends, 64, 64)
+        got, flag = emu_run(emul, jobs, ops, ends, 64, 64)
         assert flag == (bad_at << 8 | code)
         assert (got == want).all() and not got[:, 10].any() and not got[:, 20].any()
 
@@ -466,9 +489,69 @@ def test_forty_levels(gpu_ctx):
 
 
 @pytest.mark.gpu
+def test_both_entry_points_run_one_plan(gpu_ctx):
+    """64 rows, three levels of 30 ARITHMETIC jobs, level 1 reading a cell of level 0: lcp2_rec_gate_rows and lcp2_witness_plan_rows
+    with npos = nchains = 0 and pos_level_ends = NULL, from host lists and from device lists, leave run_plan's matrix.  Then one job
+    of level 1 becomes a RANDOM_ACCESS job whose index is a CELL holding 16, which only the device can see: both entry points
+    return LCP2_E_INVALID, name the same job, and leave levels 0 and 1 without that job written and nothing of level 2"""
+    import re
+    import eth_lc_plonky2_amd as m
+    g = rg()
+    lib, h, n = gpu_ctx.lib, gpu_ctx.handle, 64
+    good = arithmetic_jobs(90, n, np.random.default_rng(12))
+    levels = [list(good[:30]), list(good[30:60]), list(good[60:])]
+    src_row, _, src_op, _ = levels[0][0]
+    row, kind, op, operands = levels[1][0]
+    levels[1][0] = (row, kind, op, operands[:2] + [g.CELL(src_row, 4 * src_op + 3)] + operands[3:])
+    zero = np.zeros((NW, n), dtype=np.uint64)
+
+    def both(jobs, ops, ends, device_lists):
+        """[(status, last error, matrix)] of lcp2_rec_gate_rows and of lcp2_witness_plan_rows"""
+        out = []
+        dj, do = (upload(gpu_ctx, jobs), upload(gpu_ctx, ops)) if device_lists else (jobs.ctypes.data, ops.ctypes.data)
+        mem = m.MEM_DEVICE if device_lists else m.MEM_HOST
+        plan = m.binding.WitnessPlan(dj, jobs.size, ends.ctypes.data, None, 0, None, 0, None, do, ops.size, ends.size)
+        for by_plan in (False, True):
+            dm = DeviceMatrix(gpu_ctx, zero)
+            wp = ctypes.c_void_p(dm.ptr)
+            status = (lib.lcp2_witness_plan_rows(h, ctypes.byref(plan), mem, wp, NW, n) if by_plan else
+                      lib.lcp2_rec_gate_rows(h, ctypes.c_void_p(dj), jobs.size, ctypes.c_void_p(do), ops.size, vp(ends), ends.size, mem, wp, NW, n))
+            out.append((status, lib.lcp2_last_error(h) if status else b"", dm.read()))
+            dm.free()
+        if device_lists:
+            gpu_ctx.buffer_free(dj)
+            gpu_ctx.buffer_free(do)
+        return out
+
+    jobs, ops, ends = g.pack_plan(levels)
+    want = g.run_plan(jobs, ops, ends, NW, n)
+    assert list(ends) == [30, 60, 90] and (ops["src"] == 1).sum() == 1 and not (want == g.run_plan(jobs, ops, ends[:1], NW, n)).all()
+    for device_lists in (False, True):
+        for status, _, got in both(jobs, ops, ends, device_lists):
+            assert status == 0 and (got == want).all(), device_lists
+    # level 0's first job writes 16 (1 * 16 * 1 + 0), and a job of level 1 reads it as its RANDOM_ACCESS index
+    levels[0][0] = (src_row, ARITH, src_op, [g.IMM(1), g.IMM(0), g.IMM(16), g.IMM(1), g.IMM(0)])
+    levels[1][1] = (levels[1][1][0], RA, 0, [g.CELL(src_row, 4 * src_op + 3)] + [g.IMM(k) for k in range(16)])
+    jobs, ops, ends = g.pack_plan(levels)
+    bad_at = 59   # pack_plan sorts a level by kind: the RANDOM_ACCESS job is the last of level 1
+    assert list(ends) == [30, 60, 90] and int(jobs["kind"][bad_at]) == RA
+    keep = np.ones(jobs.size, dtype=bool)
+    keep[bad_at] = False
+    want = g.run_plan(jobs[keep], ops, [30, 59], NW, n)
+    assert not (want == g.run_plan(jobs[keep], ops, [30], NW, n)).all() and not (want == g.run_plan(jobs[keep], ops, [30, 59, 89], NW, n)).all()
+    for device_lists in (False, True):
+        (rec_status, rec_error, rec_got), (plan_status, plan_error, plan_got) = both(jobs, ops, ends, device_lists)
+        assert rec_status == INVALID == plan_status
+        assert b"rec rows: job 59: random-access index" in rec_error and b"plan rows: rec job 59: random-access index" in plan_error
+        assert re.search(rb"job (\d+):", rec_error).group(1) == re.search(rb"job (\d+):", plan_error).group(1) == b"%d" % bad_at
+        assert (rec_got == want).all() and (plan_got == want).all(), device_lists
+
+
+@pytest.mark.gpu
 def test_long_host_list(gpu_ctx):
-    """a host list of 2^18 + 5 jobs: the pinned staging buffer holds 2^18 records, so the jobs go up in two pieces, and the piece
-    boundary lies inside level 0 (level_ends = [count - 3, count]).  Built as test_long_host_lists builds its list: 1280 jobs
+    """a host list of 2^18 + 5 jobs: the pinned staging buffer holds 2^18 records, so the upload of the whole list takes it twice;
+    that boundary lies inside level 0 (level_ends = [count - 3, count]) and is an upload boundary only - the list is whole in HBM
+    before the first launch, and a level is one launch.  Built as test_long_host_lists builds its list: 1280 jobs
     fill a 64-row matrix; the list repeats the first 1275 (equal jobs for one slot leave that value; they share their operands)
     and ends with the other 5, whose slots nothing earlier writes.  The 3 jobs of level 1 read a cell level 0 wrote."""
     g = rg()

@@ -10,7 +10,6 @@ permutation of every row, which is what a host generator has to run before it kn
 12 inputs) per row and calls lcp2_poseidon_gate_rows once; both parts are timed, and the three matrices must be equal.
 Prints ONE JSON line and writes it to profiles/plan_rows_probe.json.
     python3 tools/plan_rows_probe.py 5"""
-import ctypes
 import json
 import os
 import sys
@@ -22,24 +21,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))   # rows_lib: the builder of the
 NW = 135
 
 
-def emulation():
-    from rows_lib import build_emu
-    V, U = ctypes.c_void_p, ctypes.c_uint64
-    return build_emu("emu_plan", [("emu_plan_level", None, [V, U, U, V, U, V, U, U, V, U, V, ctypes.c_uint, U, V, U, ctypes.c_uint])])
-
-
 def host_walk(E, plan, n):
     """the plan on one host thread, level by level: (matrix, ms)"""
-    import numpy as np
-    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None   # noqa: E731
-    got, flags = np.zeros((NW, n), dtype=np.uint64), np.full(2, (1 << 64) - 1, dtype=np.uint64)
+    import rows_lib
     t0 = time.perf_counter()
-    for l in range(len(plan.rec_level_ends)):
-        rb, cb = (int(plan.rec_level_ends[l - 1]), int(plan.pos_level_ends[l - 1])) if l else (0, 0)
-        E.emu_plan_level(vp(plan.rec_jobs), rb, int(plan.rec_level_ends[l]), vp(plan.pos_jobs), plan.pos_jobs.size, vp(plan.chain_ends), cb,
-                         int(plan.pos_level_ends[l]), vp(plan.operands), plan.operands.size, vp(got), NW, n, vp(flags), l, 256)
+    got, flags = rows_lib.run_levels(E, plan, n, threads=256)
     ms = 1e3 * (time.perf_counter() - t0)
-    assert int(flags[0]) == (1 << 64) - 1
+    assert rows_lib.refusal(E, flags, plan) is None
     return got, ms
 
 
@@ -95,7 +83,8 @@ def workload(ctx, E, name, plan, n, reps):
 def measure(ctx, reps=5):
     import numpy as np
     from eth_lc_plonky2_amd import recursion_gates as rg
-    E = emulation()
+    import rows_lib
+    E = rows_lib.emu_plan()
     rng = np.random.default_rng(31)
     f = lambda: int(rng.integers(0, rg.P, dtype=np.uint64))   # noqa: E731
     Z = rg.IMM(0)

@@ -2,9 +2,8 @@
 """lcp2_rec_gate_rows as a workload: recursion_gates.chain_plan over 2^bits rows in `levels` levels (about 2^16 jobs at the defaults),
 run from a zero matrix with host lists (validation and upload included) and with lists already in HBM, the result compared with the
 Python-integer matrix.  Prints ONE JSON line and writes it to profiles/rec_rows_probe.json, with the host time the same plan needs
-in Python integers (recursion_gates.run_plan) and in C++ (csrc/rec_rows.hpp compiled for the CPU, one thread: tests/emu/emu_rec.cpp).
+in Python integers (recursion_gates.run_plan) and in C++ (csrc/rec_rows.hpp compiled for the CPU, one thread: tests/emu/emu_plan.cpp).
     python3 tools/rec_rows_probe.py 16 8 5"""
-import ctypes
 import json
 import os
 import sys
@@ -16,22 +15,17 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))   # rows_lib: the builder of the
 
 
 def host_cpp_ms(plan, n, reps):
-    """the plan through rec_rows.hpp on one host thread, level by level (best of reps), and whether it gives the expected matrix"""
-    import numpy as np
-    from rows_lib import build_emu, vp
-    V, U = ctypes.c_void_p, ctypes.c_uint64
-    E = build_emu("emu_rec", [("emu_rec_level", None, [V, U, U, V, U, V, ctypes.c_uint, U, V, ctypes.c_uint])])
+    """the plan through rec_rows.hpp on one host thread, level by level as the witness plan without chains it is (best of reps), and
+    whether it gives the expected matrix and refuses nothing"""
+    import rows_lib
+    E, levels = rows_lib.emu_plan(), rows_lib.rec_plan(plan.jobs, plan.operands, plan.level_ends)
     best, same = None, True
     for _ in range(reps):
-        got, flag = np.zeros((135, n), dtype=np.uint64), np.full(1, (1 << 64) - 1, dtype=np.uint64)
         t0 = time.perf_counter()
-        begin = 0
-        for end in plan.level_ends.tolist():
-            E.emu_rec_level(vp(plan.jobs), begin, end, vp(plan.operands), plan.operands.size, vp(got), 135, n, vp(flag), 256)
-            begin = end
+        got, flags = rows_lib.run_levels(E, levels, n, threads=256)
         t = time.perf_counter() - t0
         best = t if best is None else min(best, t)
-        same = same and bool((got == plan.expected).all())
+        same = same and rows_lib.refusal(E, flags, levels) is None and bool((got == plan.expected).all())
     return 1e3 * best, same
 
 
