@@ -213,7 +213,8 @@ def gate_base_sum(num_limbs=BASE_SUM_LIMBS):
         asm.flags |= GATE_NATIVE_BASE_SUM2
         for i in reversed(range(num_limbs)):
             asm.emit_bool(W(1 + i))
-        acc = asm.dbladd(W(num_limbs), W(num_limbs - 1))
+        # Horner from the top limb down; a single limb is the sum itself (0 + limb, so that acc is a register as below)
+        acc = asm.dbladd(W(num_limbs), W(num_limbs - 1)) if num_limbs > 1 else asm.add(asm.imm(0), W(1))
         for i in reversed(range(num_limbs - 2)):
             asm.dbladd(acc, W(1 + i), dst=acc[1])
         asm.sub(acc, W(0), dst=acc[1])

@@ -1,14 +1,16 @@
 // K6 for gfx950: the quotient polynomial values on the LDE coset (compute_quotient_polys + eval_vanishing_poly_base_batch of
-// plonk/prover.rs, every gate's eval_unfiltered_base) - the host staging of the gate programs, the native plonky2 gate evaluators,
+// plonk/prover.rs, every gate's eval_unfiltered_base) - the host staging of the gate programs, the native PoseidonGate evaluator,
 // the PoseidonGate / light-gate / permutation kernels, their launchers, the challenge-dependent setup and the combination of a
-// coset-sharded proof.  The kernel skeleton and the interpreter are quotient_common.hpp; the generated evaluators have kernels of
-// their own (kernels_gates.hpp, kernels_gates_*.hip).
+// coset-sharded proof.  The kernel skeleton and the interpreter are quotient_common.hpp; the native ArithmeticGate and BaseSumGate<2>
+// are the one walk of light_gates.hpp (each alone, and both at once for the pair of a light list: build() holds all three forms to
+// the gates' programs); the generated evaluators have kernels of their own (kernels_gates.hpp, kernels_gates_*.hip).
 //
 // The LDE matrices are indexed in their storage (= Merkle leaf) order, so all column reads are coalesced 512-byte runs per wave;
 // the only gathers are the two Z(g x) values per point in k_q_perm.
 #include <algorithm>
 #include "gate_program.hpp"
 #include "kernels_gates.hpp"
+#include "light_gates.hpp"
 
 namespace lcp2 {
 
@@ -167,67 +169,41 @@ __device__ __forceinline__ void q_poseidon_native(const QuotientArgs &a, u64 i, 
 }
 #endif
 
-// ---- native ArithmeticGate { num_ops } (gates/arithmetic_base.rs): output - (c0 * m0 * m1 + c1 * addend) per operation, wires
-// 4k .. 4k+3.  Constraints are folded last to first (plain Horner with alpha), four operations = 16 wire loads per batch.
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ void q_arithmetic_native(const QuotientArgs &a, u64 i, u32 num_ops, QEmit &emit) {
-  const u64 *W = a.wires + i;
-  const u64 st = a.stride;
-  const u64 c0 = a.consts[(u64)a.num_selectors * st + i], c1 = a.consts[(u64)(a.num_selectors + 1) * st + i];
-  emit.begin_terms();  // operation k is constraint k: weight alpha^k
-  for (int top = (int)num_ops; top > 0; top -= 4) {  // operations [top - 4, top), clamped at 0
-    const int first = top >= 4 ? top - 4 : 0;
-    u64 w[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = W[(u64)min(4 * first + j, 4 * (int)num_ops - 1) * st];  // a short last batch re-reads its last wire
-#pragma unroll
-    for (int k = 3; k >= 0; k--) {
-      if (first + k < top) {
-        const u64 comp = gl_add(gl_mul(gl_mul(w[4 * k], w[4 * k + 1]), c0), gl_mul(w[4 * k + 2], c1));
-        emit.term(a, (u32)(first + k), gl_sub(w[4 * k + 3], comp));
-      }
-    }
-  }
-  emit.finish_terms();
-}
-// ---- native BaseSumGate<2> { num_limbs } (gates/base_sum.rs): constraints [sum_i 2^i limb_i - wire_0, limb_i^2 - limb_i ...],
-// folded last to first: the limb constraints from the top limb down (the recomposition is the same walk), then the sum.
-__device__ __forceinline__ void q_base_sum2_native(const QuotientArgs &a, u64 i, u32 num_limbs, QEmit &emit) {
-  const u64 *W = a.wires + i;
-  const u64 st = a.stride;
-  u64 sum = 0;
-  emit.begin_terms();  // constraint 0 is the sum, constraint 1 + l the booleanity of limb l
-  for (int top = (int)num_limbs; top > 0; top -= 16) {  // limbs [top - 16, top) = wires [top - 15, top]
-    u64 w[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) { const int l = top - 1 - j; w[j] = W[(u64)(1 + (l > 0 ? l : 0)) * st]; }
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      if (top - 1 - j >= 0) {
-        emit.term(a, (u32)(top - j), gl_mul_nc(w[j], gl_sub(w[j], 1)));  // limb top - 1 - j
-        sum = gl_add(gl_add(sum, sum), w[j]);
-      }
-    }
-  }
-  emit.term(a, 0, gl_sub(sum, W[0]));
-  emit.finish_terms();
-}
-#endif
-
 // the native evaluators as evaluator types (quotient_common.hpp q_gate_value)
 #if defined(__HIP_DEVICE_COMPILE__)
 struct QPoseidon {
   static __device__ __forceinline__ void run(const QuotientArgs &a, const GateDev &, u64 i, u64 *lds, u32 T, u32 tid, QEmit &emit) { q_poseidon_native(a, i, lds, T, tid, emit); }
 };
+// ArithmeticGate and BaseSumGate<2>: light_gates.hpp, one text for each gate alone and for the pair of a light list
 struct QArithmetic {
-  static __device__ __forceinline__ void run(const QuotientArgs &a, const GateDev &G, u64 i, u64 *, u32, u32, QEmit &emit) { q_arithmetic_native(a, i, G.num_constraints, emit); }
+  static __device__ __forceinline__ void run(const QuotientArgs &a, const GateDev &G, u64 i, u64 *, u32, u32, QEmit &emit) { q_arith_base_walk<true, false>(a, i, G.num_constraints, 0, emit, emit); }
 };
 struct QBaseSum2 {
-  static __device__ __forceinline__ void run(const QuotientArgs &a, const GateDev &G, u64 i, u64 *, u32, u32, QEmit &emit) { q_base_sum2_native(a, i, G.num_constraints - 1, emit); }
+  static __device__ __forceinline__ void run(const QuotientArgs &a, const GateDev &G, u64 i, u64 *, u32, u32, QEmit &emit) { q_arith_base_walk<false, true>(a, i, 0, G.num_constraints - 1, emit, emit); }
 };
+// ArithmeticGate gA and BaseSumGate<2> gB of one circuit in one walk over the wires: loaded once, they feed both evaluators
+__device__ __forceinline__ void q_pair_values(const QuotientArgs &a, u32 gA, u32 gB, const GateDev &GA, const GateDev &GB, u64 i, u64 valA[QUOTIENT_MAX_CH], u64 valB[QUOTIENT_MAX_CH]) {
+  QEmit eA, eB;
+  q_emit_begin(a, GA, eA); q_emit_begin(a, GB, eB);
+  q_arith_base_walk<true, true>(a, i, GA.num_constraints, GB.num_constraints - 1, eA, eB);
+  q_gate_finish(a, gA, GA, i, eA, valA); q_gate_finish(a, gB, GB, i, eB, valB);
+}
 #else
 struct QPoseidon; struct QArithmetic; struct QBaseSum2;
 #endif
+// The claim check of a pair (launch_native_check), g = gA | gB << 16: each gate's program against its value out of the shared walk
+struct QArithBasePair;
+template <>
+__device__ __forceinline__ void q_claim_check<QArithBasePair>(const QuotientArgs &a, u32 g, u64 i, u64 *lds, u32 T, u32 tid, unsigned long long *flag) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const u32 gA = g & 0xFFFFu, gB = g >> 16;
+  const GateDev GA = q_load_gate(a, gA), GB = q_load_gate(a, gB);
+  u64 pA[QUOTIENT_MAX_CH], pB[QUOTIENT_MAX_CH], vA[QUOTIENT_MAX_CH], vB[QUOTIENT_MAX_CH];
+  q_gate_value<QInterpreted>(a, gA, GA, i, lds, T, tid, pA); q_gate_value<QInterpreted>(a, gB, GB, i, lds, T, tid, pB);
+  q_pair_values(a, gA, gB, GA, GB, i, vA, vB);
+  q_claim_compare(a, i, pA, vA, flag); q_claim_compare(a, i, pB, vB, flag);
+#endif
+}
 
 // K6 is one launch per gate type plus the permutation pass: every kernel carries only the registers its gate needs (the native
 // PoseidonGate wants ~120 VGPRs, the permutation pass ~90, an interpreted gate ~80), so none drags the others' occupancy down,
@@ -374,58 +350,14 @@ __global__ __launch_bounds__(QUOTIENT_THREADS, 2) void k_q_perm(QuotientArgs a, 
     if (c < CH) a.out[(u64)c * a.N + ig] = gl_mul(res[c], zhi);
 }
 
-// ArithmeticGate and BaseSumGate<2> of one circuit in one walk over the wires (both read the routed wires from index 0 up: the
-// wires are loaded once, 16 at a time from the top, and feed both evaluators; same constraint order as q_arithmetic_native and
-// q_base_sum2_native, so the sums are the same field elements)
-__device__ __forceinline__ void q_arith_base_pair(const QuotientArgs &a, u64 i, u32 gA, u32 gB, const GateDev &GA, const GateDev &GB, u64 valA[QUOTIENT_MAX_CH], u64 valB[QUOTIENT_MAX_CH]) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const u32 CH = a.num_challenges;
-  QEmit eA, eB;
-  eA.CH = eB.CH = CH; eA.emitted = eB.emitted = 0;
-#pragma unroll
-  for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) { eA.acc[c] = eB.acc[c] = 0; eA.step[c] = eB.step[c] = c < CH ? konst(a.alphas)[c] : 0; }
-  eA.begin_terms(); eB.begin_terms();
-  const int num_ops = (int)GA.num_constraints, num_limbs = (int)GB.num_constraints - 1;
-  const u64 *W = a.wires + i;
-  const u64 st = a.stride;
-  const u64 c0 = a.consts[(u64)a.num_selectors * st + i], c1 = a.consts[(u64)(a.num_selectors + 1) * st + i];
-  const int top_wire = max(4 * num_ops, num_limbs + 1), last_wire = (int)a.num_wires - 1;
-  u64 sum = 0, w0 = 0;
-  for (int hi = (top_wire + 15) & ~15; hi > 0; hi -= 16) {  // wires [hi - 16, hi)
-    u64 w[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = W[(u64)min(hi - 16 + j, last_wire) * st];
-#pragma unroll
-    for (int kk = 3; kk >= 0; kk--) {
-      if ((hi - 16) / 4 + kk < num_ops) {
-        const u64 comp = gl_add(gl_mul(gl_mul(w[4 * kk], w[4 * kk + 1]), c0), gl_mul(w[4 * kk + 2], c1));
-        eA.term(a, (u32)((hi - 16) / 4 + kk), gl_sub(w[4 * kk + 3], comp));
-      }
-    }
-#pragma unroll
-    for (int j = 15; j >= 0; j--) {
-      const int limb = hi - 16 + j - 1;  // wire 0 is the sum, limb l sits on wire l + 1
-      if (limb >= 0 && limb < num_limbs) {
-        eB.term(a, (u32)(1 + limb), gl_mul_nc(w[j], gl_sub(w[j], 1)));
-        sum = gl_add(gl_add(sum, sum), w[j]);
-      }
-    }
-    if (hi == 16) w0 = w[0];
-  }
-  eB.term(a, 0, gl_sub(sum, w0));
-  eA.finish_terms(); eB.finish_terms();
-  const u64 fA = q_filter(a, gA, GA, i), fB = q_filter(a, gB, GB, i);
-#pragma unroll
-  for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
-    if (c < CH) { valA[c] = gl_mul(fA, eA.acc[c]); valB[c] = gl_mul(fB, eB.acc[c]); }
-#endif
-}
-
 // The light gates of a circuit in ONE launch: interpreted gates (Constant, PublicInput and whatever else has no native form) and
 // the native ArithmeticGate / BaseSumGate, evaluated one after the other by the same thread with a single update of `out`.  Alone
 // each of them is a latency-bound kernel of a few hundred to a few thousand instructions per point (one instruction per 5 - 8
 // cycles against 3.7 for the heavy gates); together their loads overlap and three read-modify-write passes over `out` go away.
-struct LightGates { u32 count; u32 g[8]; };
+// pair_a / pair_b: the positions in g[] of the first ArithmeticGate and the first BaseSumGate<2> when the list has both (they share
+// one walk over the wires: q_pair_values), LIGHT_NO_PAIR otherwise; chosen on the host (launch_gates)
+constexpr u32 LIGHT_NO_PAIR = ~0u;
+struct LightGates { u32 count; u32 g[8]; u32 pair_a, pair_b; };
 template <bool CHECK>
 __global__ __launch_bounds__(QUOTIENT_THREADS, 2) void k_q_light(QuotientArgs a, LightGates L, u32 accumulate, unsigned long long *flag) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -436,24 +368,13 @@ __global__ __launch_bounds__(QUOTIENT_THREADS, 2) void k_q_light(QuotientArgs a,
   u64 sum[QUOTIENT_MAX_CH];
 #pragma unroll
   for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) sum[c] = 0;
-  // an ArithmeticGate and a BaseSumGate in the list share one walk over the wires
-  u32 ka = ~0u, kb = ~0u;
-  for (u32 k = 0; k < L.count; k++) {
-    const u32 kind = konst((const u32 *)a.gates)[(size_t)L.g[k] * (sizeof(GateDev) / 4) + 7] & LCP2_GATE_NATIVE_MASK;
-    if (kind == LCP2_GATE_NATIVE_ARITHMETIC && ka == ~0u) ka = k;
-    if (kind == LCP2_GATE_NATIVE_BASE_SUM2 && kb == ~0u) kb = k;
-  }
-  const bool pair = ka != ~0u && kb != ~0u;
+  const u32 ka = L.pair_a, kb = L.pair_b;
+  const bool pair = ka != LIGHT_NO_PAIR;
   if (pair) {
     const GateDev GA = q_load_gate(a, L.g[ka]), GB = q_load_gate(a, L.g[kb]);
-    bool run = true;
-    if (CHECK) {
-      const u64 sa = a.consts[(u64)GA.selector_index * a.stride + i], sb = a.consts[(u64)GB.selector_index * a.stride + i];
-      run = __any(sa == GA.selector_value || sb == GB.selector_value);
-    }
-    if (run) {
+    if (q_wave_holds<CHECK>(a, GA, i) || q_wave_holds<CHECK>(a, GB, i)) {
       u64 va[QUOTIENT_MAX_CH], vb[QUOTIENT_MAX_CH];
-      q_arith_base_pair(a, i, L.g[ka], L.g[kb], GA, GB, va, vb);
+      q_pair_values(a, L.g[ka], L.g[kb], GA, GB, i, va, vb);
 #pragma unroll
       for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
         if (c < a.num_challenges) sum[c] = gl_add(va[c], vb[c]);
@@ -502,20 +423,27 @@ bool is_light(const GateDev &G) {
   const u32 k = G.flags & LCP2_GATE_NATIVE_MASK;
   return k == 0 || k == LCP2_GATE_NATIVE_ARITHMETIC || k == LCP2_GATE_NATIVE_BASE_SUM2;
 }
+// the claim check names a pair in one word, gA | gB << 16 (launch_native_check): a gate index that does not fit is never paired
+bool pairable(u32 g) { return g < (1u << 16); }
 // tier (nullable): only the gates g with tier[g] == want (the full tier is -1, a bundle its index); nullptr: every gate
 template <bool CHECK>
 u32 launch_gates(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, unsigned long long *flag, const int *tier = nullptr, int want = -1) {
   u32 launched = 0;
-  LightGates L{};
+  const LightGates none{0, {}, LIGHT_NO_PAIR, LIGHT_NO_PAIR};
+  LightGates L = none;
   auto flush = [&] {
     if (!L.count) return;
+    if (L.pair_a == LIGHT_NO_PAIR || L.pair_b == LIGHT_NO_PAIR) L.pair_a = L.pair_b = LIGHT_NO_PAIR;  // one of the two alone: no pair
     hipLaunchKernelGGL((k_q_light<CHECK>), q_grid(a), dim3(QUOTIENT_THREADS), q_interp_lds_bytes(a), s, a, L, launched ? 1u : 0u, flag);
     launched++;
-    L.count = 0;
+    L = none;
   };
   for (u32 g = 0; g < host_gates.size(); g++) {
     if (host_gates[g].num_constraints == 0 || (tier && tier[g] != want)) continue;
     if (is_light(host_gates[g])) {
+      const u32 kind = host_gates[g].flags & LCP2_GATE_NATIVE_MASK;
+      if (kind == LCP2_GATE_NATIVE_ARITHMETIC && L.pair_a == LIGHT_NO_PAIR && pairable(g)) L.pair_a = L.count;
+      if (kind == LCP2_GATE_NATIVE_BASE_SUM2 && L.pair_b == LIGHT_NO_PAIR && pairable(g)) L.pair_b = L.count;
       L.g[L.count++] = g;
       if (L.count == 8) flush();
       continue;
@@ -592,13 +520,21 @@ void launch_tier_combine(hipStream_t s, const QuotientArgs &a, const QuotientTie
 void launch_gate_check(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, unsigned long long *flag) {
   launch_gates<true>(s, a, host_gates, flag);
 }
+// Every claim against its program on the points of `a`: the generated evaluators, the native PoseidonGate, ArithmeticGate and
+// BaseSumGate<2> each alone, and every ArithmeticGate with every BaseSumGate<2> (whichever two a tier's light list pairs) out of
+// the shared walk, each gate against its own program.  Compared: filter * sum_j alpha^j c_j per challenge, that is constraint
+// values, their weights and the filter.  Not compared: the kernels' wave votes and stores (the proofs' parity tests hold those).
 void launch_native_check(hipStream_t s, const QuotientArgs &a, const std::vector<GateDev> &host_gates, unsigned long long *flag) {
+  auto kind_of = [&](u32 g) { return host_gates[g].flags & LCP2_GATE_NATIVE_MASK; };
   for (u32 g = 0; g < host_gates.size(); g++) {
-    const u32 kind = host_gates[g].flags & LCP2_GATE_NATIVE_MASK;
+    const u32 kind = kind_of(g);
     if (kind & 0x8000u) { launch_generated(s, a, (kind >> 8) & 0x7Fu, g, 0, flag, GEN_CLAIM_CHECK); continue; }
     switch (kind) {
       case LCP2_GATE_NATIVE_POSEIDON: launch_claim_check<QPoseidon>(s, a, g, flag); break;
-      case LCP2_GATE_NATIVE_ARITHMETIC: launch_claim_check<QArithmetic>(s, a, g, flag); break;
+      case LCP2_GATE_NATIVE_ARITHMETIC: launch_claim_check<QArithmetic>(s, a, g, flag);
+        for (u32 gB = 0; gB < host_gates.size() && pairable(g) && pairable(gB); gB++)  // an ArithmeticGate only: its pairs
+          if (kind_of(gB) == LCP2_GATE_NATIVE_BASE_SUM2) launch_claim_check<QArithBasePair>(s, a, g | gB << 16, flag);
+        break;
       case LCP2_GATE_NATIVE_BASE_SUM2: launch_claim_check<QBaseSum2>(s, a, g, flag); break;
       default: break;
     }
@@ -617,7 +553,7 @@ __global__ __launch_bounds__(256) void k_quotient_setup(QuotientSetupArgs a) {
     }
   } else if (t < 255) {          // alpha_c^(m_g - 1) for every gate g
     for (u32 g = t - QUOTIENT_TERM_POWS; g < a.num_gates; g += 255 - QUOTIENT_TERM_POWS) {
-      const u32 m = konst((const u32 *)a.gates)[(size_t)g * (sizeof(GateDev) / 4) + 6];
+      const u32 m = konst((const u32 *)a.gates)[(size_t)g * GW_WORDS + GW_NUM_CONSTRAINTS];
       for (u32 c = 0; c < QUOTIENT_MAX_CH; c++) a.small[SMALL_GATE_SCALE + (size_t)g * QUOTIENT_MAX_CH + c] = c < CH ? (m ? gl_pow(a.alphas[c], m - 1) : 1) : 0;
     }
   } else {                       // the scalars

@@ -35,6 +35,9 @@ const char *params_problem(const lcp2_params &p, bool *unsupported) {
 }  // namespace lcp2
 
 namespace {
+// light_gates.hpp weights constraint j with entry j of the alpha-limb table, as the generated evaluators do
+static_assert(QUOTIENT_TERM_POWS == 128, "the limit LIGHT_GATE_LIMIT names");
+const char *const LIGHT_GATE_LIMIT = "LCP2_GATE_NATIVE_ARITHMETIC / LCP2_GATE_NATIVE_BASE_SUM2: at most 128 constraints (the alpha power table holds 128 weights)";
 // validate the programs once so that neither the kernels nor the host verifier ever index out of range
 const char *validate_programs(const lcp2_circuit_desc *d) {
   const lcp2_params &p = d->params;
@@ -53,9 +56,11 @@ const char *validate_programs(const lcp2_circuit_desc *d) {
       case LCP2_GATE_NATIVE_ARITHMETIC:
         if ((G.flags & LCP2_GATE_EMIT_FORWARD) || G.num_constraints == 0 || 4 * (size_t)G.num_constraints > p.num_wires || p.num_constants - d->num_selectors < 2)
           return "LCP2_GATE_NATIVE_ARITHMETIC needs 4 wires per operation and 2 gate constants";
+        if (G.num_constraints > QUOTIENT_TERM_POWS) return LIGHT_GATE_LIMIT;
         break;
       case LCP2_GATE_NATIVE_BASE_SUM2:
         if ((G.flags & LCP2_GATE_EMIT_FORWARD) || G.num_constraints < 2 || G.num_constraints > p.num_wires) return "LCP2_GATE_NATIVE_BASE_SUM2 needs num_limbs + 1 wires";
+        if (G.num_constraints > QUOTIENT_TERM_POWS) return LIGHT_GATE_LIMIT;
         break;
       default:
         // a generated evaluator weights constraint j with alpha^j whichever way the program lists them (the claim check decides)

@@ -1,6 +1,7 @@
 // Argument blocks and launch wrappers of the prover kernels (kernels_prover.hip; K6, the quotient: kernels_quotient.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <vector>
 #include "gl64.hpp"
 #include "ntt.hpp"
@@ -29,6 +30,9 @@ constexpr size_t SMALL_BETAS = 0, SMALL_GAMMAS = 4, SMALL_ALPHAS = 8, SMALL_ALPH
 struct GateDev {  // = lcp2_gate
   u32 selector_index, selector_value, group_start, group_end, code_offset, code_len, num_constraints, flags;
 };
+// word indices into the uploaded table, for the kernels that read a single field (q_load_gate reads the words in this order)
+constexpr u32 GW_NUM_CONSTRAINTS = 6, GW_FLAGS = 7, GW_WORDS = 8;
+static_assert(sizeof(GateDev) == 4 * GW_WORDS && offsetof(GateDev, num_constraints) == 4 * GW_NUM_CONSTRAINTS && offsetof(GateDev, flags) == 4 * GW_FLAGS, "GateDev's words");
 
 struct PermArgs {
   const u64 *wires;    // witness values on the rows [row0, row0 + n) of H, [num_wires][wires_stride]

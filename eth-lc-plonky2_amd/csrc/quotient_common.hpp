@@ -280,8 +280,8 @@ __device__ __forceinline__ void q_gate_finish(const QuotientArgs &a, u32 g, cons
       val[c] = gl_mul(f, sum);
     }
 }
-// An evaluator is a type with  static void run(a, G, i, lds, T, tid, emit): the interpreter here, the native plonky2 gates in
-// kernels_quotient.hip, the generated programs in kernels_gates.hpp.
+// An evaluator is a type with  static void run(a, G, i, lds, T, tid, emit): the interpreter here, the native PoseidonGate and the
+// two instantiations of light_gates.hpp for one gate in kernels_quotient.hip, the generated programs in kernels_gates.hpp.
 struct QInterpreted {
   static __device__ __forceinline__ void run(const QuotientArgs &a, const GateDev &G, u64 i, u64 *lds, u32 T, u32 tid, QEmit &emit) { q_interpret(a, G, i, lds, T, tid, emit); }
 };
@@ -297,9 +297,9 @@ __device__ __forceinline__ void q_gate_value(const QuotientArgs &a, u32 g, const
 #endif
 __device__ __forceinline__ GateDev q_load_gate(const QuotientArgs &a, u32 g) {
   GateDev G;  // field by field: an address-space-qualified struct has no implicit copy
-  const_as<u32> gw = konst((const u32 *)a.gates) + (size_t)g * (sizeof(GateDev) / 4);
+  const_as<u32> gw = konst((const u32 *)a.gates) + (size_t)g * GW_WORDS;
   G.selector_index = gw[0]; G.selector_value = gw[1]; G.group_start = gw[2]; G.group_end = gw[3];
-  G.code_offset = gw[4]; G.code_len = gw[5]; G.num_constraints = gw[6]; G.flags = gw[7];
+  G.code_offset = gw[4]; G.code_len = gw[5]; G.num_constraints = gw[GW_NUM_CONSTRAINTS]; G.flags = gw[GW_FLAGS];
   return G;
 }
 
@@ -339,6 +339,13 @@ __device__ __forceinline__ void q_gate_store(const QuotientArgs &a, u64 i, const
   }
 }
 // build()-time check of a claim: gate g's program, interpreted, against evaluator EVAL on the random point i of a.wires / a.consts
+__device__ __forceinline__ void q_claim_compare(const QuotientArgs &a, u64 i, const u64 (&r0)[QUOTIENT_MAX_CH], const u64 (&r1)[QUOTIENT_MAX_CH], unsigned long long *flag) {
+  bool bad = false;
+#pragma unroll
+  for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
+    if (c < a.num_challenges && r0[c] != r1[c]) bad = true;
+  if (bad) atomicMin(flag, (unsigned long long)i + 1);
+}
 template <class EVAL>
 __device__ __forceinline__ void q_claim_check(const QuotientArgs &a, u32 g, u64 i, u64 *lds, u32 T, u32 tid, unsigned long long *flag) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -346,11 +353,7 @@ __device__ __forceinline__ void q_claim_check(const QuotientArgs &a, u32 g, u64 
   u64 r0[QUOTIENT_MAX_CH], r1[QUOTIENT_MAX_CH];
   q_gate_value<QInterpreted>(a, g, G, i, lds, T, tid, r0);
   q_gate_value<EVAL>(a, g, G, i, lds, T, tid, r1);
-  bool bad = false;
-#pragma unroll
-  for (u32 c = 0; c < QUOTIENT_MAX_CH; c++)
-    if (c < a.num_challenges && r0[c] != r1[c]) bad = true;
-  if (bad) atomicMin(flag, (unsigned long long)i + 1);
+  q_claim_compare(a, i, r0, r1, flag);
 #endif
 }
 

@@ -424,8 +424,8 @@ enum { LCP2_OP_ADD = 0, LCP2_OP_SUB = 1, LCP2_OP_MUL = 2, LCP2_OP_EMIT = 3, LCP2
  * verifier always interprets the program.  0 = none. */
 #define LCP2_GATE_NATIVE_MASK 0xFF00u
 #define LCP2_GATE_NATIVE_POSEIDON 0x0100u   /* PoseidonGate, gates/poseidon.rs: 135 wires, 123 constraints, EMIT_FORWARD order */
-#define LCP2_GATE_NATIVE_ARITHMETIC 0x0200u /* ArithmeticGate { num_ops = num_constraints }: wires 4k..4k+3, constants 0 and 1 */
-#define LCP2_GATE_NATIVE_BASE_SUM2 0x0300u  /* BaseSumGate<2> { num_limbs = num_constraints - 1 }: wire 0 = sum, wires 1.. = bits */
+#define LCP2_GATE_NATIVE_ARITHMETIC 0x0200u /* ArithmeticGate { num_ops = num_constraints <= 128 }: wires 4k..4k+3, constants 0 and 1 */
+#define LCP2_GATE_NATIVE_BASE_SUM2 0x0300u  /* BaseSumGate<2> { num_limbs = num_constraints - 1 <= 127 }: wire 0 = sum, wires 1.. = bits */
 /* straight-line device forms generated offline from gate programs (tools/gen/, csrc/generated_gates.hpp): program k of that file */
 #define LCP2_GATE_NATIVE_GENERATED(k) (0x8000u | ((uint32_t)(k) << 8))
 typedef struct {

@@ -1,6 +1,6 @@
-// TEST HARNESS (not product code): emu_pos.cpp and emu_u32.cpp under ASan + UBSan as a stand-alone program
-// (tests/checks/emu_sanitize.sh): the Poseidon edge rows one by one and as a grid on a tagged matrix, and a u32 job list with two
-// refused jobs.
+// TEST HARNESS (not product code): emu_pos.cpp, emu_u32.cpp and emu_gates.cpp under ASan + UBSan as a stand-alone program
+// (tests/checks/emu_sanitize.sh): the Poseidon edge rows one by one and as a grid on a tagged matrix, a u32 job list with two
+// refused jobs, and the walk of the light native gates (csrc/light_gates.hpp) on wire matrices of exactly num_wires columns.
 #include <vector>
 #include "sanitize_common.hpp"
 #include "emu_rc.hpp"
@@ -15,6 +15,9 @@ void emu_pos_gate_rows(const PoseidonRowDev *rows, unsigned long long nrows, uns
                        unsigned threads);
 void emu_u32_gate_rows(const U32JobDev *jobs, unsigned long long njobs, unsigned long long *wires, unsigned long long n, unsigned long long *flag,
                        unsigned blocks, unsigned threads);
+void emu_light_walk(unsigned num_ops, unsigned num_limbs, const unsigned long long *wires, unsigned num_wires, const unsigned long long *consts,
+                    unsigned num_selectors, unsigned long long count, const unsigned long long *alphas, unsigned long long *a_alone,
+                    unsigned long long *b_alone, unsigned long long *a_pair, unsigned long long *b_pair);
 }
 
 int main() {
@@ -56,6 +59,27 @@ int main() {
   emu_u32_gate_rows(jobs.data(), jobs.size(), w32.data(), n, &flag, 2, 64);
   CHECK(flag == row_refusal(7, 1));
   CHECK(w32[0 * n + 7] == TAG && w32[(70 / 16) * n + 70 % 16] == TAG && w32[0 * n + 8] == 0xFFFFFFFFu - 8);
-  printf("emu_pos and emu_u32 under the sanitizers: ok\n");
+
+  // the light-gate walk: the wire matrix ends with wire num_wires - 1 (heap: a read past it is ASan's), num_wires = the top wire the
+  // shape reads and one above it, the shapes on both sides of a batch of 16; the pair must give what each gate gives alone
+  const unsigned shapes[][2] = {{20, 63}, {1, 127}, {33, 1}, {4, 15}, {4, 16}, {5, 14}, {3, 0}, {0, 17}};
+  for (const auto &sh : shapes) {
+    const unsigned ops = sh[0], limbs = sh[1], top = 4 * ops > (limbs ? limbs + 1 : 0) ? 4 * ops : limbs + 1;
+    for (unsigned nw = top; nw <= top + 1; nw++) {
+      const u64 cnt = 3;
+      std::vector<unsigned long long> lw((size_t)nw * cnt), lc(3 * cnt), out[4];
+      u64 seed = 1 + nw;
+      for (auto &v : lw) v = gl_canon(seed = seed * 6364136223846793005ull + 1442695040888963407ull);
+      for (auto &v : lc) v = gl_canon(seed = seed * 6364136223846793005ull + 1442695040888963407ull);
+      for (auto &o : out) o.assign(2 * cnt, TAG);
+      const unsigned long long alphas[2] = {lw[0] | 1, 0};
+      emu_light_walk(ops, limbs, lw.data(), nw, lc.data(), 1, cnt, alphas, out[0].data(), out[1].data(), out[2].data(), out[3].data());
+      for (u64 k = 0; k < 2 * cnt; k++) {
+        CHECK(ops && limbs ? out[0][k] == out[2][k] && out[1][k] == out[3][k] : out[2][k] == TAG && out[3][k] == TAG);
+        CHECK((out[0][k] == TAG) == !ops && (out[1][k] == TAG) == !limbs);
+      }
+    }
+  }
+  printf("emu_pos, emu_u32 and the light-gate walk under the sanitizers: ok\n");
   return 0;
 }

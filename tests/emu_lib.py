@@ -16,8 +16,10 @@ def load():
 
 
 def load_gates():
-    """tests/emu/libemu_gates.so: the generated gate evaluators (csrc/generated_gates_*.hpp) compiled for the CPU"""
+    """tests/emu/libemu_gates.so: the generated gate evaluators (csrc/generated_gates_*.hpp) and the walk of the two light native gates
+    (csrc/light_gates.hpp) compiled for the CPU"""
     return build_emu("emu_gates", (
         ("emu_generated_count", c.c_uint, []), ("emu_generated_waves", c.c_uint, [c.c_uint]),
         ("emu_generated_gate", c.c_int, [c.c_uint, V, V, V, c.c_uint, c.c_uint64, V, V]),
+        ("emu_light_walk", None, [c.c_uint, c.c_uint, V, c.c_uint, V, c.c_uint, c.c_uint64, V, V, V, V, V]),
         ("emu_gl_mul_u32", c.c_uint64, [c.c_uint64, c.c_uint32]), ("emu_gl_shl_nc", c.c_uint64, [c.c_uint64, c.c_uint])), opt="-O1")

@@ -138,6 +138,82 @@ def test_generated_evaluators_equal_their_programs_on_the_cpu():
                     assert int(out[i, ch]) == want, (name, i, ch, alphas)
 
 
+# ---------------------------------------------------------------- the walk of the two light native gates (csrc/light_gates.hpp) on the CPU
+LIGHT_SHAPES = ([(k, 0) for k in (1, 3, 4, 5, 20, 33)] + [(0, l) for l in (1, 14, 15, 16, 17, 31, 63, 127)] +
+                [(20, 63), (1, 127), (33, 1), (4, 15), (4, 16), (5, 14)])   # (num_ops, num_limbs), 0: the shape has no such gate
+
+
+def _light_programs(num_ops, num_limbs):
+    """(code, imm) of ArithmeticGate { num_ops } - the loop of circuit.gate_arithmetic - and of BaseSumGate<2> { num_limbs }"""
+    import eth_lc_plonky2_amd as m
+    cm = m.circuit
+    out = []
+    for build in (None if not num_ops else "arithmetic", None if not num_limbs else cm.gate_base_sum(num_limbs)):
+        if build is None:
+            out.append(None)
+            continue
+        asm = cm.GateAsm(cm.ImmTable())
+        if build == "arithmetic":
+            if num_ops == cm.ARITH_OPS:
+                cm.gate_arithmetic(asm)
+            else:
+                for k in reversed(range(num_ops)):
+                    xy = asm.mul(cm.W(4 * k), cm.W(4 * k + 1))
+                    t = asm.mul(xy, cm.C(0))
+                    u = asm.mul(cm.W(4 * k + 2), cm.C(1))
+                    s = asm.add(t, u)
+                    d = asm.sub(cm.W(4 * k + 3), s)
+                    asm.emit(d)
+                    asm.release(xy, t, u, s, d)
+            assert asm.num_constraints == num_ops
+        else:
+            build(asm)
+            assert asm.num_constraints == num_limbs + 1 and not asm.flags & cm.GATE_EMIT_FORWARD
+        out.append((asm.words, asm.imm_table.values))
+    return out
+
+
+def test_light_gate_walk_equals_the_programs_on_the_cpu():
+    """q_arith_base_walk<true, false>, <false, true> and <true, true> - the text k_q_light runs - against the interpretation of the gates'
+    programs: operation counts and limb counts on both sides of a batch of 16 wires, both orders of 4 num_ops against num_limbs + 1,
+    with 135 wires and with exactly as many as the shape reads (the clamped loads of the top batch).  Points and challenges as for the
+    generated evaluators: random points, one of small values, one of p - 1; random alphas, then alpha = 0."""
+    import ctypes
+    import emu_lib
+    E = emu_lib.load_gates()
+    rng = np.random.default_rng(2025)
+    count, nsel = 6, 3
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    for num_ops, num_limbs in LIGHT_SHAPES:
+        progs = _light_programs(num_ops, num_limbs)
+        top = max(4 * num_ops, num_limbs + 1 if num_limbs else 0)
+        for nw in (135, top):
+            wires = rng.integers(0, P, size=(nw, count), dtype=np.uint64)
+            wires[:, 0] = rng.integers(0, 4, size=nw).astype(np.uint64)
+            wires[:, 1] = np.uint64(P - 1)
+            consts = rng.integers(0, P, size=(nsel + 2, count), dtype=np.uint64)
+            for alphas in ([int(rng.integers(1, P, dtype=np.uint64)), int(rng.integers(1, P, dtype=np.uint64))], [0, 3]):
+                al = np.array(alphas, dtype=np.uint64)
+                tag = np.uint64(2 ** 64 - 2)
+                a_alone, b_alone, a_pair, b_pair = (np.full((count, 2), tag, dtype=np.uint64) for _ in range(4))
+                E.emu_light_walk(num_ops, num_limbs, vp(wires), nw, vp(consts), nsel, count, vp(al), vp(a_alone), vp(b_alone), vp(a_pair), vp(b_pair))
+                for i in range(count):
+                    w = [int(v) for v in wires[:, i]]
+                    c = [int(v) for v in consts[nsel:, i]]
+                    for ch in range(2):
+                        for prog, alone, pair in ((progs[0], a_alone, a_pair), (progs[1], b_alone, b_pair)):
+                            where = (num_ops, num_limbs, nw, i, ch, alphas)
+                            if prog is None:
+                                assert alone[i, ch] == tag and pair[i, ch] == tag, where
+                                continue
+                            want = _interpret(prog[0], prog[1], w, c, [0] * 4, False, alphas[ch])
+                            assert int(alone[i, ch]) == want, where
+                            if num_ops and num_limbs:
+                                assert int(pair[i, ch]) == want, where
+                            else:
+                                assert pair[i, ch] == tag, where
+
+
 def test_constant_multiplication_helpers():
     import emu_lib
     E = emu_lib.load_gates()
