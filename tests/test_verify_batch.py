@@ -1,6 +1,8 @@
 """lcp2_verify_batch on the GPU: data.verify for a batch of proofs of one circuit, check 1 by k_verify_canon, checks 4 to 7 by
 k_verify_paths and k_verify_fri.  Proofs come from the oracle prover on the CPU and the expected code of every case is orc_verify's
-(verify_batch_cases.py), which lcp2_verify names too."""
+(verify_batch_cases.py), which lcp2_verify names too.  The sweeps change one word per proof across whole sections of the layout -
+k_verify_paths is GPU-only code, the emulation walks a path with one lane - and are large enough to take the chunk loop of
+verify_batch.hip past its first chunk, from device memory and from host memory."""
 import ctypes
 import re
 
@@ -45,6 +47,116 @@ def test_one_call_holds_every_case_of_a_circuit(gpu_ctx, name):
     clean = np.full(1, -9, dtype=np.int32)
     assert raw_call(m, gpu_ctx, vd, vp(proofs), proofs.shape[1], 1, m.binding.MEM_HOST, pis, pis.shape[1], clean) == OK and clean[0] == 0
     vd.close()
+
+
+SWEEPS = ([("synthetic_5", s) for s in vc.STRATA] + [("synthetic_6", s) for s in vc.STRATA]
+          + [("synthetic_9", "queries"), (vc.HIGH_RATE, "queries")])
+
+
+def wrong(labels, got, want):
+    """(how many verdicts differ, the first few as (label, got, want))"""
+    at = np.nonzero(np.asarray(got) != np.asarray(want))[0]
+    return len(at), [(labels[i], int(got[i]), int(want[i])) for i in at[:8]]
+
+
+def from_device(m, ctx, vd, proofs, pis):
+    dev = ctx.buffer_alloc(proofs.size)
+    try:
+        ctx.buffer_write(dev, proofs)
+        return ctx.verify_batch(vd, dev, pis, mem=m.binding.MEM_DEVICE, count=proofs.shape[0])
+    finally:
+        ctx.buffer_free(dev)
+
+
+def report(what, count, L, mem, want):
+    bound = vc.HOST_CHUNK if mem == "host" else min(vc.HOST_CHUNK, vc.device_chunk_bound(L))
+    print("%s: %d proofs from %s memory, at least %d chunks, codes %s" % (what, count, mem, -(-count // bound), sorted(set(int(w) for w in want))))
+
+
+@pytest.mark.parametrize("name,stratum", SWEEPS)
+def test_one_word_sweep_from_host_and_device_memory(gpu_ctx, name, stratum):
+    """a stratum of one-word changes (verify_batch_cases.sweep) in one call from host memory and one from a device buffer: every word
+    outside the queries, every word offset of a query with every word of the last query, or words >= p across the proof.  Both verdict
+    arrays equal orc_verify's codes element for element and the call returns LCP2_E_VERIFY.  The head and queries strata of
+    synthetic_6 are more device proofs than one chunk of verify_batch.hip stages."""
+    import eth_lc_plonky2_amd as m
+    circ, digest, cap, labels, proofs, pis, want = vc.sweep(name, stratum)
+    L = m.proof_layout(circ.params)
+    count = proofs.shape[0]
+    if name == "synthetic_6" and stratum != "noncanonical":
+        assert count > vc.device_chunk_bound(L)
+    vd = m.CircuitData.verifier_only(circ, digest, cap)
+    checks = np.full(count, -9, dtype=np.int32)
+    assert raw_call(m, gpu_ctx, vd, vp(proofs), proofs.shape[1], count, m.binding.MEM_HOST, pis, pis.shape[1], checks) == E_VERIFY
+    assert not wrong(labels, checks, want)[0], wrong(labels, checks, want)
+    on_device = from_device(m, gpu_ctx, vd, proofs, pis)
+    assert not wrong(labels, on_device, want)[0], wrong(labels, on_device, want)
+    report("%s %s" % (name, stratum), count, L, "host", want)
+    report("%s %s" % (name, stratum), count, L, "device", want)
+    vd.close()
+
+
+def test_device_chunks_that_fail_at_their_head_precede_live_ones(gpu_ctx):
+    """head + queries of synthetic_6 in one device buffer: the head stratum is more proofs than a chunk, so the first chunk holds
+    only proofs the host stops at checks 2 and 3 and no kernel of checks 4 to 7 runs for it; the chunks behind it are live"""
+    import eth_lc_plonky2_amd as m
+    circ, digest, cap, hl, hp, hpis, hwant = vc.sweep("synthetic_6", "head")
+    _, _, _, ql, qp, qpis, qwant = vc.sweep("synthetic_6", "queries")
+    L = m.proof_layout(circ.params)
+    bound = vc.device_chunk_bound(L)
+    assert len(hwant) >= bound and ((hwant[:bound] == 2) | (hwant[:bound] == 3)).all() and (qwant >= 4).all()
+    labels, want = hl + ql, np.concatenate([hwant, qwant])
+    proofs, pis = np.concatenate([hp, qp]), np.concatenate([hpis, qpis])
+    del hp, qp
+    vd = m.CircuitData.verifier_only(circ, digest, cap)
+    got = from_device(m, gpu_ctx, vd, proofs, pis)
+    assert not wrong(labels, got, want)[0], wrong(labels, got, want)
+    report("synthetic_6 head + queries", len(want), L, "device", want)
+    vd.close()
+
+
+TILED = 2 * vc.HOST_CHUNK + 37
+CLEAN_AT = (0, vc.HOST_CHUNK - 1, vc.HOST_CHUNK, TILED - 1)
+CHANGED_PI_AT = vc.HOST_CHUNK + 1234   # in the second chunk
+
+
+@pytest.fixture(scope="module")
+def tiled(gpu_ctx):
+    """(labels, verdicts, want) of ONE call from host memory over three chunks: the queries stratum of synthetic_5 repeated to
+    2 * 4096 + 37 proofs, the clean proof at both ends and on both sides of the first chunk boundary, and one clean proof in the second
+    chunk under public inputs of its own"""
+    import eth_lc_plonky2_amd as m
+    circ, digest, cap, labels, proofs, pis, want = vc.sweep("synthetic_5", "queries")
+    proof, pi = vc.clean("synthetic_5")
+    bad_pi, bad_pi_code = vc.changed_public_input("synthetic_5")
+    pick = np.arange(TILED) % len(want)
+    labels, proofs, pis, want = [labels[i] for i in pick], proofs[pick], pis[pick], want[pick]
+    for i in CLEAN_AT + (CHANGED_PI_AT,):
+        labels[i], proofs[i], pis[i], want[i] = "clean", proof, pi, 0
+    labels[CHANGED_PI_AT], pis[CHANGED_PI_AT], want[CHANGED_PI_AT] = "public_input", bad_pi, bad_pi_code
+    vd = m.CircuitData.verifier_only(circ, digest, cap)
+    got = gpu_ctx.verify_batch(vd, proofs, pis)
+    report("synthetic_5 queries, tiled", TILED, m.proof_layout(circ.params), "host", want)
+    vd.close()
+    return labels, got, want
+
+
+def test_host_batch_of_three_chunks(tiled):
+    """more host proofs than two chunks of 4096, the last chunk partial: every verdict is the oracle's, and exactly the four clean
+    proofs - first, last, and the two at the first chunk boundary - are accepted"""
+    labels, got, want = tiled
+    assert len(got) == TILED > 2 * vc.HOST_CHUNK
+    assert not wrong(labels, got, want)[0], wrong(labels, got, want)
+    assert all(got[i] == 0 for i in CLEAN_AT) and list(np.nonzero(got == 0)[0]) == list(CLEAN_AT)
+
+
+def test_public_inputs_of_a_proof_in_a_later_chunk(tiled):
+    """the one proof of the second chunk whose public inputs differ gets the oracle's code for that pair (its words are the clean
+    proof's), and the proofs beside it, under the circuit's public inputs, keep theirs"""
+    labels, got, want = tiled
+    i = CHANGED_PI_AT
+    assert vc.HOST_CHUNK < i < 2 * vc.HOST_CHUNK and labels[i] == "public_input" and got[i] == want[i] != 0
+    assert got[i - 1] == want[i - 1] >= 4 and got[i + 1] == want[i + 1] >= 4
 
 
 def test_prover_handle_and_verifier_only_handle_agree(gpu_ctx):

@@ -23,8 +23,8 @@ def emuv():
                             ("emu_verify_batch", c.c_int, [V, V, V, V, U, U, V, U, V, V])))
 
 
-def run_emu(E, m, name):
-    circ, digest, cap, labels, proofs, pis, want = vc.batch(name)
+def run_emu(E, m, name, cases=None):
+    circ, digest, cap, labels, proofs, pis, want = cases or vc.batch(name)
     desc, keep = m.binding._describe(circ, 0)
     dg, cp = np.ascontiguousarray(digest, dtype=np.uint64), np.ascontiguousarray(cap, dtype=np.uint64)
     k, Q = proofs.shape[0], circ.params.num_query_rounds
@@ -57,6 +57,24 @@ def test_emulated_batch_names_the_oracles_check(emuv, name):
     if "two_query_defects" in labels:  # the host stops in query 0's first layer (check 5 or 6): not at the smaller check number of query 3
         two = labels.index("two_query_defects")
         assert want[two] in (5, 6) and statuses[two][0] & 0xFF == want[two] and statuses[two][3] & 0xFF == 4
+
+
+@pytest.mark.parametrize("name,stratum", [("synthetic_6", "queries"), ("synthetic_5", "noncanonical")])
+def test_emulated_batch_over_a_one_word_sweep(emuv, name, stratum):
+    """the strata the GPU verifier is held to (verify_batch_cases.sweep), two of them here: every word offset of a query changed in
+    one proof each, and words >= p across the whole proof; every verdict is orc_verify's, and a defect inside query q leaves every
+    other query without a status"""
+    import eth_lc_plonky2_amd as m
+    cases = vc.sweep(name, stratum)
+    labels, want, checks, statuses, rejected, p = run_emu(emuv, m, name, cases)
+    wrong = [(l, int(g), int(w)) for l, g, w in zip(labels, checks, want) if g != w]
+    assert not wrong, (len(wrong), wrong[:8])
+    assert rejected == len(want) and (want != 0).all()
+    if stratum == "noncanonical":
+        assert (statuses == NONE).all()  # check 1 stops a proof before its queries
+    else:
+        for i, (j, q) in enumerate(labels):
+            assert (np.delete(statuses[i], q) == NONE).all() and statuses[i][q] & 0xFF == want[i], (j, q)
 
 
 def test_wrong_lengths_are_refused_before_anything_is_read(emuv):

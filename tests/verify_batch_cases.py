@@ -1,5 +1,7 @@
 """Shared by test_verify_batch_emu.py (CPU) and test_verify_batch.py (GPU): proofs of the circuits the suite already proves in
-seconds, made by the ORACLE prover, and the tamper cases of the batch verifier with the code orc_verify gives each of them."""
+seconds, made by the ORACLE prover, and the tamper cases of the batch verifier with the code orc_verify gives each of them: batch(), a clean
+proof and some fifteen hand-picked defects per circuit, and sweep(), one proof per changed word over whole sections of the layout."""
+import concurrent.futures
 import functools
 
 import numpy as np
@@ -26,6 +28,123 @@ def bump(m, proof, pos):
     bad = proof.copy()
     bad[pos] = np.uint64((int(bad[pos]) + 1) % m.GOLDILOCKS_P)
     return bad
+
+
+STRATA = ("head", "queries", "noncanonical")
+HIGH_RATE = "shrink_2"   # the high-rate config of the sweeps: its caps are a single digest, so a path is 14 siblings and ends at index 0
+PIN_BYTES = 4 << 20      # lcp2_ctx::PIN_BYTES (csrc/internal.hpp)
+HOST_CHUNK = 4096        # verify_batch.hip: no chunk holds more proofs
+ORACLE_THREADS = 8       # a stratum is some hundred orc_verify calls of 10 to 30 ms
+
+
+def device_chunk_bound(L):
+    """verify_batch.hip stages the words outside the queries of every device proof of a chunk in the pinned buffer: no chunk of
+    device proofs holds more than this many"""
+    return PIN_BYTES // (8 * (L.queries + L.total - L.final_poly))
+
+
+def stratum_spots(m, p, stratum):
+    """(labels, positions, None | values) of a stratum: one proof per entry, word `position` of it changed - by bump where values is
+    None.  head: every word outside the query section, label ("head", position).  queries: label (j, q), word j of query q - every
+    offset j of a query once, the query rotating with j, and every word of the last query.  noncanonical: every 16th word of the
+    proof set to p, every 16th from word 8 on to 2^64 - 1, label ("p" | "max", position)."""
+    L = m.proof_layout(p)
+    Q, qw = p.num_query_rounds, int(L.query_words)
+    if stratum == "head":
+        pos = list(range(0, L.queries)) + list(range(L.final_poly, L.total))
+        return [("head", x) for x in pos], np.array(pos, dtype=np.int64), None
+    if stratum == "queries":
+        labels = [(j, j % Q) for j in range(qw)] + [(j, Q - 1) for j in range(qw) if j % Q != Q - 1]
+        assert {j for j, q in labels} == set(range(qw)) and {q for j, q in labels} == set(range(Q)) and len(set(labels)) == len(labels)
+        return labels, np.array([L.queries + q * qw + j for j, q in labels], dtype=np.int64), None
+    assert stratum == "noncanonical"
+    at_p, at_max = list(range(0, L.total, 16)), list(range(8, L.total, 16))
+    values = np.array([m.GOLDILOCKS_P] * len(at_p) + [2 ** 64 - 1] * len(at_max), dtype=np.uint64)
+    return [("p", x) for x in at_p] + [("max", x) for x in at_max], np.array(at_p + at_max, dtype=np.int64), values
+
+
+@functools.lru_cache(maxsize=None)
+def _proved(name):
+    """(circ, digest, cap, the oracle's proof, public inputs) of circuit `name`"""
+    import eth_lc_plonky2_amd as m
+    circ, wires, pis = make_circuit(m, name)
+    oc = oracle_lib.OracleCircuit(oracle_lib.load(), circ)
+    proof = oc.prove(wires, pis)
+    assert oc.verify(proof, pis) == 0
+    digest, cap = oc.digest()
+    oc.close()
+    proof.setflags(write=False)
+    return circ, digest, cap, proof, np.ascontiguousarray(pis, dtype=np.uint64)
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_codes(name, stratum):
+    """(labels, positions, values, want) of a stratum of circuit `name`: what costs oracle time, kept for the session; the proofs
+    themselves (a hundred megabytes and more per stratum) are written out per call of sweep()"""
+    import eth_lc_plonky2_amd as m
+    circ, digest, cap, proof, pis = _proved(name)
+    p = circ.params
+    labels, pos, values = stratum_spots(m, p, stratum)
+    if values is None:
+        values = proof[pos] + np.uint64(1)  # proof words are < p < 2^64 - 1
+        values[values == np.uint64(m.GOLDILOCKS_P)] = 0
+    assert (values != proof[pos]).all()
+    ov = oracle_lib.OracleCircuit.verifier_only(oracle_lib.load(), circ, digest, cap)
+    want = np.zeros(len(labels), dtype=np.int32)
+
+    def codes(mine):  # orc_verify keeps its state on its stack and ctypes drops the GIL for the call: the cases go over threads
+        work = proof.copy()
+        for i in mine:
+            work[pos[i]] = values[i]
+            want[i] = ov.verify(work, pis)
+            work[pos[i]] = proof[pos[i]]
+    with concurrent.futures.ThreadPoolExecutor(ORACLE_THREADS) as pool:
+        list(pool.map(codes, [range(k, len(labels), ORACLE_THREADS) for k in range(ORACLE_THREADS)]))
+    ov.close()
+    bad = [(l, int(w)) for l, w in zip(labels, want) if w == 0]
+    assert not bad, (name, stratum, bad[:8])  # a case is valid only if the oracle alone rejects it
+    if stratum == "noncanonical":
+        assert (want == 1).all(), (name, [(l, int(w)) for l, w in zip(labels, want) if w != 1][:8])
+    if stratum == "queries":
+        L = m.proof_layout(p)
+        assert sorted({j for j, q in labels}) == list(range(L.query_words))  # no part of the layout has been dropped
+        assert set(want) >= ({4, 5, 6} if p.num_fri_layers else {4}), (name, sorted(set(want)))
+    for a in (pos, values, want):
+        a.setflags(write=False)
+    return labels, pos, values, want
+
+
+def sweep(name, stratum):
+    """(circ, digest, cap, labels, proofs (k, proof_words), public inputs (k, npi), want (k,) int32) of a stratum (STRATA,
+    stratum_spots) of circuit `name`: k copies of the oracle's proof with one word changed each; want[i] is orc_verify's code, never 0.
+    Read-only."""
+    circ, digest, cap, proof, pis = _proved(name)
+    labels, pos, values, want = _sweep_codes(name, stratum)
+    proofs = np.repeat(proof[None, :], len(labels), axis=0)
+    proofs[np.arange(len(labels)), pos] = values
+    pis_all = np.repeat(pis[None, :], len(labels), axis=0)
+    for a in (proofs, pis_all):
+        a.setflags(write=False)
+    return circ, digest, cap, labels, proofs, pis_all, want
+
+
+@functools.lru_cache(maxsize=None)
+def changed_public_input(name):
+    """(public inputs with one bit changed, orc_verify's code for them with the clean proof)"""
+    circ, digest, cap, proof, pis = _proved(name)
+    bad_pis = pis.copy()
+    bad_pis[1] ^= np.uint64(2)
+    ov = oracle_lib.OracleCircuit.verifier_only(oracle_lib.load(), circ, digest, cap)
+    code = ov.verify(proof, bad_pis)
+    ov.close()
+    assert code != 0
+    bad_pis.setflags(write=False)
+    return bad_pis, code
+
+
+def clean(name):
+    """(the oracle's proof, its public inputs) of circuit `name`: orc_verify accepts them"""
+    return _proved(name)[3:]
 
 
 @functools.lru_cache(maxsize=None)
