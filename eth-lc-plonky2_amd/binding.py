@@ -102,6 +102,22 @@ class WitnessPlan(ctypes.Structure):
 _lib = None
 
 
+class WitnessReport(ctypes.Structure):
+    """lcp2_witness_report: what lcp2_check_witness found (include/lcp2.h)"""
+    _fields_ = [("gate_violations", ctypes.c_uint64), ("gate_row", ctypes.c_uint64), ("gate_index", ctypes.c_uint32), ("gate_constraint", ctypes.c_uint32),
+                ("copy_violations", ctypes.c_uint64), ("copy_row", ctypes.c_uint64), ("copy_wire", ctypes.c_uint32),
+                ("copy_to_row", ctypes.c_uint64), ("copy_to_wire", ctypes.c_uint32), ("noncanonical_cells", ctypes.c_uint64)]
+    per_gate = None   # gate_violations split by gate (numpy, num_gates), when it was asked for
+
+    @property
+    def ok(self):
+        """no gate and no copy violation"""
+        return self.gate_violations == 0 and self.copy_violations == 0
+
+    def __repr__(self):
+        return "WitnessReport(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
 class ChallengerState(ctypes.Structure):
     """lcp2_challenger: plonky2's Challenger { sponge_state, input_buffer, output_buffer } by value"""
     _fields_ = [("sponge", ctypes.c_uint64 * 12), ("input", ctypes.c_uint64 * 8), ("output", ctypes.c_uint64 * 8),
@@ -190,6 +206,7 @@ def load_library():
         "lcp2_proof_words": (c.c_size_t, [c.POINTER(Params)]),
         "lcp2_proof_layout_of": (c.c_int, [c.POINTER(Params), c.POINTER(ProofLayout)]),
         "lcp2_prove": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]),
+        "lcp2_check_witness": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_size_t, c.POINTER(WitnessReport), c.c_void_p, c.c_uint32]),
         "lcp2_commit_wires": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]),
         "lcp2_commit_wires_coeffs": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]),
         "lcp2_commit_wires_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]),
@@ -779,6 +796,24 @@ class CircuitData:
             wp = ctypes.c_void_p(wires)
         self._check(self.lib.lcp2_prove(self.handle, wp, mem, _ptr(pis), pis.size, _ptr(proof), proof.size))
         return proof
+
+    def check_witness(self, wires, public_inputs, per_gate=False, mem=MEM_HOST):
+        """lcp2_check_witness: where the witness violates gate and copy constraints, exactly (wires as for prove).  Returns a
+        WitnessReport; per_gate=True also fills report.per_gate, the gate violations split by gate."""
+        pis = _np_u64(public_inputs).ravel()
+        if mem == MEM_HOST:
+            w = _np_u64(wires)
+            if w.shape != (self.circ.params.num_wires, 1 << self.circ.params.degree_bits):
+                raise Lcp2Error(-1, "witness must be [num_wires][n]")
+            wp = _ptr(w)
+        else:
+            wp = ctypes.c_void_p(wires)
+        report = WitnessReport()
+        ng = len(self.circ.gateset.gates)
+        counts = np.zeros(ng, dtype=np.uint64) if per_gate else None
+        self._check(self.lib.lcp2_check_witness(self.handle, wp, mem, _ptr(pis), pis.size, ctypes.byref(report), _ptr(counts), ng))
+        report.per_gate = counts
+        return report
 
     # ---- host witnesses with the upload off the critical path (lcp2_witness_stage / lcp2_prove_staged)
     def stage_witness(self, wires, slot):

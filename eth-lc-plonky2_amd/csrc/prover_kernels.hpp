@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <vector>
+#include "gate_staging.hpp"
 #include "gl64.hpp"
 #include "ntt.hpp"
 
@@ -11,16 +12,10 @@ namespace lcp2 {
 constexpr u32 PERM_MAX_CHUNKS = 10;   // ceil(80 routed wires / quotient degree factor 8)
 constexpr u32 QUOTIENT_THREADS = 128;
 constexpr u32 QUOTIENT_MAX_CH = 2;
-// Operand staging of the gate-program interpreter (device-side form of the programs, made by stage_gate_programs at build()):
-// every WIRE / CONST operand is fetched by an LDG instruction that issues up to QUOTIENT_STAGE column loads back to back and
-// parks the values in LDS slots; the instructions after it read kind STAGE.  One exposed HBM round trip per 16 operands
-// instead of one per operand (the interpreter executes one instruction at a time, so an operand load cannot overlap anything).
-constexpr u32 QUOTIENT_STAGE = 12;
+// (QUOTIENT_STAGE and the staged encoding of the gate programs: gate_staging.hpp)
 constexpr u32 QUOTIENT_ALPHA_POWS = 32; // >= CH + CH * PERM_MAX_CHUNKS + 1 exponents
 constexpr u32 QUOTIENT_TERM_POWS = 128; // alpha^e, e < 128, as 22-bit limbs: the constraint weights of the generated gates (at most 128 constraints)
 constexpr u32 QUOTIENT_GENERATED_GATES = 17; // programs in csrc/generated_gates*.hpp (static_assert-ed against the index file)
-constexpr u32 QOP_LDG = 10;      // w0 = 10 | count << 8, w1 = offset into stage_list
-constexpr u32 QKIND_STAGE = 5;   // operand = staging slot idx
 constexpr u32 EVAL_CHUNK = 4096;
 
 // word offsets inside lcp2_circuit::small (per-proof scalars on the device)

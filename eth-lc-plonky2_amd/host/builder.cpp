@@ -925,6 +925,50 @@ ProofWithPublicInputs CircuitData::prove(const PartialWitness &pw) {
   return out;
 }
 
+// ---- where a witness is wrong (lcp2_check_witness): the report as text, the gate under the builder's own name
+std::string CircuitData::describe_report(const lcp2_witness_report &r) const {
+  if (r.gate_violations == 0 && r.copy_violations == 0) return "the witness satisfies every gate and copy constraint";
+  auto cell = [](uint64_t row, uint32_t wire) { return "(" + std::to_string(row) + ", " + std::to_string(wire) + ")"; };
+  std::string text;
+  if (r.gate_violations) {
+    const char *name = r.gate_index < desc_.gates.size() && r.gate_index < G_COUNT ? gate_name(r.gate_index) : "gate ?";
+    text = "row " + std::to_string(r.gate_row) + ", gate " + name + ", constraint " + std::to_string(r.gate_constraint) + " (" +
+           std::to_string(r.gate_violations) + " gate constraints violated)";
+  }
+  if (r.copy_violations) {
+    if (!text.empty()) text += "; ";
+    text += "copy constraint " + cell(r.copy_row, r.copy_wire) + " != " +
+            (r.copy_to_wire == 0xFFFFFFFFu ? std::string("(no cell: the sigma value is no cell id)") : cell(r.copy_to_row, r.copy_to_wire)) + " (" +
+            std::to_string(r.copy_violations) + " cells)";
+  }
+  return text;
+}
+
+static std::string diagnose_on_device(lcp2_ctx *ctx, lcp2_circuit *gpu, const CircuitData &data, const uint64_t *wires, lcp2_mem mem,
+                                      const std::vector<F> &public_inputs) {
+  lcp2_witness_report report;
+  const int rc = lcp2_check_witness(gpu, wires, mem, public_inputs.data(), public_inputs.size(), &report, nullptr, 0);
+  if (rc != LCP2_OK) throw std::runtime_error(std::string("lcp2_check_witness: ") + lcp2_status_str(rc) + " (" + lcp2_last_error(ctx) + ")");
+  return data.describe_report(report);
+}
+
+std::string CircuitData::diagnose_witness(const std::vector<uint64_t> &wires, const std::vector<F> &public_inputs) const {
+  if (!impl_->gpu) throw std::runtime_error("CircuitData::diagnose_witness needs attach_gpu(): the check runs on the device");
+  if (wires.size() != (size_t)desc_.params.num_wires << desc_.params.degree_bits) throw std::runtime_error("CircuitData::diagnose_witness: the witness must be [num_wires][n]");
+  return diagnose_on_device(impl_->ctx, impl_->gpu, *this, wires.data(), LCP2_MEM_HOST, public_inputs);
+}
+
+std::string CircuitData::diagnose(const PartialWitness &pw) {
+  if (!impl_->gpu) throw std::runtime_error("CircuitData::diagnose needs attach_gpu(): the check runs on the device");
+  std::vector<F> public_inputs;
+  try {
+    generate_witness_gpu(pw, public_inputs);  // the witness stays in HBM
+  } catch (const UnsatisfiedError &e) {
+    return std::string("witness generation: ") + e.what();  // the generators' own finding: there is no complete witness to check
+  }
+  return diagnose_on_device(impl_->ctx, impl_->gpu, *this, (const uint64_t *)impl_->d_wires, LCP2_MEM_DEVICE, public_inputs);
+}
+
 void CircuitData::verify(const ProofWithPublicInputs &proof) const {
   const lcp2_circuit *c = impl_->gpu ? impl_->gpu : impl_->verifier;
   if (!c) throw std::runtime_error("CircuitData::verify needs the circuit digest: attach_gpu() first");

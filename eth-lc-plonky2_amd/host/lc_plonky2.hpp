@@ -168,6 +168,15 @@ class CircuitData {
   // remaining cells are scattered from the host; leaves the witness in the circuit's device buffer
   void generate_witness_gpu(const PartialWitness &pw, std::vector<F> &public_inputs);
   void read_device_witness(std::vector<uint64_t> &wires) const;   // test helper: copy of the device witness matrix
+  // WHERE a witness is wrong (lcp2_check_witness on the attached circuit), as text that names the gate by the builder's own name:
+  //   "row R, gate ArithmeticGate, constraint i (N gate constraints violated); copy constraint (row, wire) != (row', wire') (M cells)"
+  // or "the witness satisfies every gate and copy constraint".  diagnose(pw) runs the generators first (the witness stays in HBM); a
+  // conflict they find themselves is returned as their own message.  diagnose_witness takes a full wire matrix [num_wires][n] in host
+  // memory - a witness the generators did not make.  Both need attach_gpu (std::runtime_error otherwise: the check runs on the device,
+  // there is no CPU form of it); describe_report is the text of a report alone and needs nothing.
+  std::string diagnose(const PartialWitness &pw);
+  std::string diagnose_witness(const std::vector<uint64_t> &wires, const std::vector<F> &public_inputs) const;
+  std::string describe_report(const lcp2_witness_report &report) const;
   void verify(const ProofWithPublicInputs &proof) const;          // data.verify(proof): host only
   // data.verify for `count` proofs at once on the attached context (lcp2_verify_batch): proofs = count * proof words, public_inputs
   // = count * the circuit's public inputs, failed_checks[i] = 0 or the check proof i fails.  Returns whether every proof is accepted

@@ -492,6 +492,41 @@ int lcp2_proof_layout_of(const lcp2_params *p, lcp2_proof_layout *out);
 int lcp2_prove(lcp2_circuit *c, const uint64_t *wires, lcp2_mem wires_mem, const uint64_t *public_inputs, size_t num_public_inputs,
                uint64_t *proof, size_t proof_words);
 
+/* WHERE a witness violates the circuit (plonky2 names the failing gate and the partition that was "set twice with different
+ * values"; lcp2_prove only says LCP2_E_UNSAT).  Exact, on the device, over all n rows: no challenge enters, every constraint is
+ * looked at on its own and every comparison is made on canonical values.
+ *   gates   the row's own gates are those g with constants[selector_index_g][row] == selector_value_g, in index order; each of their
+ *           constraints is evaluated UNFILTERED by walking the gate's program (never a native evaluator: those give alpha-sums).
+ *   copies  routed cell (wire j, row r) is tied to the cell (j', r') whose id k_is[j'] w^r' is the value sigma_j(w^r); j' and r' are
+ *           recovered from the value itself (its n-th power names the coset, a discrete logarithm in H the row), for any k_is in
+ *           distinct cosets.  A cell that is its own sigma image is tied to nothing.  A sigma value that is the id of no cell counts
+ *           as a violation of that cell.
+ * wires: [num_wires][n] column-major, any u64; a host witness is uploaded into scratch of the context, a device witness is read in
+ * place and never written.  per_gate (nullable, host): num_gates counters, gate_violations split by gate; num_gates is looked at
+ * only with per_gate and must then be the circuit's gate count.
+ * LCP2_OK whenever the check ran - violations are data, not an error.  LCP2_E_INVALID: null c / wires / report, a wrong
+ * num_public_inputs or num_gates.  LCP2_E_NODEVICE: a verifier-only handle.  LCP2_E_UNSUPPORTED: a sharded handle (it holds only its
+ * own blocks), a circuit with 2^16 gates or a gate with 2^16 constraints or more.
+ * The proving state of the handle is left alone: the call may come between any two other calls, also between the seams of a proof
+ * in flight, and a proof made after it equals one made without it.  The context's stream is synchronised on return.
+ * Timing (lcp2_prof_*): there is no family of its own; the gate pass is booked under LCP2_K_QUOTIENT and the copy pass under
+ * LCP2_K_PERM_Z, one launch each - a caller that profiles proofs should reset or read the timers around the call. */
+typedef struct {
+  uint64_t gate_violations;      /* (row, constraint) pairs whose unfiltered constraint of the row's own gate is non-zero */
+  uint64_t gate_row;             /* the first such pair in (row, gate, constraint) order; ~0 if none */
+  uint32_t gate_index;           /* index into desc->gates */
+  uint32_t gate_constraint;      /* plonky2's constraint index within the gate: a program without LCP2_GATE_EMIT_FORWARD lists its
+                                    constraints last to first, so index = num_constraints - 1 - emission order */
+  uint64_t copy_violations;      /* routed cells whose canonical value differs from that of the cell their sigma value names */
+  uint64_t copy_row;             /* the first such cell in (row, wire) order; row ~0 if none */
+  uint32_t copy_wire;
+  uint64_t copy_to_row;          /* the cell it is tied to; wire 0xFFFFFFFF (row ~0) if the sigma value is no cell id */
+  uint32_t copy_to_wire;
+  uint64_t noncanonical_cells;   /* witness words >= p (informational) */
+} lcp2_witness_report;
+int lcp2_check_witness(lcp2_circuit *c, const uint64_t *wires, lcp2_mem wires_mem, const uint64_t *public_inputs, size_t num_public_inputs,
+                       lcp2_witness_report *report, uint64_t *per_gate, uint32_t num_gates);
+
 /* ---- a HOST witness without its upload on the critical path.  data.prove(pw) of a fork that runs plonky2's own generators ends up with
  * the full witness in host memory (4.5 GB at n = 2^22); lcp2_prove(.., LCP2_MEM_HOST, ..) copies it first and proves afterwards.  For a
  * sequence of proofs (BASELINE configs[4]: a batch of updates) the copy of witness i + 1 runs while proof i is computed:
