@@ -118,6 +118,16 @@ class WitnessReport(ctypes.Structure):
         return "WitnessReport(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
 
 
+class FillReport(ctypes.Structure):
+    """lcp2_fill_report: what lcp2_witness_fill_copies did (include/lcp2.h)"""
+    _fields_ = [(f, ctypes.c_uint64) for f in ("num_classes", "classes_set", "cells_filled", "conflicts", "conflict_index", "owner_index")]
+    unsat = False   # the call returned LCP2_E_UNSAT: conflicts > 0, the classes hold their owners' values
+    message = ""    # lcp2_last_error of such a call: both list indices, both cells
+
+    def __repr__(self):
+        return "FillReport(%s, unsat=%s)" % (", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_), self.unsat)
+
+
 class ChallengerState(ctypes.Structure):
     """lcp2_challenger: plonky2's Challenger { sponge_state, input_buffer, output_buffer } by value"""
     _fields_ = [("sponge", ctypes.c_uint64 * 12), ("input", ctypes.c_uint64 * 8), ("output", ctypes.c_uint64 * 8),
@@ -206,6 +216,8 @@ def load_library():
         "lcp2_proof_words": (c.c_size_t, [c.POINTER(Params)]),
         "lcp2_proof_layout_of": (c.c_int, [c.POINTER(Params), c.POINTER(ProofLayout)]),
         "lcp2_prove": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]),
+        "lcp2_witness_fill_copies": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.POINTER(FillReport)]),
+        "lcp2_circuit_copy_classes": (c.c_int, [c.c_void_p, c.c_void_p, c.POINTER(c.c_uint64)]),
         "lcp2_check_witness": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_size_t, c.POINTER(WitnessReport), c.c_void_p, c.c_uint32]),
         "lcp2_commit_wires": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]),
         "lcp2_commit_wires_coeffs": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]),
@@ -814,6 +826,35 @@ class CircuitData:
         self._check(self.lib.lcp2_check_witness(self.handle, wp, mem, _ptr(pis), pis.size, ctypes.byref(report), _ptr(counts), ng))
         report.per_gate = counts
         return report
+
+    def fill_copies(self, cells, wires_ptr, mem=MEM_HOST, ncells=None):
+        """lcp2_witness_fill_copies: every record of `cells` is written into the device matrix `wires_ptr` ([num_wires][n]), and the
+        listed cell with the smallest list index of each copy class gives its value to every routed cell of the class.  cells: a numpy
+        array of CELL_DTYPE records, or with mem=MEM_DEVICE a device pointer to `ncells` lcp2_cell records.  Returns the FillReport;
+        conflicting values (LCP2_E_UNSAT) do not raise: report.unsat is set and report.message names the cells.  Every other status
+        raises Lcp2Error."""
+        if mem == MEM_HOST:
+            if not isinstance(cells, np.ndarray) or cells.dtype != CELL_DTYPE:
+                raise Lcp2Error(-1, "cells must be an array of CELL_DTYPE records")
+            c = np.ascontiguousarray(cells).ravel()
+            p, count = (_ptr(c) if c.size else None), c.size
+        else:
+            p, count = ctypes.c_void_p(cells), int(ncells)
+        report = FillReport()
+        rc = self.lib.lcp2_witness_fill_copies(self.handle, p, count, mem, ctypes.c_void_p(wires_ptr), ctypes.byref(report))
+        if rc == E_UNSAT:
+            report.unsat = True
+            report.message = self.lib.lcp2_last_error(self.ctx.handle).decode()
+        else:
+            self._check(rc)
+        return report
+
+    def copy_classes(self):
+        """lcp2_circuit_copy_classes: (class_of [num_routed_wires][n] uint32 - 0xFFFFFFFF for a cell in no class -, num_classes)"""
+        NR, n = self.circ.params.num_routed_wires, 1 << self.circ.params.degree_bits
+        class_of, count = np.zeros((NR, n), dtype=np.uint32), ctypes.c_uint64()
+        self._check(self.lib.lcp2_circuit_copy_classes(self.handle, _ptr(class_of), ctypes.byref(count)))
+        return class_of, count.value
 
     # ---- host witnesses with the upload off the critical path (lcp2_witness_stage / lcp2_prove_staged)
     def stage_witness(self, wires, slot):

@@ -513,3 +513,86 @@ def tag_witness(wires, tag):
     constraint, identity permutation).  Used to give every rank / update of a batch a proof of its own."""
     wires[100:, -1] = np.uint64(int(tag) % gl.P)
     return wires
+
+
+# ---------------------------------------------------------------- copy classes: the numpy model of lcp2_witness_fill_copies
+NO_CLASS = 0xFFFFFFFF
+
+
+def copy_next_cells(circ):
+    """next[cell] for every routed cell (cell = wire * n + row): the cell whose id k_j' w^r' the sigma value is, looked up in the sorted
+    table of all ids - no discrete logarithm.  Raises ValueError when the sigma columns are no permutation of the cell ids."""
+    n, NR, NC = circ.n, circ.params.num_routed_wires, circ.params.num_constants
+    sub = gl.powers(gl.root_of_unity(circ.params.degree_bits), n)
+    ids = np.concatenate([gl.mul(gl.canon(circ.k_is[j]), sub) for j in range(NR)])
+    order = np.argsort(ids, kind="stable")
+    sorted_ids = ids[order]
+    sig = gl.canon(circ.constants_sigmas[NC:NC + NR, :n]).ravel()
+    at = np.minimum(np.searchsorted(sorted_ids, sig), ids.size - 1)
+    if not (sorted_ids[at] == sig).all():
+        raise ValueError("a sigma value is the id of no cell")
+    nxt = order[at]
+    if np.unique(nxt).size != nxt.size:
+        raise ValueError("two cells have the same image")
+    return nxt
+
+
+def copy_classes_model(circ):
+    """(class_of [num_routed_wires][n] uint32, num_classes): union-find over cell -> next cell.  A class is a cycle of more than one
+    cell; the classes are numbered in ascending order of their smallest cell, NO_CLASS marks a cell that is its own image."""
+    nxt = copy_next_cells(circ)
+    parent = np.arange(nxt.size)
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for cell in np.nonzero(nxt != parent)[0]:
+        a, b = find(int(cell)), find(int(nxt[cell]))
+        if a != b:
+            parent[max(a, b)] = min(a, b)   # the root of a set is its smallest cell
+    root = np.array([find(int(x)) for x in range(nxt.size)])
+    alone = nxt == np.arange(nxt.size)
+    roots = np.unique(root[~alone])
+    class_of = np.full(nxt.size, NO_CLASS, dtype=np.uint32)
+    class_of[~alone] = np.searchsorted(roots, root[~alone]).astype(np.uint32)
+    return class_of.reshape(circ.params.num_routed_wires, circ.n), int(roots.size)
+
+
+def fill_copies_model(circ, cells, wires, class_of=None):
+    """lcp2_witness_fill_copies on a host matrix `wires` [num_wires][n] (changed in place).  cells: records with row, col, value (the
+    binding's CELL_DTYPE).  Returns a dict with the fields of lcp2_fill_report, `refused` (the index of the first entry out of range, or
+    None; such entries do nothing) and `status` (0, -1 refused, -5 conflicts).  Two entries for one cell in no class: the later wins
+    here, the library leaves either."""
+    n, W, NR = circ.n, circ.params.num_wires, circ.params.num_routed_wires
+    if class_of is None:
+        class_of = copy_classes_model(circ)[0]
+    num_classes = int(class_of[class_of != NO_CLASS].max()) + 1 if (class_of != NO_CLASS).any() else 0
+    owner, listed, refused = {}, set(), None
+    for i, c in enumerate(cells):
+        row, col = int(c["row"]), int(c["col"])
+        if row >= n or col >= W:
+            refused = i if refused is None else refused
+            continue
+        wires[col, row] = c["value"]
+        if col < NR and class_of[col, row] != NO_CLASS:
+            owner.setdefault(int(class_of[col, row]), i)
+            listed.add((col, row))
+    filled = 0
+    for cls, i in owner.items():
+        member = class_of == cls
+        wires[:NR][member] = cells[i]["value"]
+        filled += int(member.sum())
+    conflicts = []
+    for i, c in enumerate(cells):
+        row, col = int(c["row"]), int(c["col"])
+        if row < n and col < NR and class_of[col, row] != NO_CLASS:
+            if int(c["value"]) % gl.P != int(cells[owner[int(class_of[col, row])]]["value"]) % gl.P:
+                conflicts.append(i)
+    none = (1 << 64) - 1
+    first = conflicts[0] if conflicts else none
+    return dict(num_classes=num_classes, classes_set=len(owner), cells_filled=filled - len(listed), conflicts=len(conflicts), conflict_index=first,
+                owner_index=owner[int(class_of[int(cells[first]["col"]), int(cells[first]["row"])])] if conflicts else none,
+                refused=refused, status=-1 if refused is not None else (-5 if conflicts else 0))

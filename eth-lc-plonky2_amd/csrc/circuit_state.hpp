@@ -79,6 +79,11 @@ struct lcp2_circuit {
   hipEvent_t wit_ready[2] = {nullptr, nullptr};  // the slot's upload has finished (recorded on the context's copy stream)
   bool wit_staged[2] = {false, false};
   ~lcp2_circuit() { for (hipEvent_t e : wit_ready) if (e) (void)hipEventDestroy(e); }
+  // lcp2_witness_fill_copies (witness_fill.hip): the copy classes read back from the sigma columns, built at the first call
+  DevBuf copy_class_of;              // [num_routed_wires][n] u32: the class of a routed cell, 0xFFFFFFFF for a cell that is its own image
+  u64 copy_num_classes = 0;
+  uint32_t copy_rounds = 0;          // pointer-jumping rounds that lowered a label while the table was built
+  bool copy_classes_ready = false;
   bool check_pending = false;  // the gate-check verdict of stage_quotient_values has not been read yet (it arrives with the quotient cap)
   uint32_t world() const { return bc ? (1u << p.rate_bits) / bc : 1; }
   // q = ceil(log2 Q): K6 evaluates the quotient on the 2^q n-point coset 7 H_{2^q n}, the first 2^q n leaves of every LDE
@@ -188,6 +193,9 @@ struct StageEnv {
         nchunks(npp + 1), ncs(NC + NR), L(p), s(ctx->stream), be{ctx}, ntt(be) {}
 };
 
+// ---- witness_check.hip: the cell-id decode tables of this circuit on the device (witness_check.hpp WcDecode), cached in the context
+struct WcDecode;
+int wc_device_decode(lcp2_circuit *c, StageEnv &e, WcDecode *out);
 // ---- prover_stages.hip: each is a function of its inputs and of the commitments made by the stages before it
 int stage_wires(lcp2_circuit *c, const u64 *wires_in, lcp2_mem wires_mem, const u64 *d_coeffs, u64 *cap_out, bool rows_only = false);
 int perm_begin(lcp2_circuit *c, const u64 *betas, const u64 *gammas);

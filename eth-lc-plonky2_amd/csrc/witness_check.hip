@@ -170,6 +170,24 @@ extern "C" int lcp2_check_witness(lcp2_circuit *c, const uint64_t *wires, lcp2_m
 }
 
 namespace lcp2 {
+// the decode tables of this circuit on the device (cached in the context under the k_is): also what lcp2_witness_fill_copies decodes with
+int wc_device_decode(lcp2_circuit *c, StageEnv &e, WcDecode *out) {
+  const u32 NR = e.NR, d = e.p.degree_bits;
+  std::string kis_key = "wckis:" + std::to_string(d);
+  for (u64 k : c->k_is) kis_key += ":" + std::to_string(k);
+  const u64 *d_tables = e.be.table(kis_key, [&] {
+    std::vector<u64> t(2 * (size_t)NR);
+    wc_decode_tables(c->k_is.data(), NR, d, t.data());
+    return t;
+  });
+  WcDecode t{};
+  t.roots = e.ntt.root_table(d, false);
+  if (e.be.status) return e.be.status;
+  t.kn = d_tables; t.kinv = d_tables + NR; t.num_routed = NR; t.degree_bits = d;
+  *out = t;
+  return LCP2_OK;
+}
+
 int check_witness_run(lcp2_circuit *c, const u64 *wires, lcp2_mem wires_mem, const uint64_t *public_inputs, size_t num_public_inputs,
                       lcp2_witness_report *report, uint64_t *per_gate) {
   lcp2_ctx *ctx = c->ctx;
@@ -214,17 +232,8 @@ int check_witness_run(lcp2_circuit *c, const u64 *wires, lcp2_mem wires_mem, con
   }
   // ---- copy constraints, and the words >= p
   const u64 *d_sigmas = c->cs_values.u() + (u64)NC * n;
-  std::string kis_key = "wckis:" + std::to_string(d);
-  for (u64 k : c->k_is) kis_key += ":" + std::to_string(k);
-  const u64 *d_tables = e.be.table(kis_key, [&] {
-    std::vector<u64> t(2 * (size_t)NR);
-    wc_decode_tables(c->k_is.data(), NR, d, t.data());
-    return t;
-  });
   WcDecode t{};
-  t.roots = e.ntt.root_table(d, false);
-  if (e.be.status) return e.be.status;
-  t.kn = d_tables; t.kinv = d_tables + NR; t.num_routed = NR; t.degree_bits = d;
+  LCP2_TRY(wc_device_decode(c, e, &t));
   {
     ProfScope ps(ctx, LCP2_K_PERM_Z, (double)n * 8.0 * (W + NR));
     hipLaunchKernelGGL(k_witness_copies, dim3((unsigned)((n + 255) / 256), W), dim3(256), 0, s, d_wires, d_sigmas, c->d_kis.u(), t, n, res);

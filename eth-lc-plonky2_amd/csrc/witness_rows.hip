@@ -1,10 +1,11 @@
 // Witness-row entry points of liblcp2.so (K10): lcp2_sha256_witness, lcp2_scatter_cells, lcp2_poseidon_gate_rows,
 // lcp2_u32_gate_rows, lcp2_rec_gate_rows and lcp2_witness_plan_rows, with the device scratch, the host-to-device staging and the
-// refusal flag they share.  The last two check their arguments and run one level runner (run_plan_rows): a rec-gate call is a plan
-// without PoseidonGate chains.  The kernels are in kernels_witness.hip; the per-row texts in sha_rows.hpp, pos_rows.hpp,
+// refusal flag they share (row_stage.hpp, which lcp2_witness_fill_copies uses too).  The last two check their arguments and run one
+// level runner (run_plan_rows): a rec-gate call is a plan without PoseidonGate chains.  The kernels are in kernels_witness.hip; the per-row texts in sha_rows.hpp, pos_rows.hpp,
 // u32_rows.hpp, rec_rows.hpp and pos_plan.hpp.
 #include <cstring>
 #include "internal.hpp"
+#include "row_stage.hpp"
 #include "sha_layout.hpp"
 #include "sha_rows.hpp"
 #include "pos_rows.hpp"
@@ -30,68 +31,6 @@ int scratch_ensure(lcp2_ctx *ctx, int slot, size_t bytes, void **out) {
 }  // namespace lcp2
 
 namespace {
-// Host -> device staging of one call through the context's pinned buffer (a copy out of pinned memory is a plain DMA that the
-// stream orders).  The buffer is free when a call begins: every entry point here waits for its transfers before it returns.
-struct Stage {
-  lcp2_ctx *ctx;
-  size_t used = 0;  // bytes of the pinned buffer this call has handed out
-  // the next `bytes` bytes of the pinned buffer, nullptr when they do not fit (or there is no buffer)
-  char *room(size_t bytes) const { return ctx->pin && used + bytes <= lcp2_ctx::PIN_BYTES ? (char *)ctx->pin + used : nullptr; }
-  // Behind what this call already staged, else from the caller's memory: `src` must stay until the stream is synchronised.
-  // via_pin = false: never through the pinned buffer, for a list that goes up in pieces (the buffer serves one transfer per
-  // call, and the copy of an earlier piece may still be reading it)
-  int behind(void *dst, const void *src, size_t bytes, bool via_pin = true) {
-    char *p = via_pin ? room(bytes) : nullptr;
-    if (p) { memcpy(p, src, bytes); used += (bytes + 63) & ~(size_t)63; }
-    LCP2_HIP(ctx, hipMemcpyAsync(dst, p ? p : src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return LCP2_OK;
-  }
-  // Whole payload through the whole pinned buffer, in pieces of its size: `src` is reusable on return, and so is the buffer for
-  // the next call of whole(), which first waits for the copy this one left in flight.  Not to be mixed with behind() in one call
-  int whole(void *dst, const void *src, size_t bytes) {
-    if (!ctx->pin) {
-      LCP2_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-      LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      return LCP2_OK;
-    }
-    for (size_t at = 0; at < bytes; at += lcp2_ctx::PIN_BYTES) {
-      const size_t piece = std::min(lcp2_ctx::PIN_BYTES, bytes - at);
-      LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the copy out of the staging buffer that may still be in flight
-      memcpy(ctx->pin, (const char *)src + at, piece);
-      LCP2_HIP(ctx, hipMemcpyAsync((char *)dst + at, ctx->pin, piece, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return LCP2_OK;
-  }
-};
-
-// The refusal flag of a call whose kernels validate jobs (row_flag.hpp), in scratch slot 1: one word, or the two of a plan
-struct RefusalFlag {
-  lcp2_ctx *ctx;
-  size_t nwords = 1;
-  u64 *d = nullptr;
-  u64 words[2] = {0, 0};
-  int begin() {
-    LCP2_TRY(scratch_ensure(ctx, 1, nwords * sizeof(u64), (void **)&d));
-    LCP2_HIP(ctx, hipMemsetAsync(d, 0xFF, nwords * sizeof(u64), ctx->stream));  // ROW_NO_PROBLEM
-    return LCP2_OK;
-  }
-  // after the last launch: launch errors first, then the words come back and the stream is waited for (the caller's lists may go;
-  // every cell is written)
-  int read() {
-    LCP2_HIP(ctx, hipGetLastError());
-    LCP2_HIP(ctx, hipMemcpyAsync(words, d, nwords * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    LCP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LCP2_OK;
-  }
-  // read() of one word.  A refusal is LCP2_E_INVALID, "<family>: job N: <reason> (found on the device: <written>)"
-  int end(const char *family, const char *(*reason)(u32), const char *written) {
-    LCP2_TRY(read());
-    if (words[0] == ROW_NO_PROBLEM) return LCP2_OK;
-    return ctx->fail(LCP2_E_INVALID, std::string(family) + ": job " + std::to_string(words[0] >> 8) + ": " + reason((u32)(words[0] & 0xFF)) +
-                                         " (found on the device: " + written + ")");
-  }
-};
-
 // A table of ascending ends over `total` records, as level_ends, rec_level_ends, pos_level_ends and a host chain_ends must be:
 // ENDS_OK, or the first entry below the one before it or above `total`, or `count` where the table does not end at `total`
 constexpr size_t ENDS_OK = ~(size_t)0;

@@ -872,10 +872,19 @@ void CircuitData::generate_witness_gpu(const PartialWitness &pw, std::vector<F> 
   // the cells of the remaining rows (the list is made once: most of a light-client circuit's bindings sit on SHA-256 rows)
   if (!d->gpu_plan.ready) {
     GpuWitnessPlan fresh;
+    // set_fill_copies: the first host-written cell of a variable class stands for the class (every bound cell is a routed wire, and
+    // build() made one sigma cycle of the class), the device writes the others - also those on SHA-256 and PoseidonGate rows,
+    // which hold the same value already
+    std::vector<bool> listed(d->fill_copies ? d->parent.size() : 0, false);
     for (const CellBinding &c : d->cells) {
       uint32_t g = d->gate_of_row[c.row];
       if (g == G_SHA_ADD || g == G_SHA_ROUND_A || g == G_SHA_ROUND_E || g == G_SHA_SCHED || g == G_POSEIDON) continue;
-      fresh.host_cells.push_back(CellBinding{c.row, c.col, d->find(c.var)});
+      const uint32_t root = d->find(c.var);
+      if (d->fill_copies) {
+        if (listed[root]) continue;
+        listed[root] = true;
+      }
+      fresh.host_cells.push_back(CellBinding{c.row, c.col, root});
     }
     if (recording) { fresh.batches = std::move(recorded.batches); fresh.ready = true; }
     d->gpu_plan = std::move(fresh);  // not ready if this proof left the recorded plan half way: the next one records again
@@ -894,9 +903,17 @@ void CircuitData::generate_witness_gpu(const PartialWitness &pw, std::vector<F> 
     buf[k].value = V.val[var];
   }
   const auto t_scatter = now();
-  rc = lcp2_scatter_cells(d->ctx, buf.data(), buf.size(), (uint64_t *)d->d_wires, n);
-  if (rc == LCP2_OK) rc = lcp2_scatter_cells(d->ctx, cells.data(), cells.size(), (uint64_t *)d->d_wires, n);  // what the generators of this proof wrote cell by cell
-  if (rc != LCP2_OK) throw std::runtime_error(std::string("lcp2_scatter_cells: ") + lcp2_status_str(rc));
+  d->cells_sent = buf.size() + cells.size();
+  if (d->fill_copies) {
+    // (conflicting values of one class have thrown in V.set: LCP2_E_UNSAT cannot come from a list with one cell per class)
+    rc = lcp2_witness_fill_copies(d->gpu, buf.data(), buf.size(), LCP2_MEM_HOST, (uint64_t *)d->d_wires, nullptr);
+    if (rc == LCP2_OK) rc = lcp2_witness_fill_copies(d->gpu, cells.data(), cells.size(), LCP2_MEM_HOST, (uint64_t *)d->d_wires, nullptr);
+    if (rc != LCP2_OK) throw std::runtime_error(std::string("lcp2_witness_fill_copies: ") + lcp2_status_str(rc) + " (" + lcp2_last_error(d->ctx) + ")");
+  } else {
+    rc = lcp2_scatter_cells(d->ctx, buf.data(), buf.size(), (uint64_t *)d->d_wires, n);
+    if (rc == LCP2_OK) rc = lcp2_scatter_cells(d->ctx, cells.data(), cells.size(), (uint64_t *)d->d_wires, n);  // what the generators of this proof wrote cell by cell
+    if (rc != LCP2_OK) throw std::runtime_error(std::string("lcp2_scatter_cells: ") + lcp2_status_str(rc));
+  }
   if (prof)
     printf("  witness generation %.2f ms: host generators %.2f ms on %u lane(s) (%zu sweeps, %zu visits of %zu ops, %zu PoseidonGate rows), SHA-256 batches %.2f ms, "
            "PoseidonGate rows on the device + cell list %.2f ms, scatter of %zu cells %.2f ms\n",
@@ -904,6 +921,13 @@ void CircuitData::generate_witness_gpu(const PartialWitness &pw, std::vector<F> 
   public_inputs.clear();
   for (uint32_t v : d->public_inputs) public_inputs.push_back(V.get(v, "public input"));
 }
+
+void CircuitData::set_fill_copies(bool on) {
+  if (impl_->fill_copies == on) return;
+  impl_->fill_copies = on;
+  impl_->gpu_plan = GpuWitnessPlan();  // the cell list depends on the mode: the next proof plans again
+}
+size_t CircuitData::cells_sent_last() const { return impl_->cells_sent; }
 
 void CircuitData::read_device_witness(std::vector<uint64_t> &wires) const {
   const size_t words = (size_t)desc_.params.num_wires << desc_.params.degree_bits;

@@ -112,6 +112,8 @@ struct CircuitData::Impl {
   // the values refreshed per proof; pinned (lcp2_host_register) so that its upload is a DMA
   std::vector<lcp2_cell> cell_buf;
   bool cell_buf_pinned = false;
+  bool fill_copies = false;               // CircuitData::set_fill_copies: one cell per variable class through lcp2_witness_fill_copies
+  size_t cells_sent = 0;                  // lcp2_cell records of the last generate_witness_gpu
   mutable std::vector<F> value_store;
   mutable std::vector<uint32_t> stamp_store;
   mutable uint32_t epoch = 0;

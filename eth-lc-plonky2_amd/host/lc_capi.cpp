@@ -31,7 +31,7 @@ extern "C" const char *lch_last_error(void) { return g_error.c_str(); }
 
 extern "C" int lch_light_client_step_create(lcp2_ctx *ctx, const char *prev_json, const char *cur_json, uint32_t flags, uint32_t extra, lch_session **out) {
   if (!ctx || !prev_json || !cur_json || !out) return fail(LCP2_E_INVALID, "null argument");
-  if (flags & ~(LCH_BLS_PROOF_STAND_IN | LCH_SYNC_COMMITTEE_ONLY)) return fail(LCP2_E_INVALID, "unknown flag");
+  if (flags & ~(LCH_BLS_PROOF_STAND_IN | LCH_SYNC_COMMITTEE_ONLY | LCH_FILL_COPIES)) return fail(LCP2_E_INVALID, "unknown flag");
   *out = nullptr;
   try {
     std::unique_ptr<lch_session> s(new lch_session());
@@ -99,6 +99,7 @@ extern "C" int lch_light_client_step_create(lcp2_ctx *ctx, const char *prev_json
     if (!s->info.build_ms) s->info.build_ms = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
     s->data->attach_gpu(ctx);
+    s->data->set_fill_copies((flags & LCH_FILL_COPIES) != 0);
     s->info.attach_ms = ms_since(t0);
     s->info.degree_bits = s->data->degree_bits();
     s->info.num_public_inputs = s->data->description().num_public_inputs;

@@ -21,6 +21,7 @@ typedef struct lch_session lch_session;
 
 #define LCH_BLS_PROOF_STAND_IN 1u    /* the circuit also verifies, recursively, a proof with the BLS proof's 25 216 public inputs (stand-in statement circuit) */
 #define LCH_SYNC_COMMITTEE_ONLY 2u   /* BASELINE configs[1]: the SyncCommitteeSSZ gadget of cur_json's next_sync_committee alone */
+#define LCH_FILL_COPIES 4u           /* CircuitData::set_fill_copies(true): one host-written cell per variable class through lcp2_witness_fill_copies (off by default) */
 
 typedef struct {
   uint32_t degree_bits;

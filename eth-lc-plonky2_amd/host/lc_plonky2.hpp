@@ -168,6 +168,12 @@ class CircuitData {
   // remaining cells are scattered from the host; leaves the witness in the circuit's device buffer
   void generate_witness_gpu(const PartialWitness &pw, std::vector<F> &public_inputs);
   void read_device_witness(std::vector<uint64_t> &wires) const;   // test helper: copy of the device witness matrix
+  // Opt-in, off by default: generate_witness_gpu lists ONE host-written cell per variable class instead of every bound cell and sends
+  // the list through lcp2_witness_fill_copies, which hands the value to the other cells of the class on the device (the classes of
+  // the builder's union-find are the cycles of its sigma columns).  The proof is the same word for word.  Set before the first
+  // prove, or at any time: the cell list is planned again.  cells_sent_last(): the lcp2_cell records the last witness generation sent
+  void set_fill_copies(bool on);
+  size_t cells_sent_last() const;
   // WHERE a witness is wrong (lcp2_check_witness on the attached circuit), as text that names the gate by the builder's own name:
   //   "row R, gate ArithmeticGate, constraint i (N gate constraints violated); copy constraint (row, wire) != (row', wire') (M cells)"
   // or "the witness satisfies every gate and copy constraint".  diagnose(pw) runs the generators first (the witness stays in HBM); a

@@ -13,6 +13,7 @@ from . import binding as _b
 from . import build as _build
 
 BLS_PROOF_STAND_IN, SYNC_COMMITTEE_ONLY = 1, 2
+FILL_COPIES = 4   # LCH_FILL_COPIES: one host-written cell per variable class through lcp2_witness_fill_copies (off by default)
 
 
 class Info(ctypes.Structure):

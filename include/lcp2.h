@@ -527,6 +527,51 @@ typedef struct {
 int lcp2_check_witness(lcp2_circuit *c, const uint64_t *wires, lcp2_mem wires_mem, const uint64_t *public_inputs, size_t num_public_inputs,
                        lcp2_witness_report *report, uint64_t *per_gate, uint32_t num_gates);
 
+/* ONE VALUE PER COPY CLASS (plonky2: a generator sets one target of a partition, PartitionWitness::get_full_witness hands the value to
+ * every wire of the partition).  The copy classes are the cycles of the permutation the sigma columns describe, read back from the
+ * sigma VALUES as lcp2_check_witness reads them; a class is a cycle of more than one routed cell, and the classes are numbered in
+ * ascending order of their smallest cell index, cell index = wire * n + row.  The table (4 bytes per routed cell: 1.34 GB at
+ * n = 2^22 with 80 routed wires) is built on the device at the first call for a handle, kept in it and freed with it; building it
+ * takes four further arrays of that size - two (label, pointer) pairs, 5.4 GB there, 6.7 GB as the scratch allocator rounds it up -
+ * from scratch slot 0 of the context, which the context keeps, like the scratch of the other witness calls, until it is destroyed.
+ *   what the call writes   every listed cell as lcp2_scatter_cells writes it: wires[col][row] = value, as given, canonical or not.  If a
+ *           listed routed cell belongs to a class, the class takes the value of its listed cell with the SMALLEST LIST INDEX (the
+ *           owner), and every routed cell of the class - listed or not - receives the owner's value word for word.  The value comes
+ *           from the list, never from the matrix.  A class with no listed cell is not touched: no cell of it is read or written (a
+ *           row generator may have filled it).  Cells of non-routed wires and routed cells that are their own sigma image are plain
+ *           scatter writes; two entries for one such cell leave one of the two values, unspecified which.
+ *   conflicts   a listed cell whose CANONICAL value differs from its class's value ("set twice with different values").  The call then
+ *           returns LCP2_E_UNSAT with the report complete, lcp2_last_error names both list indices and both cells, and every cell of
+ *           the class - the conflicting ones included - holds the owner's value, so the matrix does not depend on the order the
+ *           lanes ran in.  Equal canonical but different raw values (v and v + p) are no conflict: the owner's raw value is stored.
+ *   validation   cells_mem = LCP2_MEM_HOST: row < n and col < num_wires are checked before anything is launched, a refused list
+ *           (LCP2_E_INVALID, "cell N: reason") writes nothing, and the list goes up through the context's pinned staging buffer when
+ *           it fits.  LCP2_MEM_DEVICE: the kernel validates; an invalid entry writes nothing and takes part in no class, the rest is
+ *           done, and the call returns LCP2_E_INVALID naming the FIRST refused entry.  ncells = 0 is LCP2_OK, touches nothing and
+ *           builds nothing (the report is zero but for the two indices).
+ * wires: device, [num_wires][n] column-major.  report: host, nullable.
+ * LCP2_E_INVALID: null c or wires, a null list with ncells > 0, a cells_mem above 1; and, with the reason in lcp2_last_error, sigma
+ * columns that are no permutation of the routed cell ids - a value that is the id of no cell, or two cells with the same image (both
+ * are named).  That is found while the table is built, which takes a bounded number of rounds (at most 32) whatever the columns hold.
+ * LCP2_E_NODEVICE: a verifier-only handle.  LCP2_E_UNSUPPORTED: a sharded handle, num_routed_wires * n >= 2^32 or ncells >= 2^32 (cell
+ * and list indices are 32-bit).
+ * The proving state of the handle is left alone, as by lcp2_check_witness: the call may come between any two other calls, also between
+ * the seams of a proof in flight.  The context's stream is synchronised on return.  Timing (lcp2_prof_*): LCP2_K_OTHER, one scope
+ * per call; the construction of the table books its decode pass, each pointer-jumping round and the numbering as scopes of their own. */
+typedef struct {
+  uint64_t num_classes;     /* copy classes of the circuit with more than one cell (a routed cell that is its own sigma image is in none) */
+  uint64_t classes_set;     /* of those, the classes that at least one listed cell belongs to */
+  uint64_t cells_filled;    /* routed cells that received their class's value and were not themselves listed */
+  uint64_t conflicts;       /* listed cells whose CANONICAL value differs from their class's value */
+  uint64_t conflict_index;  /* the smallest list index of such a cell; ~0 if none */
+  uint64_t owner_index;     /* the list index of the cell that gave that class its value; ~0 if none */
+} lcp2_fill_report;
+int lcp2_witness_fill_copies(lcp2_circuit *c, const lcp2_cell *cells, size_t ncells, lcp2_mem cells_mem,
+                             uint64_t *wires /* device, column-major [num_wires][n] */, lcp2_fill_report *report /* host, nullable */);
+/* the class table the call works from (tests, tools): class_of[wire * n + row] for the routed wires, host, num_routed_wires * n words;
+ * 0xFFFFFFFF for a cell in no class.  Either pointer may be null.  Builds the table if the handle has none yet; refusals as above. */
+int lcp2_circuit_copy_classes(lcp2_circuit *c, uint32_t *class_of, uint64_t *num_classes);
+
 /* ---- a HOST witness without its upload on the critical path.  data.prove(pw) of a fork that runs plonky2's own generators ends up with
  * the full witness in host memory (4.5 GB at n = 2^22); lcp2_prove(.., LCP2_MEM_HOST, ..) copies it first and proves afterwards.  For a
  * sequence of proofs (BASELINE configs[4]: a batch of updates) the copy of witness i + 1 runs while proof i is computed:
