@@ -16,6 +16,7 @@ u64p = ctypes.POINTER(ctypes.c_uint64)
 u32p = ctypes.POINTER(ctypes.c_uint32)
 u8p = ctypes.POINTER(ctypes.c_uint8)
 MEM_HOST, MEM_DEVICE = 0, 1
+VERIFY_HEADS = {"host": 0, "device": 1}  # LCP2_VERIFY_HEAD_HOST, LCP2_VERIFY_HEAD_DEVICE
 E_UNSAT = -5
 SECTION_OPENINGS, SECTION_FRI_CAP0, SECTION_AFTER_CAPS = 0, 1, 2
 
@@ -243,6 +244,8 @@ def load_library():
         "lcp2_quotient_commit": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_verify": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_int)]),
         "lcp2_verify_batch": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_size_t, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p]),
+        "lcp2_verify_batch_ex": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_size_t, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p,
+                                           c.c_uint32]),
         "lcp2_last_challenges": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_gate_program_degree": (c.c_int, [c.c_void_p, c.c_size_t, c.c_uint32, c.POINTER(c.c_uint32)]),
         "lcp2_circuit_gate_tiers": (c.c_int, [c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p]),
@@ -565,11 +568,14 @@ class Context:
                            pends.ctypes.data if pends.size else None, ptrs[3], counts[3], rends.size)
         self._check(self.lib.lcp2_witness_plan_rows(self.handle, ctypes.byref(plan), mem, ctypes.c_void_p(wires_dev), int(ncols), int(n)))
 
-    def verify_batch(self, circuit_data, proofs, public_inputs, mem=MEM_HOST, count=None):
+    def verify_batch(self, circuit_data, proofs, public_inputs, mem=MEM_HOST, count=None, head="host"):
         """lcp2_verify_batch: data.verify for a batch of proofs of one circuit (any CircuitData, verifier-only ones included), Merkle
         paths and FRI queries on this context's device.  proofs: a (count, proof_words) array, or with mem=MEM_DEVICE a device pointer
-        and `count`; public_inputs: (count, num_public_inputs), host.  Returns the int32 array of failed checks (0 = accepted, 1..7 as
-        ProofRejected.check); does not raise on rejection."""
+        and `count`; public_inputs: (count, num_public_inputs), host.  head: "host" (transcript and vanishing identity on the host, one
+        proof at a time) or "device" (lcp2_verify_batch_ex with LCP2_VERIFY_HEAD_DEVICE: on the device as well; the same verdicts).
+        Returns the int32 array of failed checks (0 = accepted, 1..7 as ProofRejected.check); does not raise on rejection."""
+        if head not in VERIFY_HEADS:
+            raise Lcp2Error(-1, "head is 'host' or 'device'")
         words = circuit_data.proof_words
         if mem == MEM_HOST:
             pr = _np_u64(proofs)
@@ -587,7 +593,10 @@ class Context:
         if npi * count != pis.size:
             raise Lcp2Error(-1, "public_inputs is not count rows")
         checks = np.zeros(count, dtype=np.int32)
-        rc = self.lib.lcp2_verify_batch(self.handle, circuit_data.handle, ptr, words, count, mem, _ptr(pis), npi, _ptr(checks))
+        if head == "host":
+            rc = self.lib.lcp2_verify_batch(self.handle, circuit_data.handle, ptr, words, count, mem, _ptr(pis), npi, _ptr(checks))
+        else:
+            rc = self.lib.lcp2_verify_batch_ex(self.handle, circuit_data.handle, ptr, words, count, mem, _ptr(pis), npi, _ptr(checks), VERIFY_HEADS[head])
         if rc != -7:
             self._check(rc)
         return checks

@@ -1,11 +1,25 @@
 // The gate-program format of include/lcp2.h in code, once, for every HOST reader of a program: the instruction, its checks, and
 // the straight-line walk over an algebra (F_p^2 values at zeta: verifier.hip; extension targets: host/recursion.cpp; degree
 // bounds: prover_build.hip).  Plain C++17 without HIP or field arithmetic, so that host/*.cpp and tools/gen/ include it too.
-// Not for the device (K6 interprets the staged encoding, quotient_common.hpp) nor for the oracle (an independent restatement).
+// K6 interprets the staged encoding (quotient_common.hpp) and the oracle restates the format independently; the one device reader of
+// this text is the batch verifier's identity kernel (kernels_verify_head.hip), for which the instruction and the walk are marked
+// GP_HD (host and device under hipcc, nothing elsewhere) and the registers are any type with operator[].
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include "../../include/lcp2.h"
+
+#if defined(__HIPCC__)
+#define GP_HD __host__ __device__
+#else
+#define GP_HD
+#endif
+// unrolling is asked for in device code only (there it keeps the PMDS window in registers); every host build compiles the loops as written
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GP_UNROLL _Pragma("unroll")
+#else
+#define GP_UNROLL
+#endif
 
 namespace gate_program {
 
@@ -20,10 +34,10 @@ inline constexpr uint64_t MDS_DIAG[MDS_WIDTH] = {8, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0
 // one instruction (two words): source k is of kind[k] at idx[k].  No reader looks at the bits outside these fields; encode() zeroes them.
 struct Insn {
   uint32_t op, dst, kind[2], idx[2];
-  Insn(uint32_t w0, uint32_t w1) : op(w0 & 0xF), dst((w0 >> 8) & 0xFF), kind{(w0 >> 16) & 0xF, (w0 >> 20) & 0xF}, idx{w1 & 0xFFFF, w1 >> 16} {}
+  GP_HD Insn(uint32_t w0, uint32_t w1) : op(w0 & 0xF), dst((w0 >> 8) & 0xFF), kind{(w0 >> 16) & 0xF, (w0 >> 20) & 0xF}, idx{w1 & 0xFFFF, w1 >> 16} {}
   void encode(uint32_t w[2]) const { w[0] = op | dst << 8 | kind[0] << 16 | kind[1] << 20; w[1] = idx[0] | idx[1] << 16; }
-  bool emits() const { return op == LCP2_OP_EMIT || op == LCP2_OP_EMITBOOL; }
-  bool pmds() const { return op == LCP2_OP_PMDS; }
+  GP_HD bool emits() const { return op == LCP2_OP_EMIT || op == LCP2_OP_EMITBOOL; }
+  GP_HD bool pmds() const { return op == LCP2_OP_PMDS; }
   // operands that are single values of kind[k].  A PMDS has none: idx[0] is a window of 12 registers, idx[1] a block of 12 immediates.
   int nsrc() const { return pmds() ? 0 : (emits() || op == LCP2_OP_SBOX) ? 1 : 2; }
   // one past the highest register read or written
@@ -63,11 +77,12 @@ inline const char *insn_problem(const Insn &in, const Limits &L) {
 //   V wire(i), gate_const(i), pi(i), imm(u64);  S scalar(u64), scalar_mul(S, S)
 //   V add(a, b), sub(a, b), mul(a, b), mul_add(a, b, acc) = a b + acc, scale_add(x, s, acc) = x s + acc
 // `imm` is the table of immediates, of either 64-bit unsigned type (null: every immediate reads as 0, for an algebra that ignores
-// the values); regs holds the registers the programs were validated for; on_emit(V) receives the constraints in program order.
+// the values); regs (a pointer, or any type whose operator[] gives a V &) holds the registers the programs were validated for;
+// on_emit(V) receives the constraints in program order.
 // THE ORDER OF THE ALGEBRA CALLS IS PART OF THE CONTRACT: over targets every call adds gates to a circuit, and another order or
 // an unfused mul + add where one mul_add stands gives another circuit with another digest (tests/cpp/test_gadgets.cpp pins them).
-template <class Alg, class Word, class Emit>
-void walk_program(Alg &A, const uint32_t *code, size_t first, size_t len, const Word *imm, typename Alg::V *regs, Emit on_emit) {
+template <class Alg, class Word, class Regs, class Emit>
+GP_HD void walk_program(Alg &A, const uint32_t *code, size_t first, size_t len, const Word *imm, Regs regs, Emit on_emit) {
   using V = typename Alg::V;
   auto immediate = [&](uint32_t i) { return A.imm(imm ? imm[i] : 0); };
   for (size_t pc = first; pc < first + len; pc++) {
@@ -77,11 +92,14 @@ void walk_program(Alg &A, const uint32_t *code, size_t first, size_t len, const 
       return kind == KIND_REG ? regs[i] : kind == KIND_WIRE ? A.wire(i) : kind == KIND_CONST ? A.gate_const(i) : kind == KIND_IMM ? immediate(i) : A.pi(i);
     };
     if (in.pmds()) {
-      V x[MDS_WIDTH];  // the two windows may be the same
+      V x[MDS_WIDTH];  // the two windows may be the same (unrolled: on the device x stays in registers)
+      GP_UNROLL
       for (uint32_t i = 0; i < MDS_WIDTH; i++) x[i] = regs[in.idx[0] + i];
+      GP_UNROLL
       for (uint32_t r = 0; r < MDS_WIDTH; r++) {
         V t = immediate(in.idx[1] + r);
         if (MDS_DIAG[r]) t = A.scale_add(x[r], A.scalar(MDS_DIAG[r]), t);
+        GP_UNROLL
         for (uint32_t i = 0; i < MDS_WIDTH; i++) t = A.scale_add(x[(i + r) % MDS_WIDTH], A.scalar(MDS_CIRC[i]), t);
         regs[in.dst + r] = t;
       }

@@ -19,6 +19,7 @@ class HostPoseidon {
     return h;
   }
   void permute(u64 s[12]) const { pos_permute(s, rc_); }
+  const u64 *round_constants() const { return rc_; }
   void hash_no_pad(const u64 *in, size_t len, u64 out[4]) const {
     u64 s[12] = {0};
     for (size_t off = 0; off < len; off += 8) {
@@ -139,6 +140,9 @@ struct VerifierView {
   const lcp2_gate *gates;
   const uint32_t *code;
   const u64 *imm, *k_is, *digest, *cs_cap;
+  // sizes of the tables, for the caller that uploads them (verify_batch.hip); verifier_view sets them, the host verifier reads none
+  size_t code_words = 0, num_imm = 0;
+  u32 num_regs = 0;
 };
 
 }  // namespace lcp2

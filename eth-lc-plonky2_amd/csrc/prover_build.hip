@@ -431,6 +431,7 @@ VerifierView verifier_view(const lcp2_circuit *c) {
   v.p = &c->p; v.npi = c->npi; v.num_selectors = c->num_selectors;
   v.gates = c->gates.data(); v.num_gates = (u32)c->gates.size(); v.code = c->code.data(); v.imm = c->imm.data();
   v.k_is = c->k_is.data(); v.digest = c->digest; v.cs_cap = c->cs_cap.data();
+  v.code_words = c->code.size(); v.num_imm = c->imm.size(); v.num_regs = c->num_regs;
   return v;
 }
 }  // namespace lcp2

@@ -726,6 +726,23 @@ int lcp2_verify(const lcp2_circuit *c, const uint64_t *proof, size_t proof_words
 int lcp2_verify_batch(lcp2_ctx *ctx, const lcp2_circuit *c, const uint64_t *proofs, size_t proof_words, size_t count, lcp2_mem proofs_mem,
                       const uint64_t *public_inputs, size_t num_public_inputs, int32_t *failed_checks);
 
+/* lcp2_verify_batch with a choice of where checks 2 and 3 (the head: public-input hash, transcript, proof of work, vanishing identity
+ * at zeta, reduced openings, query indices) run.  flags: LCP2_VERIFY_HEAD_HOST - exactly lcp2_verify_batch, which is this call with
+ * that value - or LCP2_VERIFY_HEAD_DEVICE; anything else is LCP2_E_INVALID with failed_checks untouched.  Arguments, return codes,
+ * length refusals and verdicts are lcp2_verify_batch's: proof i gets the check lcp2_verify names for it, the smallest one when
+ * several would fail.  There is no automatic choice: the device head costs a fixed latency per chunk (a chain of dependent Poseidon
+ * permutations), the host head a time per proof, and DESIGN.md section 3 has the measured crossover.
+ * With LCP2_VERIFY_HEAD_DEVICE, per call the circuit's gates, gate code, immediates, coset shifts, digest and constants cap are
+ * uploaded (whatever kind of handle c is), and per chunk of the batch host proofs and the chunk's public inputs; no word of a proof
+ * is downloaded - of device proofs nothing is copied at all - and each chunk ends with one copy (canon flags, head codes, status
+ * words) and one stream synchronisation.  Scratch slots of the context used: 0 host proofs, 1 challenge blocks, flags, head codes,
+ * status words, transcript challenges and identity sums, 2 public inputs and circuit tables, 3 the constants cap.  A chunk holds
+ * min(4096, (pinned bytes - 256) / (8 * num_public_inputs + 8 + 4 * num_query_rounds)) proofs.  Timing: LCP2_K_OTHER. */
+#define LCP2_VERIFY_HEAD_HOST   0u
+#define LCP2_VERIFY_HEAD_DEVICE 1u
+int lcp2_verify_batch_ex(lcp2_ctx *ctx, const lcp2_circuit *c, const uint64_t *proofs, size_t proof_words, size_t count, lcp2_mem proofs_mem,
+                         const uint64_t *public_inputs, size_t num_public_inputs, int32_t *failed_checks, uint32_t flags);
+
 /* ---- byte serialisation of a proof: plonky2 0.1.4 util/serialization.rs `write_proof_with_public_inputs`
  * ([RECALL] of the published format; the reference holds no serialised proof - src/main.rs:230-233 moves the object - so
  * this layout is PARITY UNPINNED).  Little-endian throughout: a field element is its canonical u64, an extension element two
