@@ -47,6 +47,16 @@ class CircuitDesc(ctypes.Structure):
                 ("num_regs", ctypes.c_uint32)]
 
 
+class CircuitRows(ctypes.Structure):
+    """lcp2_circuit_rows: what lcp2_circuit_rows_expand / lcp2_circuit_create_from_rows build the preprocessed columns from"""
+    _fields_ = [("gate_of_row", ctypes.c_void_p), ("num_rows", ctypes.c_size_t), ("pad_gate", ctypes.c_uint32), ("row_constants", ctypes.c_void_p),
+                ("bindings", ctypes.c_void_p), ("num_bindings", ctypes.c_size_t), ("bindings_mem", ctypes.c_int), ("num_classes", ctypes.c_uint32)]
+
+
+BINDING_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("cls", "<u4")])   # lcp2_copy_binding as a numpy record
+assert BINDING_DTYPE.itemsize == 12
+
+
 class ProofLayout(ctypes.Structure):
     """lcp2_proof_layout: word offsets of every field of the flat proof"""
     _fields_ = ([(n, ctypes.c_uint64) for n in ("cap_words", "wires_cap", "zs_cap", "quot_cap", "op_constants", "op_sigmas", "op_wires", "op_zs",
@@ -211,6 +221,8 @@ def load_library():
         "lcp2_oracle_open": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]),
         "lcp2_oracle_read": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p]),
         "lcp2_circuit_create": (c.c_int, [c.c_void_p, c.POINTER(CircuitDesc), c.POINTER(c.c_void_p)]),
+        "lcp2_circuit_rows_expand": (c.c_int, [c.c_void_p, c.POINTER(CircuitDesc), c.POINTER(CircuitRows), c.c_void_p]),
+        "lcp2_circuit_create_from_rows": (c.c_int, [c.c_void_p, c.POINTER(CircuitDesc), c.POINTER(CircuitRows), c.POINTER(c.c_void_p)]),
         "lcp2_verifier_create": (c.c_int, [c.POINTER(CircuitDesc), c.c_void_p, c.c_void_p, c.POINTER(c.c_void_p)]),
         "lcp2_circuit_destroy": (None, [c.c_void_p]),
         "lcp2_circuit_digest": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p]),
@@ -601,6 +613,20 @@ class Context:
             self._check(rc)
         return checks
 
+    def expand_rows(self, circ, rows, bindings_ptr=None, num_bindings=None):
+        """lcp2_circuit_rows_expand: the matrix [num_constants + num_routed_wires][n] that `rows` (circuit.Rows) describe for the
+        parameters, gate set and coset shifts of `circ` - what circ.constants_sigmas would hold.  bindings_ptr / num_bindings: a device
+        list of lcp2_copy_binding records instead of rows.bindings."""
+        d, keep = _describe(circ, 0)
+        r, keep_rows = _describe_rows(rows, bindings_ptr, num_bindings)
+        shape = (circ.params.num_constants + circ.params.num_routed_wires, 1 << circ.params.degree_bits)
+        ptr = self.buffer_alloc(shape[0] * shape[1])
+        try:
+            self._check(self.lib.lcp2_circuit_rows_expand(self.handle, ctypes.byref(d), ctypes.byref(r), ctypes.c_void_p(ptr)))
+            return self.buffer_read(ptr, shape[0] * shape[1]).reshape(shape)
+        finally:
+            self.buffer_free(ptr)
+
     def buffer_alloc(self, words):
         p = ctypes.c_void_p()
         self._check(self.lib.lcp2_buffer_alloc(self.handle, int(words) * 8, ctypes.byref(p)))
@@ -736,6 +762,24 @@ def _describe(circ, constants_sigmas_ptr=None, mem=MEM_HOST):
     return d, (gates, gs, circ)
 
 
+def _describe_rows(rows, bindings_ptr=None, num_bindings=None):
+    """lcp2_circuit_rows for a circuit.Rows; a device binding list as (pointer, count) instead of rows.bindings.  Returns (struct, keepalive)"""
+    gate_of_row = np.ascontiguousarray(rows.gate_of_row, dtype=np.uint32).ravel()
+    consts = None if rows.row_constants is None else np.ascontiguousarray(rows.row_constants, dtype=np.uint64)
+    r = CircuitRows()
+    r.gate_of_row, r.num_rows, r.pad_gate = (gate_of_row.ctypes.data if gate_of_row.size else None), gate_of_row.size, rows.pad_gate
+    r.row_constants = consts.ctypes.data if consts is not None and consts.size else None
+    r.num_classes = rows.num_classes
+    if bindings_ptr is not None:
+        r.bindings, r.num_bindings, r.bindings_mem, b = bindings_ptr, int(num_bindings), MEM_DEVICE, None
+    else:
+        if not isinstance(rows.bindings, np.ndarray) or rows.bindings.dtype != BINDING_DTYPE:
+            raise Lcp2Error(-1, "bindings must be an array of BINDING_DTYPE records")
+        b = np.ascontiguousarray(rows.bindings).ravel()
+        r.bindings, r.num_bindings, r.bindings_mem = (b.ctypes.data if b.size else None), b.size, MEM_HOST
+    return r, (gate_of_row, consts, b)
+
+
 class CircuitData:
     """builder.build::<C>() result: the handle `prove` and `verify` are called on
     (reference: eth-lc-plonky2/src/main.rs:227-233)."""
@@ -750,6 +794,16 @@ class CircuitData:
         d, keep = _describe(circ, constants_sigmas_ptr, mem)
         h = ctypes.c_void_p()
         ctx._check(ctx.lib.lcp2_circuit_create(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        return cls(ctx, circ, h, keep)
+
+    @classmethod
+    def build_from_rows(cls, ctx, circ, rows, bindings_ptr=None, num_bindings=None):
+        """lcp2_circuit_create_from_rows: the handle of `circ` with its preprocessed columns built on the device from `rows`
+        (circuit.Rows); circ.constants_sigmas is not looked at (the description goes in with a null matrix)."""
+        d, keep = _describe(circ, 0)
+        r, keep_rows = _describe_rows(rows, bindings_ptr, num_bindings)
+        h = ctypes.c_void_p()
+        ctx._check(ctx.lib.lcp2_circuit_create_from_rows(ctx.handle, ctypes.byref(d), ctypes.byref(r), ctypes.byref(h)))
         return cls(ctx, circ, h, keep)
 
     @classmethod

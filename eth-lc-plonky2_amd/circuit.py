@@ -596,3 +596,106 @@ def fill_copies_model(circ, cells, wires, class_of=None):
     return dict(num_classes=num_classes, classes_set=len(owner), cells_filled=filled - len(listed), conflicts=len(conflicts), conflict_index=first,
                 owner_index=owner[int(class_of[int(cells[first]["col"]), int(cells[first]["row"])])] if conflicts else none,
                 refused=refused, status=-1 if refused is not None else (-5 if conflicts else 0))
+
+
+# ---------------------------------------------------------------- rows and copy bindings: the numpy model of lcp2_circuit_rows_expand
+BINDING_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("cls", "<u4")])   # = binding.BINDING_DTYPE (lcp2_copy_binding)
+
+
+class Rows:
+    """What lcp2_circuit_rows_expand / lcp2_circuit_create_from_rows take instead of the expanded matrix (lcp2_circuit_rows):
+    gate_of_row [num_rows] (the rows behind take pad_gate), row_constants [num_rows][num_constants - num_selectors] or None (zeros),
+    bindings (BINDING_DTYPE records: a bound routed cell and its copy class, in the order the cycles run) and num_classes."""
+
+    def __init__(self, gate_of_row, pad_gate, row_constants, bindings, num_classes):
+        self.gate_of_row = np.ascontiguousarray(gate_of_row, dtype=np.uint32)
+        self.pad_gate = int(pad_gate)
+        self.row_constants = None if row_constants is None else np.ascontiguousarray(row_constants, dtype=np.uint64)
+        self.bindings = np.ascontiguousarray(bindings, dtype=BINDING_DTYPE)
+        self.num_classes = int(num_classes)
+
+
+def bindings_of(entries):
+    """BINDING_DTYPE records from (row, col, cls) triples"""
+    out = np.zeros(len(entries), dtype=BINDING_DTYPE)
+    for i, (row, col, cls) in enumerate(entries):
+        out[i] = (row, col, cls)
+    return out
+
+
+def circuit_rows_of(circ, gate_of_row=None):
+    """The Rows from which the device must build circ.constants_sigmas again, word for word.  gate_of_row (default: read back from the
+    selector columns - the gate whose selector column holds its selector value) and the gate constants come from the matrix and the
+    gate set; the trailing rows of the last row's gate with zero constants are left to pad_gate.  The bindings: every sigma cycle of
+    more than one cell, walked from its smallest cell along sigma (copy_next_cells has the successor), one class per cycle in
+    ascending order of that cell."""
+    n, NR, NC, gs = circ.n, circ.params.num_routed_wires, circ.params.num_constants, circ.gateset
+    S = gs.num_selectors
+    if gate_of_row is None:
+        gate_of_row = np.full(n, len(gs.gates), dtype=np.int64)
+        for g, G in enumerate(gs.gates):
+            gate_of_row[circ.constants_sigmas[G.selector_index, :n] == np.uint64(G.selector_value)] = g
+        assert (gate_of_row < len(gs.gates)).all(), "a row whose selector columns name no gate"
+    gate_of_row = np.asarray(gate_of_row, dtype=np.int64)
+    consts = np.ascontiguousarray(circ.constants_sigmas[S:NC, :n].T)
+    pad_gate = int(gate_of_row[-1])
+    padded = (gate_of_row == pad_gate) & ~consts.any(axis=1)
+    num_rows = n - int(np.argmin(padded[::-1])) if not padded.all() else 0
+    nxt = copy_next_cells(circ)
+    seen = nxt == np.arange(nxt.size)
+    entries, cls = [], 0
+    for start in np.nonzero(~seen)[0]:
+        cell = int(start)
+        if seen[cell]:
+            continue
+        while not seen[cell]:
+            seen[cell] = True
+            entries.append((cell % n, cell // n, cls))
+            cell = int(nxt[cell])
+        cls += 1
+    return Rows(gate_of_row[:num_rows], pad_gate, consts[:num_rows] if NC > S else None, bindings_of(entries), max(cls, 1))
+
+
+def expand_rows_model(circ_params, gateset, k_is, rows):
+    """lcp2_circuit_rows_expand in numpy: the matrix [num_constants + num_routed_wires][n].  The selector value of the row's gate in its
+    selector column and UNUSED_SELECTOR in the others, row_constants transposed, the identity ids, and then the list-order rule as a
+    dict of lists: the bound cells of a class in the order the list names them, each mapped to the next, the last to the first.
+    Raises ValueError where the library refuses (the message starts with what lcp2_last_error names: "row R" / "binding I")."""
+    n, NR, NC, S = 1 << circ_params.degree_bits, circ_params.num_routed_wires, circ_params.num_constants, gateset.num_selectors
+    gate_of_row = np.full(n, rows.pad_gate, dtype=np.int64)
+    if rows.gate_of_row.size > n:
+        raise ValueError("num_rows > n")
+    gate_of_row[:rows.gate_of_row.size] = rows.gate_of_row
+    if rows.pad_gate >= len(gateset.gates):
+        raise ValueError("pad_gate out of range")
+    bad = np.nonzero(gate_of_row >= len(gateset.gates))[0]
+    if bad.size:
+        raise ValueError("row %d: gate index out of range" % bad[0])
+    out = np.zeros((NC + NR, n), dtype=np.uint64)
+    out[:S] = UNUSED_SELECTOR
+    for g, G in enumerate(gateset.gates):
+        out[G.selector_index, gate_of_row == g] = G.selector_value
+    if rows.row_constants is not None and rows.gate_of_row.size:
+        out[S:NC, :rows.gate_of_row.size] = rows.row_constants.reshape(rows.gate_of_row.size, NC - S).T
+    sub = gl.powers(gl.root_of_unity(circ_params.degree_bits), n)
+    k_is = gl.canon(np.asarray(k_is, dtype=np.uint64))
+    for j in range(NR):
+        out[NC + j] = gl.mul(k_is[j], sub)
+    classes, first = {}, {}
+    for i, b in enumerate(rows.bindings):
+        row, col, cls = int(b["row"]), int(b["col"]), int(b["cls"])
+        for problem, why in ((row >= n, "row out of range"), (col >= NR, "column is no routed wire"), (cls >= rows.num_classes, "class out of range")):
+            if problem:
+                raise ValueError("binding %d: %s" % (i, why))
+    for i, b in enumerate(rows.bindings):
+        first.setdefault((int(b["row"]), int(b["col"])), []).append(i)
+        classes.setdefault(int(b["cls"]), []).append((int(b["row"]), int(b["col"])))
+    twice = [v for v in first.values() if len(v) > 1]
+    if twice:
+        i, j = min(twice)[:2]
+        raise ValueError("binding %d: cell bound twice, also bound by binding %d" % (j, i))
+    pairs = [(cur, nxt) for cells in classes.values() for cur, nxt in zip(cells, cells[1:] + cells[:1])]
+    if pairs:
+        at, to = np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
+        out[NC + at[:, 1], at[:, 0]] = gl.mul(k_is[to[:, 1]], sub[to[:, 0]])
+    return out

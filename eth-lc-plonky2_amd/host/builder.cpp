@@ -7,6 +7,7 @@
 // forward pass replaces plonky2's worklist); a value set twice with different results is the UnsatisfiedError
 // that makes the reference's #[should_panic] tests panic.
 #include <cstdio>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -36,8 +37,12 @@ void PartialWitness::set_hash256_target(const Hash256Target &t, const uint8_t v[
 }
 
 // ------------------------------------------------------------------ CircuitBuilder
+static double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
 struct CircuitBuilder::Impl {
   std::unique_ptr<CircuitData::Impl> d{new CircuitData::Impl()};
+  bool compact = false;  // set_compact_build
+  std::chrono::steady_clock::time_point created = std::chrono::steady_clock::now();
   std::map<F, uint32_t> const_vars;
   int const_row = -1, const_slot = 2;
   std::map<std::pair<F, F>, std::pair<uint32_t, uint32_t>> arith_open;  // (c0, c1) -> (row, next slot)
@@ -312,30 +317,66 @@ std::unique_ptr<CircuitData> CircuitBuilder::build() {
   D.params.num_challenges = cfg.num_challenges; D.params.quotient_degree_factor = cfg.max_quotient_degree_factor;
   D.num_selectors = gs.num_selectors; D.gates = gs.gates; D.code = gs.code; D.imm = gs.imm; D.num_public_inputs = npi; D.num_regs = gs.num_regs;
   const uint32_t NC = D.params.num_constants;
+  d->selector_groups = gs.groups;
+  // k_is = g^j
+  D.k_is.resize(NR);
+  F acc = 1;
+  for (uint32_t j = 0; j < NR; j++) { D.k_is[j] = acc; acc = f_mul(acc, 7); }
+  // no connect() after this point: flatten the union-find (every variable points at its root), so that the find() of every
+  // generator input and wire cell during witness generation is one step instead of a walk
+  auto t_flat = std::chrono::steady_clock::now();
+  for (uint32_t v = 0; v < d->parent.size(); v++) d->parent[v] = d->find(v);
+  d->times.classes_ms = ms_since(t_flat);
+  d->times.gadgets_ms = std::chrono::duration<double, std::milli>(t_flat - b->created).count();
+  if (b->compact) {
+    // the compact form: nothing of size (NC + NR) n.  The bindings in the order the std::map walk of the ordinary form meets them -
+    // ascending root, then d->cells order - by one stable sort of d->cells on the root
+    auto t0 = std::chrono::steady_clock::now();
+    d->compact = true;
+    d->compact_consts.resize((size_t)d->nrows * cfg.num_constants);
+    for (uint32_t r = 0; r < d->nrows; r++)
+      for (uint32_t k = 0; k < cfg.num_constants; k++) d->compact_consts[(size_t)r * cfg.num_constants + k] = d->row_consts[r][k];
+    d->times.matrix_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    d->compact_bindings.resize(d->cells.size());
+    for (size_t i = 0; i < d->cells.size(); i++) d->compact_bindings[i] = {d->cells[i].row, d->cells[i].col, d->parent[d->cells[i].var]};
+    std::stable_sort(d->compact_bindings.begin(), d->compact_bindings.end(), [](const lcp2_copy_binding &x, const lcp2_copy_binding &y) { return x.cls < y.cls; });
+    d->times.classes_ms += ms_since(t0);
+  } else {
+    expand_constants_sigmas(d, D, &d->times);
+  }
+  data->impl_ = std::move(b->d);
+  return data;
+}
+
+// The expanded matrix [num_constants + num_routed][n] of a built circuit: what build() writes in its ordinary form, and what
+// CircuitData::expanded_description() writes on demand for a circuit built in the compact form.
+void expand_constants_sigmas(const CircuitData::Impl *d, CircuitDescription &D, BuildTimes *times) {
+  const CircuitConfig &cfg = d->config;
+  const uint32_t NC = D.params.num_constants, NR = D.params.num_routed_wires, S = D.num_selectors;
+  const uint64_t n = 1ull << D.params.degree_bits;
+  auto t0 = std::chrono::steady_clock::now();
   D.constants_sigmas.assign((size_t)(NC + NR) * n, 0);
   // selectors and gate constants
   for (uint64_t r = 0; r < n; r++) {
     uint32_t g = r < d->nrows ? d->gate_of_row[r] : (uint32_t)G_NOOP;
-    for (uint32_t s = 0; s < gs.num_selectors; s++)
-      D.constants_sigmas[(size_t)s * n + r] = (gs.groups[s].first <= g && g < gs.groups[s].second) ? g : 0xFFFFFFFFull;
+    for (uint32_t s = 0; s < S; s++)
+      D.constants_sigmas[(size_t)s * n + r] = (d->selector_groups[s].first <= g && g < d->selector_groups[s].second) ? g : 0xFFFFFFFFull;
     if (r < d->nrows)
-      for (uint32_t k = 0; k < cfg.num_constants; k++) D.constants_sigmas[(size_t)(gs.num_selectors + k) * n + r] = d->row_consts[r][k];
+      for (uint32_t k = 0; k < cfg.num_constants; k++) D.constants_sigmas[(size_t)(S + k) * n + r] = d->row_consts[r][k];
   }
-  // k_is = g^j and the subgroup
-  D.k_is.resize(NR);
-  F acc = 1;
-  for (uint32_t j = 0; j < NR; j++) { D.k_is[j] = acc; acc = f_mul(acc, 7); }
+  if (times) times->matrix_ms = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  // the subgroup; identity permutation, then one cycle per variable class
   std::vector<F> sub(n);
-  F w = f_root_of_unity(degree_bits);
+  F w = f_root_of_unity(D.params.degree_bits);
   sub[0] = 1;
   for (uint64_t i = 1; i < n; i++) sub[i] = f_mul(sub[i - 1], w);
-  // no connect() after this point: flatten the union-find (every variable points at its root), so that the find() of every
-  // generator input and wire cell during witness generation is one step instead of a walk
-  for (uint32_t v = 0; v < d->parent.size(); v++) d->parent[v] = d->find(v);
-  // identity permutation, then one cycle per variable class
   uint64_t *sig = D.constants_sigmas.data() + (size_t)NC * n;
   for (uint32_t j = 0; j < NR; j++)
     for (uint64_t i = 0; i < n; i++) sig[(size_t)j * n + i] = f_mul(D.k_is[j], sub[i]);
+  if (times) times->identity_ms = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
   std::vector<uint8_t> taken((size_t)NR * n, 0);
   std::map<uint32_t, std::vector<std::pair<uint32_t, uint32_t>>> classes;
   for (const CellBinding &c : d->cells) {
@@ -343,6 +384,8 @@ std::unique_ptr<CircuitData> CircuitBuilder::build() {
     if (taken[(size_t)c.col * n + c.row]++) throw std::runtime_error("wire cell bound twice");
     classes[d->find(c.var)].push_back({c.row, c.col});
   }
+  if (times) times->classes_ms += ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
   for (auto &kv : classes) {
     auto &cells = kv.second;
     for (size_t k = 0; k < cells.size(); k++) {
@@ -351,9 +394,22 @@ std::unique_ptr<CircuitData> CircuitBuilder::build() {
       sig[(size_t)cur.second * n + cur.first] = f_mul(D.k_is[nxt.second], sub[nxt.first]);
     }
   }
-  data->impl_ = std::move(b->d);
-  return data;
+  if (times) times->cycles_ms = ms_since(t0);
 }
+
+void CircuitBuilder::set_compact_build(bool on) { impl_->compact = on; }
+
+const CircuitDescription &CircuitData::expanded_description() const {
+  if (desc_.constants_sigmas.empty()) expand_constants_sigmas(impl_.get(), desc_, nullptr);
+  return desc_;
+}
+BuildTimes CircuitData::build_times() const { return impl_->times; }
+size_t CircuitData::build_upload_bytes() const {
+  const size_t n = (size_t)1 << desc_.params.degree_bits;
+  if (!impl_->compact) return (size_t)(desc_.params.num_constants + desc_.params.num_routed_wires) * n * 8;
+  return impl_->gate_of_row.size() * 4 + impl_->compact_consts.size() * 8 + impl_->compact_bindings.size() * sizeof(lcp2_copy_binding);
+}
+
 
 lcp2_circuit_desc CircuitDescription::c_desc() const {
   lcp2_circuit_desc d{};
@@ -611,7 +667,18 @@ void CircuitData::verifier_only_data(uint64_t digest[4], std::vector<uint64_t> &
 
 void CircuitData::attach_gpu(lcp2_ctx *ctx) {
   lcp2_circuit_desc cd = desc_.c_desc();
-  int rc = lcp2_circuit_create(ctx, &cd, &impl_->gpu);
+  int rc;
+  if (impl_->compact) {  // CircuitBuilder::set_compact_build: the device builds the preprocessed columns, no matrix crosses the bus
+    lcp2_circuit_rows rows{};
+    rows.gate_of_row = impl_->gate_of_row.data(); rows.num_rows = impl_->nrows; rows.pad_gate = G_NOOP;
+    rows.row_constants = impl_->compact_consts.data();
+    rows.bindings = impl_->compact_bindings.data(); rows.num_bindings = impl_->compact_bindings.size(); rows.bindings_mem = LCP2_MEM_HOST;
+    rows.num_classes = (uint32_t)impl_->parent.size();
+    cd.constants_sigmas = nullptr;
+    rc = lcp2_circuit_create_from_rows(ctx, &cd, &rows, &impl_->gpu);
+  } else {
+    rc = lcp2_circuit_create(ctx, &cd, &impl_->gpu);
+  }
   if (rc != LCP2_OK) throw std::runtime_error(std::string("lcp2_circuit_create: ") + lcp2_status_str(rc) + " (" + lcp2_last_error(ctx) + ")");
   impl_->ctx = ctx;
   const size_t bytes = (size_t)desc_.params.num_wires * ((size_t)1 << desc_.params.degree_bits) * 8;

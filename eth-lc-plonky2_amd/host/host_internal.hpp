@@ -112,6 +112,13 @@ struct CircuitData::Impl {
   // the values refreshed per proof; pinned (lcp2_host_register) so that its upload is a DMA
   std::vector<lcp2_cell> cell_buf;
   bool cell_buf_pinned = false;
+  // CircuitBuilder::set_compact_build: build() kept the rows and the bindings instead of the expanded matrix (attach_gpu hands them
+  // to lcp2_circuit_create_from_rows; expanded_description() expands them on the host when somebody asks for the matrix)
+  bool compact = false;
+  std::vector<uint64_t> compact_consts;                 // row-major [nrows][config.num_constants]
+  std::vector<lcp2_copy_binding> compact_bindings;      // (row, col, root of the variable), ascending root, then binding order
+  std::vector<std::pair<uint32_t, uint32_t>> selector_groups;  // the gate set's selector groups, for the expansion
+  BuildTimes times;
   bool fill_copies = false;               // CircuitData::set_fill_copies: one cell per variable class through lcp2_witness_fill_copies
   size_t cells_sent = 0;                  // lcp2_cell records of the last generate_witness_gpu
   mutable std::vector<F> value_store;
@@ -119,5 +126,8 @@ struct CircuitData::Impl {
   mutable uint32_t epoch = 0;
   uint32_t find(uint32_t v) const { while (parent[v] != v) v = parent[v]; return v; }
 };
+
+// builder.cpp: the expanded constants_sigmas of a built circuit into D (times: the phases, nullable)
+void expand_constants_sigmas(const CircuitData::Impl *d, CircuitDescription &D, BuildTimes *times);
 
 }  // namespace lc

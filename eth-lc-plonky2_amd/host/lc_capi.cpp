@@ -31,7 +31,7 @@ extern "C" const char *lch_last_error(void) { return g_error.c_str(); }
 
 extern "C" int lch_light_client_step_create(lcp2_ctx *ctx, const char *prev_json, const char *cur_json, uint32_t flags, uint32_t extra, lch_session **out) {
   if (!ctx || !prev_json || !cur_json || !out) return fail(LCP2_E_INVALID, "null argument");
-  if (flags & ~(LCH_BLS_PROOF_STAND_IN | LCH_SYNC_COMMITTEE_ONLY | LCH_FILL_COPIES)) return fail(LCP2_E_INVALID, "unknown flag");
+  if (flags & ~(LCH_BLS_PROOF_STAND_IN | LCH_SYNC_COMMITTEE_ONLY | LCH_FILL_COPIES | LCH_COMPACT_BUILD)) return fail(LCP2_E_INVALID, "unknown flag");
   *out = nullptr;
   try {
     std::unique_ptr<lch_session> s(new lch_session());
@@ -46,6 +46,7 @@ extern "C" int lch_light_client_step_create(lcp2_ctx *ctx, const char *prev_json
     auto t0 = std::chrono::steady_clock::now();
     if (flags & LCH_SYNC_COMMITTEE_ONLY) {  // the reference's test_ssz_sync_committee (src/sync_committee_pubkeys.rs:100-653)
       CircuitBuilder builder(CircuitConfig::standard_recursion_config());
+      builder.set_compact_build((flags & LCH_COMPACT_BUILD) != 0);
       SyncCommitteeTarget sc = add_virtual_sync_committee_target(builder);
       Hash256Target root = ssz_sync_committee(builder, sc);
       for (auto &limb : root) builder.register_public_input(limb.t);
@@ -62,6 +63,7 @@ extern "C" int lch_light_client_step_create(lcp2_ctx *ctx, const char *prev_json
         t0 = std::chrono::steady_clock::now();
       }
       CircuitBuilder builder(CircuitConfig::standard_recursion_config());
+      builder.set_compact_build((flags & LCH_COMPACT_BUILD) != 0);
       ProofTarget target = add_virtual_proof_target(builder, bls ? &bls_cd : nullptr);
       for (auto &limb : target.cur_state) builder.register_public_input(limb.t);  // src/main.rs:180-187
       for (auto &limb : target.new_state) builder.register_public_input(limb.t);
@@ -104,6 +106,10 @@ extern "C" int lch_light_client_step_create(lcp2_ctx *ctx, const char *prev_json
     s->info.degree_bits = s->data->degree_bits();
     s->info.num_public_inputs = s->data->description().num_public_inputs;
     s->info.proof_words = lcp2_proof_words(&s->data->description().params);
+    const BuildTimes bt = s->data->build_times();
+    s->info.build_gadgets_ms = bt.gadgets_ms; s->info.build_matrix_ms = bt.matrix_ms; s->info.build_identity_ms = bt.identity_ms;
+    s->info.build_classes_ms = bt.classes_ms; s->info.build_cycles_ms = bt.cycles_ms;
+    s->info.attach_upload_bytes = s->data->build_upload_bytes();
     *out = s.release();
     return LCP2_OK;
   } catch (const UnsatisfiedError &e) {

@@ -23,6 +23,8 @@ typedef struct lch_session lch_session;
 #define LCH_SYNC_COMMITTEE_ONLY 2u   /* BASELINE configs[1]: the SyncCommitteeSSZ gadget of cur_json's next_sync_committee alone */
 #define LCH_FILL_COPIES 4u           /* CircuitData::set_fill_copies(true): one host-written cell per variable class through lcp2_witness_fill_copies (off by default) */
 
+#define LCH_COMPACT_BUILD 8u         /* CircuitBuilder::set_compact_build(true): no expanded matrix on the host, lcp2_circuit_create_from_rows builds the columns (off by default) */
+
 typedef struct {
   uint32_t degree_bits;
   uint32_t num_public_inputs;
@@ -32,6 +34,10 @@ typedef struct {
   double attach_ms;            /* lcp2_circuit_create: the preprocessed polynomials committed on the GPU */
   double inner_prove_ms;       /* LCH_BLS_PROOF_STAND_IN: the inner proof (not part of lch_prove) */
   uint32_t inner_degree_bits, inner_public_inputs;
+  /* the phases of build_ms (lc::BuildTimes; step sessions): gadget code, selector and constant columns, identity sigmas, variable
+   * classes, cycles - the last four are what LCH_COMPACT_BUILD leaves to the device - and what attach_ms uploaded for the columns */
+  double build_gadgets_ms, build_matrix_ms, build_identity_ms, build_classes_ms, build_cycles_ms;
+  uint64_t attach_upload_bytes;
 } lch_info;
 
 /* prev_json / cur_json: two consecutive light-client updates (beacon-API V1_5 layout or the layout of the reference's fixture files).

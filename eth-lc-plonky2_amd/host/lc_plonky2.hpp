@@ -126,6 +126,11 @@ class CircuitBuilder {
   void register_public_inputs(const std::vector<Target> &ts) { for (auto t : ts) register_public_input(t); }
   size_t num_gates() const;
   void print_gate_counts(int min_delta) const;
+  // Opt-in, off by default: build() does not expand the matrix [num_constants + num_routed][n] (2.85 GB at 2^22 rows).  It keeps one
+  // gate index and the gate constants per row and the bound cells as (row, column, variable class), and attach_gpu hands those to
+  // lcp2_circuit_create_from_rows, which builds the columns on the device: same cap, same digest, same proofs.
+  // CircuitData::description().constants_sigmas is then empty; expanded_description() still gives the matrix.
+  void set_compact_build(bool on);
   // consumes the builder (the reference moves it): selectors, copy-constraint permutation, gate programs
   std::unique_ptr<CircuitData> build();
 
@@ -135,6 +140,11 @@ class CircuitBuilder {
  private:
   std::unique_ptr<Impl> impl_;
 };
+
+// where the host time of a circuit went, from the builder's construction to the end of build() (milliseconds): the gadget code
+// (everything up to the flattening of the variable classes), the selector and constant columns (compact form: the row constants),
+// the identity sigmas, the variable classes (union-find flattening and the grouping of the bound cells) and the cycles
+struct BuildTimes { double gadgets_ms = 0, matrix_ms = 0, identity_ms = 0, classes_ms = 0, cycles_ms = 0; };
 
 // what build() produced, in the form lcp2_circuit_create consumes (kept by value so tests can hand the same
 // description to another prover, e.g. the CPU oracle)
@@ -154,6 +164,11 @@ class CircuitData {
  public:
   ~CircuitData();
   const CircuitDescription &description() const { return desc_; }
+  // description() with constants_sigmas filled: a circuit built with set_compact_build expands the matrix here, at the first call
+  // (the CPU oracle and whoever else reads the matrix pay for it then); otherwise the same as description()
+  const CircuitDescription &expanded_description() const;
+  BuildTimes build_times() const;
+  size_t build_upload_bytes() const;  // what attach_gpu sends for the preprocessed columns: the matrix, or rows + constants + bindings
   uint32_t degree_bits() const { return desc_.params.degree_bits; }
   uint32_t quotient_degree_factor() const { return desc_.params.quotient_degree_factor; }
   // generate_partial_witness: runs the generators in creation order, checks every copy constraint and returns the
@@ -193,7 +208,7 @@ class CircuitData {
  private:
   friend class CircuitBuilder;
   CircuitData() = default;
-  CircuitDescription desc_;
+  mutable CircuitDescription desc_;  // (constants_sigmas: filled late by expanded_description() in the compact form)
   std::unique_ptr<Impl> impl_;
 };
 

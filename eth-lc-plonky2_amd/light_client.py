@@ -14,12 +14,16 @@ from . import build as _build
 
 BLS_PROOF_STAND_IN, SYNC_COMMITTEE_ONLY = 1, 2
 FILL_COPIES = 4   # LCH_FILL_COPIES: one host-written cell per variable class through lcp2_witness_fill_copies (off by default)
+COMPACT_BUILD = 8   # LCH_COMPACT_BUILD: no expanded matrix on the host, the device builds the preprocessed columns from rows (off by default)
 
 
 class Info(ctypes.Structure):
     _fields_ = [("degree_bits", ctypes.c_uint32), ("num_public_inputs", ctypes.c_uint32), ("num_gates", ctypes.c_uint64), ("proof_words", ctypes.c_uint64),
                 ("build_ms", ctypes.c_double), ("attach_ms", ctypes.c_double), ("inner_prove_ms", ctypes.c_double),
-                ("inner_degree_bits", ctypes.c_uint32), ("inner_public_inputs", ctypes.c_uint32)]
+                ("inner_degree_bits", ctypes.c_uint32), ("inner_public_inputs", ctypes.c_uint32),
+                # appended: the phases of build_ms and the bytes attach_ms uploaded for the preprocessed columns
+                ("build_gadgets_ms", ctypes.c_double), ("build_matrix_ms", ctypes.c_double), ("build_identity_ms", ctypes.c_double),
+                ("build_classes_ms", ctypes.c_double), ("build_cycles_ms", ctypes.c_double), ("attach_upload_bytes", ctypes.c_uint64)]
 
 
 _host = None

@@ -463,6 +463,50 @@ void lcp2_circuit_destroy(lcp2_circuit *c);
 /* circuit_digest (4 elements) and constants_sigmas_cap (2^cap_height * 4), host buffers, cap nullable */
 int lcp2_circuit_digest(const lcp2_circuit *c, uint64_t digest[4], uint64_t *cap);
 
+/* THE PREPROCESSED COLUMNS FROM ROWS AND COPY BINDINGS.  lcp2_circuit_create takes constants_sigmas expanded: 85 columns x 2^22 x 8 B =
+ * 2.85 GB at n = 2^22, written on the host and copied up.  What is behind it is one gate index per row, a few gate constants per row and
+ * the list of bound routed cells with their copy class (plonky2: gate_instances and the WirePartition); the two calls below take that
+ * and build the matrix on the device.
+ *   selector columns   for row r with g = gate_of_row[r] (pad_gate for the rows [num_rows, n)): column gates[g].selector_index holds
+ *           gates[g].selector_value, every other selector column 0xFFFFFFFF (plonky2 gates/selectors.rs UNUSED_SELECTOR).
+ *   constant columns   the transposition of row_constants, as given (canonical or not); rows [num_rows, n) and a null row_constants
+ *           are zeros.  The upload is num_rows x (num_constants - num_selectors) x 8 bytes.
+ *   sigma columns      a routed cell that no entry binds holds its own id k_is[col] w^row.  The bound cells of one class form ONE
+ *           cycle in LIST ORDER: each cell maps to the next list entry of the same class, the last one to the first; a class with a
+ *           single bound cell therefore holds its own id too.  Class ids need not be dense.  num_bindings = 0 is legal: the identity.
+ *           A caller that lists the bindings class by class in the order a host builder walks them gets that builder's matrix word
+ *           for word, hence the same cap and circuit digest.
+ * The result does not depend on the order the device ran the list in: the entries are grouped by a stable radix sort of (cls, list
+ * index) over ceil(log2 num_classes) key bits, four bits per pass; atomics only count and keep the smallest refused index.
+ * desc->constants_sigmas and constants_sigmas_mem are ignored by both calls (the pointer may be null).
+ * Refusals, with the reason in lcp2_last_error; nothing is created and `out` of lcp2_circuit_rows_expand is then unspecified:
+ *   LCP2_E_INVALID      null ctx, desc, rows or out; a null list with a non-zero count; bindings_mem above 1; num_rows > n;
+ *           pad_gate >= num_gates; "row R: gate index out of range" for the smallest such row; "binding I: <reason>" for the smallest
+ *           list index I with row >= n, col >= num_routed_wires or cls >= num_classes; "binding J: cell bound twice ... also bound by
+ *           binding I", where I is the smallest list index whose cell is bound more than once and J the next entry that binds the same
+ *           cell (found on the device with a bitmap over the routed cells).  Range problems are reported before double bindings.
+ *   LCP2_E_UNSUPPORTED  num_routed_wires * n >= 2^32 or num_bindings >= 2^32 (cell and list indices are 32-bit).
+ * Lists: gate_of_row and row_constants are host arrays and go up through the context's pinned staging buffer; a host binding list
+ * does too, a device list is read in place.  Both kinds of list are validated on the device, in the pass that reads them first.
+ * Scratch of the context, kept by it like the scratch of the witness calls: slot 1 the two refusal words, slot 2 the work area (gate
+ * table, coset shifts, gate_of_row, row_constants, two bitmaps of a bit per routed cell, two key arrays of 8 bytes per binding, the
+ * digit counts), slot 3 a host binding list; lcp2_circuit_create_from_rows also slot 0, the matrix itself.  No proving state of any
+ * handle is touched: a call may come between the seams of a proof in flight on the same context.  The context's stream is synchronised on return.
+ * Timing (lcp2_prof_*): LCP2_K_OTHER, one scope per pass (constants, identity, keys, each sort pass, cycles). */
+typedef struct { uint32_t row, col, cls; } lcp2_copy_binding;        /* 12 bytes */
+typedef struct {
+  const uint32_t *gate_of_row; size_t num_rows;  /* host; index into desc->gates; rows [num_rows, n) take pad_gate */
+  uint32_t pad_gate;
+  const uint64_t *row_constants;                 /* host, row-major [num_rows][num_constants - num_selectors]; NULL = zeros; rows beyond are zero */
+  const lcp2_copy_binding *bindings; size_t num_bindings; lcp2_mem bindings_mem;
+  uint32_t num_classes;                          /* every cls < num_classes; ids may be sparse */
+} lcp2_circuit_rows;
+/* the matrix only: out = device, [num_constants + num_routed_wires][n], column-major, exactly what desc->constants_sigmas would hold */
+int lcp2_circuit_rows_expand(lcp2_ctx *ctx, const lcp2_circuit_desc *desc, const lcp2_circuit_rows *rows, uint64_t *out);
+/* lcp2_circuit_create with desc->constants_sigmas ignored (may be NULL): the expansion into scratch slot 0 of the context, then the
+ * existing build on it.  The handle is an ordinary prover handle.  (Sharded and verifier-only handles: expand, then their constructors.) */
+int lcp2_circuit_create_from_rows(lcp2_ctx *ctx, const lcp2_circuit_desc *desc, const lcp2_circuit_rows *rows, lcp2_circuit **out);
+
 /* Size in uint64_t words of a proof (layout documented in DESIGN.md, same field order as plonky2's
  * ProofWithPublicInputs: wires_cap, plonk_zs_partial_products_cap, quotient_polys_cap, openings,
  * opening_proof { commit_phase_merkle_caps, query_round_proofs, final_poly, pow_witness }). */
