@@ -110,6 +110,22 @@ class WitnessPlan(ctypes.Structure):
                 ("pos_level_ends", ctypes.c_void_p), ("operands", ctypes.c_void_p), ("noperands", ctypes.c_size_t), ("nlevels", ctypes.c_size_t)]
 
 
+class U32PlanJob(ctypes.Structure):
+    """lcp2_u32_plan_job: one operation of a plonky2_u32 / comparison row whose inputs are operands[first_operand ..] of a plan"""
+    _fields_ = [("row", ctypes.c_uint32), ("kind", ctypes.c_uint16), ("op", ctypes.c_uint16), ("first_operand", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+U32_PLAN_JOB_DTYPE = REC_JOB_DTYPE   # the same 16-byte record; kind is U32_*
+U32_PLAN_OPERANDS = {U32_ARITHMETIC: 3, U32_ADD_MANY: 4, U32_SUBTRACTION: 3, U32_RANGE_CHECK: 1, U32_COMPARISON: 2}
+assert ctypes.sizeof(U32PlanJob) == U32_PLAN_JOB_DTYPE.itemsize == 16
+
+
+class WitnessPlanU32(ctypes.Structure):
+    """lcp2_witness_plan_u32: a witness plan that also holds u32 jobs, in the same levels (lcp2_witness_plan_rows_u32)"""
+    _fields_ = [("base", WitnessPlan), ("u32_jobs", ctypes.c_void_p), ("nu32", ctypes.c_size_t), ("u32_level_ends", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -200,6 +216,7 @@ def load_library():
         "lcp2_rec_gate_rows": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p,
                                          c.c_uint32, c.c_uint64]),
         "lcp2_witness_plan_rows": (c.c_int, [c.c_void_p, c.POINTER(WitnessPlan), c.c_int, c.c_void_p, c.c_uint32, c.c_uint64]),
+        "lcp2_witness_plan_rows_u32": (c.c_int, [c.c_void_p, c.POINTER(WitnessPlanU32), c.c_int, c.c_void_p, c.c_uint32, c.c_uint64]),
         "lcp2_commit_wires_rows_begin": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_commit_wires_chunk": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32]),
         "lcp2_commit_wires_rows_finish": (c.c_int, [c.c_void_p, c.c_void_p]),
@@ -579,6 +596,33 @@ class Context:
         plan = WitnessPlan(ptrs[0], counts[0], rends.ctypes.data if rends.size else None, ptrs[1], counts[1], ptrs[2], counts[2],
                            pends.ctypes.data if pends.size else None, ptrs[3], counts[3], rends.size)
         self._check(self.lib.lcp2_witness_plan_rows(self.handle, ctypes.byref(plan), mem, ctypes.c_void_p(wires_dev), int(ncols), int(n)))
+
+    def witness_plan_rows_u32(self, u32_jobs, rec_jobs, pos_jobs, chain_ends, operands, u32_level_ends, rec_level_ends, pos_level_ends,
+                              wires_dev, ncols, n, nu32=None, nrec=None, npos=None, nchains=None, noperands=None):
+        """lcp2_witness_plan_rows_u32: witness_plan_rows for a plan that also holds plonky2_u32 / comparison jobs, whose inputs are
+        operands of the plan (IMM or CELL).  u32_jobs: U32_PLAN_JOB_DTYPE records, with the other four lists either all numpy arrays
+        (host lists: validated before anything runs) or all device pointers with nu32, nrec, npos, nchains and noperands.  The three
+        level tables are always on the host and equally long.  u32_gates.pack_u32_plan returns all eight."""
+        ends = [np.ascontiguousarray(e, dtype=np.uint32).ravel() for e in (u32_level_ends, rec_level_ends, pos_level_ends)]
+        if len({e.size for e in ends}) != 1:
+            raise Lcp2Error(-1, "u32_level_ends, rec_level_ends and pos_level_ends must have one entry per level each")
+        lists = (u32_jobs, rec_jobs, pos_jobs, chain_ends, operands)
+        on_host = [isinstance(a, np.ndarray) for a in lists]
+        if any(on_host) != all(on_host):
+            raise Lcp2Error(-1, "the five lists must all be host arrays or all be device pointers")
+        if all(on_host):
+            if [a.dtype for a in lists] != [U32_PLAN_JOB_DTYPE, REC_JOB_DTYPE, POS_JOB_DTYPE, np.dtype(np.uint32), REC_OPERAND_DTYPE]:
+                raise Lcp2Error(-1, "the lists must be arrays of U32_PLAN_JOB_DTYPE / REC_JOB_DTYPE / POS_JOB_DTYPE / uint32 / REC_OPERAND_DTYPE records")
+            keep = [np.ascontiguousarray(a).ravel() for a in lists]
+            counts, ptrs, mem = [a.size for a in keep], [a.ctypes.data if a.size else None for a in keep], MEM_HOST
+        else:
+            if None in (nu32, nrec, npos, nchains, noperands):
+                raise Lcp2Error(-1, "device lists need nu32, nrec, npos, nchains and noperands")
+            counts, ptrs, mem = [int(nu32), int(nrec), int(npos), int(nchains), int(noperands)], [a or None for a in lists], MEM_DEVICE
+        end_ptrs = [e.ctypes.data if e.size else None for e in ends]
+        base = WitnessPlan(ptrs[1], counts[1], end_ptrs[1], ptrs[2], counts[2], ptrs[3], counts[3], end_ptrs[2], ptrs[4], counts[4], ends[0].size)
+        plan = WitnessPlanU32(base, ptrs[0], counts[0], end_ptrs[0])
+        self._check(self.lib.lcp2_witness_plan_rows_u32(self.handle, ctypes.byref(plan), mem, ctypes.c_void_p(wires_dev), int(ncols), int(n)))
 
     def verify_batch(self, circuit_data, proofs, public_inputs, mem=MEM_HOST, count=None, head="host"):
         """lcp2_verify_batch: data.verify for a batch of proofs of one circuit (any CircuitData, verifier-only ones included), Merkle

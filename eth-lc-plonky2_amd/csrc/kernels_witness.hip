@@ -17,6 +17,7 @@
 #include "u32_rows.hpp"
 #include "rec_rows.hpp"
 #include "pos_plan.hpp"
+#include "u32_plan.hpp"
 
 namespace lcp2 {
 
@@ -198,6 +199,32 @@ void launch_pos_plan_chains(hipStream_t s, const PosJobDev *jobs, u64 npos, cons
   const u64 threads = (chain_end - chain_begin) * 16;
   hipLaunchKernelGGL(k_pos_plan_chains, dim3((unsigned)((threads + PLAN_CHAIN_THREADS - 1) / PLAN_CHAIN_THREADS)), dim3(PLAN_CHAIN_THREADS), 0, s,
                      jobs, npos, chain_ends, chain_begin, chain_end, operands, noperands, wires, ncols, n, rc, flags, gate, marker);
+}
+
+// One lane per u32 job of one LEVEL of lcp2_witness_plan_rows_u32 (u32_plan.hpp u32_plan_lane: the text tests/emu/emu_plan_u32.cpp
+// runs on the CPU).  A lane reads its 16-byte job (contiguous over the wave), then its 1 to 4 operand records - 16 bytes each,
+// consecutive for a lane; in a plan packed in job order the records of a wave are one contiguous run, so the loads walk whole cache
+// lines - then the cells of its CELL operands, one gathered 8-byte load each, all issued before the first value is looked at.  The
+// operands do not go through LDS: each record is read once, by one lane.  The values are checked, the inputs become a U32JobDev in
+// registers, and u32_job_cells stores exactly as in k_u32_gate_rows: one 8-byte store per cell into its column, contiguous over the
+// wave - 512 bytes - when its 64 jobs are consecutive rows of one (kind, op).  In that order a wave stays on one kind; only
+// ARITHMETIC lanes run the one field inversion.  A refused job folds its shifted index into flags[2] and the family marker into
+// flags[0] (row_flag.hpp); lanes of a level after a refused job's return at once.
+constexpr u32 U32_PLAN_THREADS = 256;
+__global__ __launch_bounds__(U32_PLAN_THREADS) void k_u32_plan_rows(const U32PlanJobDev *__restrict__ jobs, u64 base, u64 begin, u64 end,
+                                                                     const RecOperandDev *__restrict__ operands, u64 noperands, u64 *wires,
+                                                                     u32 ncols, u64 n, u64 *flags, u64 gate, u64 marker) {
+  const u64 i = begin + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (const u32 problem = u32_plan_lane(jobs, base, begin, end, i, operands, noperands, wires, ncols, n, flags, gate)) {
+    atomicMin((unsigned long long *)flags + 2, (unsigned long long)row_refusal(i, problem));
+    atomicMin((unsigned long long *)flags, (unsigned long long)row_refusal(marker, ROW_U32_FAMILY));
+  }
+}
+void launch_u32_plan_rows(hipStream_t s, const U32PlanJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
+                          u64 *wires, u32 ncols, u64 n, u64 *flags, u64 gate, u64 marker) {
+  if (begin >= end) return;
+  hipLaunchKernelGGL(k_u32_plan_rows, dim3((unsigned)((end - begin + U32_PLAN_THREADS - 1) / U32_PLAN_THREADS)), dim3(U32_PLAN_THREADS), 0, s,
+                     jobs, base, begin, end, operands, noperands, wires, ncols, n, flags, gate, marker);
 }
 
 void launch_sha_jobs_level(hipStream_t s, const ShaJobDev *jobs, u32 first, u32 count, const uint32_t *words_in, uint32_t *rec) {

@@ -176,6 +176,12 @@ struct PosJobDev;
 void launch_pos_plan_chains(hipStream_t s, const PosJobDev *jobs, u64 npos, const u32 *chain_ends, u64 chain_begin, u64 chain_end,
                             const RecOperandDev *operands, u64 noperands, u64 *wires, u32 ncols, u64 n, const u64 *rc, u64 *flags, u64 gate,
                             u64 marker);
+// lcp2_witness_plan_rows_u32 (kernels_witness.hip k_u32_plan_rows, u32_plan.hpp): the u32 jobs [begin, end) of one level, one lane
+// each, with the shifted indices of launch_rec_gate_rows (jobs[0] is job `base`); operands: the WHOLE list; flags: the three words
+// of row_flag.hpp, gate the key of this level and marker the index a refused job folds into flags[0]
+struct U32PlanJobDev;
+void launch_u32_plan_rows(hipStream_t s, const U32PlanJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
+                          u64 *wires, u32 ncols, u64 n, u64 *flags, u64 gate, u64 marker);
 // *flag = 1 if a word of p[r * pitch + i] (r < rows, i < width) is a non-zero field element (flag zeroed by the caller)
 void launch_any_nonzero(hipStream_t s, const u64 *p, u64 pitch, u64 width, u32 rows, unsigned long long *flag);
 

@@ -1,7 +1,8 @@
 // The refusal flag of the row generators that validate a job list on the device (lcp2_u32_gate_rows, lcp2_rec_gate_rows,
-// lcp2_witness_plan_rows).
+// lcp2_witness_plan_rows, lcp2_witness_plan_rows_u32).
 //
-// One 64-bit word per call, two for a plan.  The entry point sets it to ROW_NO_PROBLEM before the first launch; a lane whose job is
+// One 64-bit word per call, two for a plan, three for a plan with u32 jobs.  The entry point sets it to ROW_NO_PROBLEM before the
+// first launch; a lane whose job is
 // refused writes no cell and folds row_refusal(index, problem) into the word with a minimum (the kernels: atomicMin; tests/emu: a
 // compare), so after the last launch the word names the FIRST refused job of the list and why (u32_problem_str / rec_problem_str),
 // whatever the order the lanes ran in.  The entry point reads it back once (witness_rows.hip RefusalFlag).
@@ -43,6 +44,23 @@ inline PlanRefusal plan_refusal(const u64 *words, const uint32_t *rec_level_ends
   for (size_t l = 0; l < nlevels; l++)
     if (shifted >= plan_gate(l ? rec_level_ends[l - 1] : 0, l) && shifted < rec_level_ends[l] + plan_shift(l)) return {0, problem, shifted - plan_shift(l)};
   return {0, problem, 0};
+}
+
+// A plan with u32 jobs (lcp2_witness_plan_rows_u32) runs a THIRD family between the two: per level the rec jobs, the u32 jobs
+// (k_u32_plan_rows), the chains.  flags[0] keeps its meaning and its gate.  A refused u32 job of level l folds
+// row_refusal(end_l + l + 1, ROW_U32_FAMILY) into it - the key of a refused chain, one below it in the problem byte: above every rec
+// refusal of the level, below the chain's, so the minimum orders the three families rec / u32 / PoseidonGate - and its own
+//   flags[2]  the minimum of row_refusal(u32 job + plan_shift(l), problem) over the refused u32 jobs, shifted per level like the rec
+//             jobs of flags[0], so that the word orders by list index across levels; read when flags[0] carries ROW_U32_FAMILY.
+// family 2: a u32 job (u32_plan_problem_str).  A call without u32 jobs keeps two words and plan_refusal.
+constexpr u64 ROW_U32_FAMILY = 0xFE;
+inline PlanRefusal plan_refusal_u32(const u64 *words, const uint32_t *rec_level_ends, const uint32_t *u32_level_ends, size_t nlevels) {
+  if (words[0] == ROW_NO_PROBLEM || (words[0] & 0xFF) != ROW_U32_FAMILY) return plan_refusal(words, rec_level_ends, nlevels);
+  const u32 problem = (u32)(words[2] & 0xFF);
+  const u64 shifted = words[2] >> 8;
+  for (size_t l = 0; l < nlevels; l++)
+    if (shifted >= plan_gate(l ? u32_level_ends[l - 1] : 0, l) && shifted < u32_level_ends[l] + plan_shift(l)) return {2, problem, shifted - plan_shift(l)};
+  return {2, problem, 0};
 }
 
 }  // namespace lcp2

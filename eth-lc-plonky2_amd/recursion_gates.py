@@ -724,25 +724,30 @@ def pack_witness_plan(levels):
 def run_witness_plan(plan, ncols, n, start=None, levels=None):
     """lcp2_witness_plan_rows in Python integers: the matrix [ncols][n] after the plan (its first `levels` levels) ran on `start`
     (zeros by default).  The rec jobs of a level through run_plan, then its chains row by row through poseidon_py.gate_row"""
-    from . import poseidon_py as pp
     out = np.zeros((ncols, n), dtype=np.uint64) if start is None else start.copy()
     nlevels = len(plan.rec_level_ends) if levels is None else levels
     for lv in range(nlevels):
         rb, re = (int(plan.rec_level_ends[lv - 1]) if lv else 0), int(plan.rec_level_ends[lv])
         out = run_plan(plan.rec_jobs[rb:re], plan.operands, [re - rb], ncols, n, start=out)
-        for g in range(int(plan.pos_level_ends[lv - 1]) if lv else 0, int(plan.pos_level_ends[lv])):
-            prev = None
-            for j in plan.pos_jobs[(int(plan.chain_ends[g - 1]) if g else 0):int(plan.chain_ends[g])]:
-                vals = []
-                for o in plan.operands[int(j["first_operand"]):int(j["first_operand"]) + POS_PLAN_OPERANDS]:
-                    src = int(o["src"])
-                    vals.append(int(out[int(o["col"]), int(o["v"])]) % P if src == REC_CELL else prev[int(o["col"])] if src == PLAN_PREV
-                                else int(o["v"]) % P)
-                assert vals[0] in (0, 1)
-                row = pp.gate_row(vals[1:], vals[0])
-                out[:pp.NUM_WIRES, int(j["row"])] = np.array(row, dtype=np.uint64)
-                prev = row[pp.W_OUTPUT:pp.W_OUTPUT + 12]
+        run_level_chains(plan, lv, out)
     return out
+
+
+def run_level_chains(plan, lv, out):
+    """the PoseidonGate chains of level `lv` of a witness plan, row by row, into the matrix `out` (in place)"""
+    from . import poseidon_py as pp
+    for g in range(int(plan.pos_level_ends[lv - 1]) if lv else 0, int(plan.pos_level_ends[lv])):
+        prev = None
+        for j in plan.pos_jobs[(int(plan.chain_ends[g - 1]) if g else 0):int(plan.chain_ends[g])]:
+            vals = []
+            for o in plan.operands[int(j["first_operand"]):int(j["first_operand"]) + POS_PLAN_OPERANDS]:
+                src = int(o["src"])
+                vals.append(int(out[int(o["col"]), int(o["v"])]) % P if src == REC_CELL else prev[int(o["col"])] if src == PLAN_PREV
+                            else int(o["v"]) % P)
+            assert vals[0] in (0, 1)
+            row = pp.gate_row(vals[1:], vals[0])
+            out[:pp.NUM_WIRES, int(j["row"])] = np.array(row, dtype=np.uint64)
+            prev = row[pp.W_OUTPUT:pp.W_OUTPUT + 12]
 
 
 def verifier_gateset(native=True):

@@ -713,3 +713,176 @@ def witness_jobs(wires, gate_of_row, G):
                 jobs["in"][:, k] = v
             parts.append(jobs)
     return np.concatenate(parts) if parts else np.zeros(0, dtype=U32_JOB_DTYPE)
+
+
+# ---------------------------------------------------------------- u32 jobs inside a witness plan (lcp2_witness_plan_rows_u32)
+# kind -> the wires of operation `op` that other operations may read: (wire, what it holds: "u32", "carry" (0..3) or "bit")
+U32_OUTPUT_CELLS = {
+    U32_ARITHMETIC: lambda op: [(6 * op + 3, "u32"), (6 * op + 4, "u32")],            # output_low, output_high
+    U32_ADD_MANY: lambda op: [(6 * op + 4, "u32"), (6 * op + 5, "carry")],            # output_result, output_carry
+    U32_SUBTRACTION: lambda op: [(5 * op + 3, "u32"), (5 * op + 4, "bit")],           # output_result, output_borrow
+    U32_RANGE_CHECK: lambda op: [],
+    U32_COMPARISON: lambda op: [(2, "bit")],                                          # result_bool
+}
+
+
+def plan_job_cells(kind, op, vals):
+    """{column: value} of one u32 job in Python integers: what lcp2_u32_gate_rows writes for (kind, op) on the input values `vals`
+    (u32 each; the generators row_* of this module, one operation at a time)"""
+    v = [int(x) for x in vals]
+    assert len(v) == len(U32_JOB_KINDS[kind][2](op)) and all(0 <= x < 1 << 32 for x in v), (kind, op, v)
+    out = {}
+
+    def limbs(first, value, count):
+        for j, limb in enumerate(_digits(value, count)):
+            out[first + j] = limb
+
+    if kind == U32_ARITHMETIC:
+        total = v[0] * v[1] + v[2]
+        lo, hi = total & 0xFFFFFFFF, total >> 32
+        for k, x in enumerate(v + [lo, hi, 0 if hi == 0xFFFFFFFF else pow(0xFFFFFFFF - hi, P - 2, P)]):
+            out[6 * op + k] = x
+        limbs(6 * U32_ARITH_OPS + U32_ARITH_LIMBS * op, total, U32_ARITH_LIMBS)
+    elif kind == U32_ADD_MANY:
+        total = sum(v)
+        for k, x in enumerate(v + [total & 0xFFFFFFFF, total >> 32]):
+            out[6 * op + k] = x
+        limbs(6 * ADD_MANY_OPS + 18 * op, total, ADD_MANY_RESULT_LIMBS + ADD_MANY_CARRY_LIMBS)
+    elif kind == U32_SUBTRACTION:
+        assert v[2] <= 1
+        d = v[0] - v[1] - v[2]
+        borrow = 1 if d < 0 else 0
+        for k, x in enumerate(v + [d + (borrow << 32), borrow]):
+            out[5 * op + k] = x
+        limbs(5 * SUB_OPS + SUB_LIMBS * op, d + (borrow << 32), SUB_LIMBS)
+    elif kind == U32_RANGE_CHECK:
+        out[op] = v[0]
+        limbs(RANGE_INPUTS + RANGE_AUX * op, v[0], RANGE_AUX)
+    else:
+        nc = CMP_CHUNKS
+        fc, sc = _digits(v[0], nc), _digits(v[1], nc)
+        out[0], out[1] = v
+        so_far = 0
+        for i in range(nc):
+            diff = (sc[i] - fc[i]) % P
+            eq = 1 if diff == 0 else 0
+            out[4 + i], out[4 + nc + i] = fc[i], sc[i]
+            out[4 + 2 * nc + i] = 0 if eq else pow(diff, P - 2, P)
+            out[4 + 3 * nc + i] = eq
+            inter = eq * so_far % P
+            out[4 + 4 * nc + i] = inter
+            so_far = (inter + (1 - eq) * diff) % P
+        out[3] = so_far
+        total = ((1 << CMP_CHUNK_BITS) + so_far) % P
+        for i in range(CMP_CHUNK_BITS + 1):
+            out[4 + 5 * nc + i] = (total >> i) & 1
+        out[2] = (total >> CMP_CHUNK_BITS) & 1
+    return out
+
+
+def pack_u32_plan(levels):
+    """levels: [(u32 items, rec items, chains), ..]: u32 items [(row, kind, op, [IMM(..) / CELL(..), ..]), ..] with the operands in
+    the order of `in` of a U32_JOB_DTYPE record, rec items and chains as in recursion_gates.pack_witness_plan -> a namespace of the
+    lists of lcp2_witness_plan_rows_u32: those of pack_witness_plan, u32_jobs (U32_PLAN_JOB_DTYPE, every level sorted by
+    (kind, op, row): the order in which the kernel stores contiguously) and u32_level_ends.  The operands of the u32 jobs follow
+    those of the other two families in the one list, in job order."""
+    from types import SimpleNamespace
+    from . import recursion_gates as rg
+    from .binding import U32_PLAN_JOB_DTYPE, U32_PLAN_OPERANDS
+    base = rg.pack_witness_plan([(rec, chains) for _, rec, chains in levels])
+    items = [sorted(u32, key=lambda it: (it[1], it[2], it[0])) for u32, _, _ in levels]
+    jobs = np.zeros(sum(len(level) for level in items), dtype=U32_PLAN_JOB_DTYPE)
+    ops = np.zeros(sum(len(it[3]) for level in items for it in level), dtype=base.operands.dtype)
+    at = k = 0
+    ends = []
+    for level in items:
+        for row, kind, op, operands in level:
+            assert len(operands) == U32_PLAN_OPERANDS[kind], (kind, len(operands))
+            jobs[k] = (row, kind, op, base.operands.size + at, 0)
+            for v, col, src in operands:
+                ops[at] = (v % (1 << 64), col, src)
+                at += 1
+            k += 1
+        ends.append(k)
+    return SimpleNamespace(u32_jobs=jobs, u32_level_ends=np.array(ends, dtype=np.uint32), rec_jobs=base.rec_jobs, pos_jobs=base.pos_jobs,
+                           chain_ends=base.chain_ends, operands=np.concatenate([base.operands, ops]), rec_level_ends=base.rec_level_ends,
+                           pos_level_ends=base.pos_level_ends)
+
+
+def plan_u32_model(start, plan, levels=None):
+    """lcp2_witness_plan_rows_u32 in Python integers: the matrix [ncols][n] after the plan (its first `levels` levels) ran on `start`.
+    Per level the rec jobs (recursion_gates.run_plan), then the u32 jobs through plan_job_cells, then the PoseidonGate chains"""
+    from . import recursion_gates as rg
+    from .binding import PLAN_CELL, U32_PLAN_OPERANDS
+    out = start.copy()
+    ncols, n = out.shape
+    for lv in range(len(plan.u32_level_ends) if levels is None else levels):
+        rb, re = (int(plan.rec_level_ends[lv - 1]) if lv else 0), int(plan.rec_level_ends[lv])
+        out = rg.run_plan(plan.rec_jobs[rb:re], plan.operands, [re - rb], ncols, n, start=out)
+        for j in plan.u32_jobs[(int(plan.u32_level_ends[lv - 1]) if lv else 0):int(plan.u32_level_ends[lv])]:
+            kind, op, first = int(j["kind"]), int(j["op"]), int(j["first_operand"])
+            vals = [int(out[int(o["col"]), int(o["v"])]) % P if o["src"] == PLAN_CELL else int(o["v"]) % P
+                    for o in plan.operands[first:first + U32_PLAN_OPERANDS[kind]]]
+            for col, v in plan_job_cells(kind, op, vals).items():
+                out[col, int(j["row"])] = v
+        rg.run_level_chains(plan, lv, out)
+    return out
+
+
+def random_u32_plan(rng, n, levels, jobs_per_level):
+    """A levelled plan of `levels` levels with jobs_per_level[l] u32 jobs in level l over the rows below n, every (row, op) slot used
+    at most once and a row holding one kind.  Level 0 is IMM only; a job of a later level draws each operand, more often than not,
+    as the CELL of an output of an earlier level (U32_OUTPUT_CELLS), so that every value stays a u32: a carry operand comes from an
+    output_carry, output_borrow or result_bool cell (or a small IMM), a borrow operand from an output_borrow or result_bool cell
+    (or IMM 0 / 1).  Some IMMs are spelled v + p.  Returns the namespace of pack_u32_plan with row_kind ([n], -1: no job) added."""
+    from .recursion_gates import CELL, IMM
+    assert len(jobs_per_level) == levels
+    kinds = [U32_ADD_MANY, U32_SUBTRACTION, U32_RANGE_CHECK, U32_ARITHMETIC, U32_ADD_MANY, U32_SUBTRACTION, U32_RANGE_CHECK, U32_COMPARISON,
+             U32_ARITHMETIC, U32_COMPARISON]
+    row_kind = np.array([kinds[r % len(kinds)] for r in range(n)])
+    slots = [(r, int(row_kind[r]), op) for r in range(n) for op in range(U32_JOB_KINDS[int(row_kind[r])][1])]
+    assert sum(jobs_per_level) <= len(slots), "more jobs than operation slots in %d rows" % n
+    # the first slots drawn hold every (kind, op) once, so that all of them occur whatever the counts; then the rest, shuffled
+    order = [slots[i] for i in rng.permutation(len(slots))]
+    first, seen = [], set()
+    for s in order:
+        if s[1:] not in seen:
+            seen.add(s[1:])
+            first.append(s)
+    order = first + [s for s in order if s not in set(first)]
+    if sum(jobs_per_level) >= len(first):   # spread: a large level must not swallow every slot of one kind's outputs
+        order = order[:sum(jobs_per_level)]
+        order = [order[i] for i in rng.permutation(len(order))]
+    pool = {"u32": [], "carry": [], "bit": []}
+
+    def imm(hi):
+        v = int(rng.integers(0, hi))
+        return IMM(v + P if v < 0xFFFFFFFF and rng.integers(0, 8) == 0 else v)
+
+    def operand(accepts, hi):
+        cells = [c for what in accepts for c in pool[what]]
+        if cells and rng.integers(0, 3):
+            return CELL(*cells[int(rng.integers(0, len(cells)))])
+        return imm(hi)
+
+    plan, used, at = [], np.zeros(n, dtype=bool), 0
+    for lv in range(levels):
+        level, produced = [], []
+        for row, kind, op in order[at:at + jobs_per_level[lv]]:
+            any_u32 = lambda: operand(("u32", "carry", "bit"), 1 << 32)   # noqa: E731
+            if kind == U32_ADD_MANY:
+                operands = [any_u32(), any_u32(), any_u32(), operand(("carry", "bit"), 4)]
+            elif kind == U32_SUBTRACTION:
+                operands = [any_u32(), any_u32(), operand(("bit",), 2)]
+            else:
+                operands = [any_u32() for _ in U32_JOB_KINDS[kind][2](op)]
+            level.append((row, kind, op, operands))
+            produced += [(what, (row, col)) for col, what in U32_OUTPUT_CELLS[kind](op)]
+            used[row] = True
+        at += jobs_per_level[lv]
+        plan.append((level, [], []))
+        for what, cell in produced:   # readable from the next level on
+            pool[what].append(cell)
+    packed = pack_u32_plan(plan)
+    packed.row_kind = np.where(used, row_kind, -1)
+    return packed

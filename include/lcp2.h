@@ -353,6 +353,39 @@ typedef struct {
 int lcp2_witness_plan_rows(lcp2_ctx *ctx, const lcp2_witness_plan *plan, lcp2_mem lists_mem,
                            uint64_t *wires /* device, column-major [ncols >= 135][n] */, uint32_t ncols, uint64_t n);
 
+/* A witness plan that also holds plonky2_u32 and comparison rows: the jobs of lcp2_u32_gate_rows with their inputs as OPERANDS of
+ * the plan's one operand list, so that the output of one operation feeds the next through the matrix and no value is computed on
+ * the host.  One replay fills a circuit that mixes SHA-256 / BigUint rows, recursion-gate rows and PoseidonGate chains; per proof
+ * only the IMM values of the leaves change.  `base` is the plan of lcp2_witness_plan_rows, unchanged.
+ * A u32 job takes its operands from operands[first_operand] on, in the order of in[] of lcp2_u32_job: ARITHMETIC 3, ADD_MANY 4,
+ * SUBTRACTION 3, RANGE_CHECK 1, COMPARISON 2.  An operand is LCP2_PLAN_IMM or LCP2_PLAN_CELL (LCP2_PLAN_PREV is refused as
+ * "operand src above 1", as in a rec job), is canonicalised when read, and its canonical value must be below 2^32.  The job writes
+ * exactly the cells lcp2_u32_gate_rows writes for the same (kind, op) and input values, and no other cell.
+ * Levels: level l holds the rec jobs of base.rec_level_ends, the u32 jobs [u32_level_ends[l-1], u32_level_ends[l]) and the chains
+ * of base.pos_level_ends; the launches go to the context's stream in that order, with no host wait between levels.  A job may read
+ * any cell the matrix held before the call or that an EARLIER level of any family writes; reading what the same level writes is
+ * the caller's error and is not detected.  A level may be empty in any family.  Inside a level any order of the u32 jobs is
+ * correct; the FAST order is (kind, op, row), as for lcp2_u32_gate_rows.  The library does not sort.
+ * LCP2_MEM_HOST: the lists are validated completely - rec jobs, then u32 jobs, then PoseidonGate jobs; structure, and the values
+ * that are IMM - before anything is written, and go up through the pinned staging buffer; the u32 plan jobs SHARE scratch slot 3
+ * of the context with the PoseidonGate jobs and chain_ends, each list at an offset rounded to 16 bytes.  LCP2_MEM_DEVICE: the
+ * kernels validate, and no index is used before it is checked.  CELL values are only seen in the kernel: the refused job writes
+ * nothing, the valid jobs of its level and of earlier levels are written, every later level writes nothing in all three families,
+ * and the call returns LCP2_E_INVALID naming the first refused job: "plan rows: u32 job N: <reason>".  If several families refuse
+ * in one level the rec job is named first, then the u32 job, then the PoseidonGate job.
+ * Refused u32 jobs: row >= n, an unknown kind, op out of range for the kind, first_operand + count > noperands, an operand src
+ * above 1, a CELL with col >= ncols or v >= n; by VALUE an operand of 2^32 or more and a subtraction borrow above 1.  The argument
+ * checks are those of lcp2_witness_plan_rows, with u32_jobs / u32_level_ends among the lists.  All counts zero is LCP2_OK; with
+ * nu32 = 0 the call IS lcp2_witness_plan_rows(&plan->base, ...).  The context's stream is synchronised on return. */
+typedef struct { uint32_t row; uint16_t kind /* LCP2_U32_* */, op; uint32_t first_operand, reserved; } lcp2_u32_plan_job; /* 16 bytes */
+typedef struct {
+  lcp2_witness_plan base;                 /* rec jobs, PoseidonGate chains, the ONE operand list, nlevels: as above */
+  const lcp2_u32_plan_job *u32_jobs; size_t nu32;   /* with the lists (lists_mem) */
+  const uint32_t *u32_level_ends;         /* host, [nlevels], ascending, last == nu32 */
+} lcp2_witness_plan_u32;
+int lcp2_witness_plan_rows_u32(lcp2_ctx *ctx, const lcp2_witness_plan_u32 *plan, lcp2_mem lists_mem,
+                               uint64_t *wires /* device, column-major [ncols >= 135][n] */, uint32_t ncols, uint64_t n);
+
 /* device buffers for callers that keep the witness resident in HBM */
 int lcp2_buffer_alloc(lcp2_ctx *ctx, size_t bytes, void **dev);
 int lcp2_buffer_free(lcp2_ctx *ctx, void *dev);
