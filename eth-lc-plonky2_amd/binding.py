@@ -78,7 +78,8 @@ POSEIDON_ROW_DTYPE = np.dtype([("row", "<u4"), ("swap", "<u4"), ("in", "<u8", (1
 assert POSEIDON_ROW_DTYPE.itemsize == 104
 SHA_JOB_DTYPE = np.dtype([("first_row", "<u4"), ("in_src", "<i4", (16,))])   # lcp2_sha_job as a numpy record
 CELL_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("value", "<u8")])      # lcp2_cell as a numpy record
-assert SHA_JOB_DTYPE.itemsize == 68 and CELL_DTYPE.itemsize == 16
+CELL_REF_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4")])                      # lcp2_cell_ref as a numpy record
+assert SHA_JOB_DTYPE.itemsize == 68 and CELL_DTYPE.itemsize == 16 and CELL_REF_DTYPE.itemsize == 8
 SHA_ROWS, SHA_ROW_COLUMNS = 310, 108   # rows of one two_to_one_sha256, columns lcp2_sha256_witness writes in each
 
 class RecOperand(ctypes.Structure):
@@ -248,6 +249,7 @@ def load_library():
         "lcp2_prove": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]),
         "lcp2_witness_fill_copies": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.POINTER(FillReport)]),
         "lcp2_circuit_copy_classes": (c.c_int, [c.c_void_p, c.c_void_p, c.POINTER(c.c_uint64)]),
+        "lcp2_witness_settle_copies": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.POINTER(FillReport)]),
         "lcp2_check_witness": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_size_t, c.POINTER(WitnessReport), c.c_void_p, c.c_uint32]),
         "lcp2_commit_wires": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]),
         "lcp2_commit_wires_coeffs": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]),
@@ -940,15 +942,26 @@ class CircuitData:
         array of CELL_DTYPE records, or with mem=MEM_DEVICE a device pointer to `ncells` lcp2_cell records.  Returns the FillReport;
         conflicting values (LCP2_E_UNSAT) do not raise: report.unsat is set and report.message names the cells.  Every other status
         raises Lcp2Error."""
+        return self._copies_call(self.lib.lcp2_witness_fill_copies, cells, CELL_DTYPE, "cells must be an array of CELL_DTYPE records", wires_ptr, mem, ncells)
+
+    def settle_copies(self, sources, wires_ptr, mem=MEM_HOST, nsources=None):
+        """lcp2_witness_settle_copies: the source with the smallest list index of each copy class gives the word the device matrix
+        `wires_ptr` ([num_wires][n]) holds at its cell to every other routed cell of the class.  sources: a numpy array of
+        CELL_REF_DTYPE records, or with mem=MEM_DEVICE a device pointer to `nsources` lcp2_cell_ref records.  Returns what
+        fill_copies returns."""
+        return self._copies_call(self.lib.lcp2_witness_settle_copies, sources, CELL_REF_DTYPE, "sources must be an array of CELL_REF_DTYPE records", wires_ptr, mem,
+                                 nsources)
+
+    def _copies_call(self, call, records, dtype, dtype_message, wires_ptr, mem, count):
         if mem == MEM_HOST:
-            if not isinstance(cells, np.ndarray) or cells.dtype != CELL_DTYPE:
-                raise Lcp2Error(-1, "cells must be an array of CELL_DTYPE records")
-            c = np.ascontiguousarray(cells).ravel()
+            if not isinstance(records, np.ndarray) or records.dtype != dtype:
+                raise Lcp2Error(-1, dtype_message)
+            c = np.ascontiguousarray(records).ravel()
             p, count = (_ptr(c) if c.size else None), c.size
         else:
-            p, count = ctypes.c_void_p(cells), int(ncells)
+            p, count = ctypes.c_void_p(records), int(count)
         report = FillReport()
-        rc = self.lib.lcp2_witness_fill_copies(self.handle, p, count, mem, ctypes.c_void_p(wires_ptr), ctypes.byref(report))
+        rc = call(self.handle, p, count, mem, ctypes.c_void_p(wires_ptr), ctypes.byref(report))
         if rc == E_UNSAT:
             report.unsat = True
             report.message = self.lib.lcp2_last_error(self.ctx.handle).decode()

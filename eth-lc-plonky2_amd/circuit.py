@@ -598,6 +598,18 @@ def fill_copies_model(circ, cells, wires, class_of=None):
                 refused=refused, status=-1 if refused is not None else (-5 if conflicts else 0))
 
 
+def settle_copies_model(circ, sources, wires, class_of=None):
+    """lcp2_witness_settle_copies on a host matrix `wires` [num_wires][n] (changed in place).  sources: records with row and col (the
+    binding's CELL_REF_DTYPE).  By definition fill_copies_model applied to the list whose values are gathered from `wires` before
+    anything is changed (an entry out of range gathers nothing and is refused there as here); the same return dict."""
+    n, W = circ.n, circ.params.num_wires
+    cells = np.zeros(len(sources), dtype=[("row", "<u4"), ("col", "<u4"), ("value", "<u8")])
+    cells["row"], cells["col"] = sources["row"], sources["col"]
+    ok = (cells["row"] < n) & (cells["col"] < W)
+    cells["value"][ok] = wires[cells["col"][ok], cells["row"][ok]]
+    return fill_copies_model(circ, cells, wires, class_of)
+
+
 # ---------------------------------------------------------------- rows and copy bindings: the numpy model of lcp2_circuit_rows_expand
 BINDING_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("cls", "<u4")])   # = binding.BINDING_DTYPE (lcp2_copy_binding)
 

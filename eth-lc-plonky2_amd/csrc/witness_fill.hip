@@ -1,6 +1,7 @@
 // lcp2_witness_fill_copies and lcp2_circuit_copy_classes: one value per copy class goes up, the device hands it to every routed cell
 // of the class (plonky2: PartitionWitness::get_full_witness).  The per-cell texts are witness_fill.hpp (portable: tests/emu/emu_fill.cpp
-// runs them on the CPU); here are the kernels, the one-time construction of the class table and the two entry points.  Nothing of the
+// runs them on the CPU); here are the kernels, the one-time construction of the class table and the entry points - also
+// lcp2_witness_settle_copies, the same call with the values read from the matrix (witness_settle.hpp, the k_settle_* kernels).  Nothing of the
 // proving state of the handle is read or written: the table is a buffer of its own in the handle, everything else is scratch of
 // the context.  All kernels are bandwidth bound: one lane per cell, rows in the fast dimension, so the loads of class_of / label and
 // the stores into the matrix are contiguous; the gathers (label[ptr], rank[label], owner[class], the owner's list entry) are the
@@ -8,6 +9,7 @@
 #include "circuit_state.hpp"
 #include "row_stage.hpp"
 #include "witness_fill.hpp"
+#include "witness_settle.hpp"
 
 using namespace lcp2;
 
@@ -155,6 +157,56 @@ __global__ void k_fill_first_conflict(const CellDev *__restrict__ cells, const u
   res[FILL_R_OWNER_CELL] = (u64)oc.row | (u64)oc.col << 32;
 }
 
+// ---- lcp2_witness_settle_copies: the same call with the values read from the matrix (witness_settle.hpp, where the order of the
+// passes is argued: owner, then conflicts, then the broadcast, which alone stores to the matrix and reads only owner cells, which it
+// never stores to).  One launch each, on one stream, so each pass sees the one before complete.
+// one lane per source: validation, the minimum on the class's owner word, the mark.  No access to the matrix
+__global__ __launch_bounds__(FILL_THREADS) void k_settle_owner(const CellRefDev *__restrict__ refs, u64 nsources, u32 *class_of, u32 *owner, u64 n, u32 num_wires,
+                                                               u32 num_routed, u64 *flag) {
+  const u64 i = (u64)blockIdx.x * FILL_THREADS + threadIdx.x;
+  if (const u32 problem = settle_owner_lane(refs, nsources, i, class_of, owner, n, num_wires, num_routed))
+    atomicMin((unsigned long long *)flag, (unsigned long long)row_refusal(i, problem));
+}
+// one lane per source, after the owners are known and before any word of the matrix changes: the owned classes and the conflicts
+__global__ __launch_bounds__(FILL_THREADS) void k_settle_conflicts(const CellRefDev *__restrict__ refs, u64 nsources, const u32 *__restrict__ class_of,
+                                                                   const u32 *__restrict__ owner, const u64 *__restrict__ wires, u64 n, u32 num_wires,
+                                                                   u32 num_routed, u64 *res) {
+  const u64 i = (u64)blockIdx.x * FILL_THREADS + threadIdx.x;
+  const u32 what = settle_conflict_lane(refs, nsources, i, class_of, owner, wires, n, num_wires, num_routed);
+  const u32 owners = fill_wave_sum(what == FILL_IS_OWNER ? 1u : 0u), conflicts = fill_wave_sum(what == FILL_CONFLICT ? 1u : 0u);
+  const bool lead = (threadIdx.x & 63) == 0;
+  if (owners && lead) atomicAdd((unsigned long long *)&res[FILL_R_CLASSES_SET], (unsigned long long)owners);
+  if (conflicts) {  // wave-uniform
+    const u64 first = fill_wave_min(what == FILL_CONFLICT ? i : ~0ull);
+    if (lead) {
+      atomicAdd((unsigned long long *)&res[FILL_R_CONFLICTS], (unsigned long long)conflicts);
+      atomicMin((unsigned long long *)&res[FILL_R_CONFLICT_INDEX], (unsigned long long)first);
+    }
+  }
+}
+// one lane per routed cell: class_of streams along rows, owner[class] -> the source -> the word at its cell are dependent gathers,
+// the store is along rows.  wires is read and written here, so it carries no __restrict__ (the lanes' reads and writes are disjoint
+// words all the same, witness_settle.hpp)
+__global__ __launch_bounds__(FILL_THREADS) void k_settle_broadcast(const CellRefDev *__restrict__ refs, u32 *class_of, const u32 *__restrict__ owner, u64 *wires,
+                                                                   u64 n, u64 ncells_routed, u64 *res) {
+  const u64 cell = (u64)blockIdx.x * FILL_THREADS + threadIdx.x;
+  const u32 filled = cell < ncells_routed ? settle_broadcast_cell(refs, class_of, owner, wires, n, (u32)cell) : 0;
+  const u32 sum = fill_wave_sum(filled);
+  if (sum && (threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&res[FILL_R_FILLED], (unsigned long long)sum);
+}
+// k_fill_first_conflict for a list of sources
+__global__ void k_settle_first_conflict(const CellRefDev *__restrict__ refs, const u32 *__restrict__ class_of, const u32 *__restrict__ owner, u64 n,
+                                        u32 num_routed, u64 *res) {
+  const u64 i = res[FILL_R_CONFLICT_INDEX];
+  if (i == ~0ull) return;
+  const CellRefDev c = refs[i];
+  const u32 o = owner[settle_class_of_source(c, class_of, n, num_routed)];
+  const CellRefDev oc = refs[o];
+  res[FILL_R_OWNER_INDEX] = o;
+  res[FILL_R_CONFLICT_CELL] = (u64)c.row | (u64)c.col << 32;
+  res[FILL_R_OWNER_CELL] = (u64)oc.row | (u64)oc.col << 32;
+}
+
 namespace {
 std::string cell_name(u64 cell, u64 n) { return "(row " + std::to_string(cell % n) + ", wire " + std::to_string(cell / n) + ")"; }
 
@@ -262,39 +314,43 @@ extern "C" int lcp2_circuit_copy_classes(lcp2_circuit *c, uint32_t *class_of, ui
   return LCP2_OK;
 }
 
-extern "C" int lcp2_witness_fill_copies(lcp2_circuit *c, const lcp2_cell *cells, size_t ncells, lcp2_mem cells_mem, uint64_t *wires,
-                                        lcp2_fill_report *report) {
-  static_assert(sizeof(lcp2_cell) == sizeof(CellDev), "ABI structs must match the kernels'");
+namespace {
+// What lcp2_witness_fill_copies (Entry = CellDev: the values are in the list) and lcp2_witness_settle_copies (Entry = CellRefDev: the
+// values are in the matrix) share: the argument checks, the host validation and the staging of a host list, the table, the cleared
+// result block and owner words, the marks' bracket around the passes, the one download and the messages.  `passes` launches the
+// call's kernels in ITS order; list_bytes is what the profile books per entry, device_note what a refused device entry left done.
+template <class Entry, class Passes>
+int copies_call(lcp2_circuit *c, const std::string &who, const Entry *list, size_t count, lcp2_mem mem, uint64_t *wires, lcp2_fill_report *report, double list_bytes,
+                const char *device_note, Passes passes) {
   LCP2_TRY(entry_guard(c, {wires}));
   lcp2_ctx *ctx = c->ctx;
-  if ((unsigned)cells_mem > 1) return ctx->fail(LCP2_E_INVALID, "fill copies: bad lcp2_mem");
-  if (ncells && !cells) return ctx->fail(LCP2_E_INVALID, "fill copies: the list is null but its count is not zero");
-  LCP2_TRY(fill_guard(c, "fill copies"));
-  if ((u64)ncells >= FILL_MAX_CELLS) return ctx->fail(LCP2_E_UNSUPPORTED, "fill copies: 2^32 listed cells or more (list indices are 32-bit)");
+  if ((unsigned)mem > 1) return ctx->fail(LCP2_E_INVALID, who + ": bad lcp2_mem");
+  if (count && !list) return ctx->fail(LCP2_E_INVALID, who + ": the list is null but its count is not zero");
+  LCP2_TRY(fill_guard(c, who.c_str()));
+  if ((u64)count >= FILL_MAX_CELLS) return ctx->fail(LCP2_E_UNSUPPORTED, who + ": 2^32 listed cells or more (list indices are 32-bit)");
   lcp2_fill_report out{};
   out.conflict_index = ~0ull; out.owner_index = ~0ull;
-  if (!ncells) {
+  if (!count) {
     if (report) *report = out;
     return LCP2_OK;
   }
-  const CellDev *list = (const CellDev *)cells;
   const u64 n = 1ull << c->p.degree_bits;
   const u32 W = c->p.num_wires, NR = c->p.num_routed_wires;
-  if (cells_mem == LCP2_MEM_HOST) {
+  if (mem == LCP2_MEM_HOST) {
     u32 problem = 0;
-    if (const size_t at = fill_cells_problem(list, ncells, n, W, &problem); at != ncells)
-      return ctx->fail(LCP2_E_INVALID, "fill copies: cell " + std::to_string(at) + ": " + fill_cell_problem_str(problem));
+    if (const size_t at = fill_cells_problem(list, count, n, W, &problem); at != count)
+      return ctx->fail(LCP2_E_INVALID, who + ": cell " + std::to_string(at) + ": " + fill_cell_problem_str(problem));
   }
   StageEnv e(c);
   LCP2_TRY(e.status);
   hipStream_t s = e.s;
   LCP2_TRY(copy_classes_ensure(c, e));
   const u64 routed = (u64)NR * n, num_classes = c->copy_num_classes;
-  if (cells_mem == LCP2_MEM_HOST) {
+  if (mem == LCP2_MEM_HOST) {
     void *up;
-    LCP2_TRY(scratch_ensure(ctx, 3, ncells * sizeof(lcp2_cell), &up));
-    LCP2_TRY(Stage{ctx}.behind(up, cells, ncells * sizeof(lcp2_cell)));
-    list = (const CellDev *)up;
+    LCP2_TRY(scratch_ensure(ctx, 3, count * sizeof(Entry), &up));
+    LCP2_TRY(Stage{ctx}.behind(up, list, count * sizeof(Entry)));
+    list = (const Entry *)up;
   }
   u64 *res;
   LCP2_TRY(scratch_ensure(ctx, 2, FILL_R_WORDS * 8 + (size_t)num_classes * 4, (void **)&res));
@@ -307,15 +363,11 @@ extern "C" int lcp2_witness_fill_copies(lcp2_circuit *c, const lcp2_cell *cells,
     launch_set_words(s, res, w, FILL_R_WORDS);
     if (num_classes) LCP2_HIP(ctx, hipMemsetAsync(owner, 0xFF, (size_t)num_classes * 4, s));  // FILL_NONE
   }
-  const unsigned list_blocks = (unsigned)((ncells + FILL_THREADS - 1) / FILL_THREADS);
   c->copy_classes_ready = false;  // the marks of the listed cells are in the table until the broadcast has taken them off
   {
-    ProfScope ps(ctx, LCP2_K_OTHER, (double)ncells * 40.0 + (double)routed * 4.0);
-    hipLaunchKernelGGL(k_fill_owner, dim3(list_blocks), dim3(FILL_THREADS), 0, s, list, (u64)ncells, class_of, owner, (u64 *)wires, n, W, NR, flag.d);
-    hipLaunchKernelGGL(k_fill_broadcast, dim3((unsigned)((routed + FILL_THREADS - 1) / FILL_THREADS)), dim3(FILL_THREADS), 0, s, list, class_of, owner,
-                       (u64 *)wires, routed, res);
-    hipLaunchKernelGGL(k_fill_conflicts, dim3(list_blocks), dim3(FILL_THREADS), 0, s, list, (u64)ncells, class_of, owner, n, W, NR, res);
-    hipLaunchKernelGGL(k_fill_first_conflict, dim3(1), dim3(1), 0, s, list, class_of, owner, n, NR, res);
+    ProfScope ps(ctx, LCP2_K_OTHER, (double)count * list_bytes + (double)routed * 4.0);
+    passes(s, list, (u64)count, dim3((unsigned)((count + FILL_THREADS - 1) / FILL_THREADS)), dim3((unsigned)((routed + FILL_THREADS - 1) / FILL_THREADS)), class_of,
+           owner, n, W, NR, routed, flag.d, res);
   }
   u64 r[FILL_R_WORDS];
   Download dl(ctx);
@@ -331,13 +383,44 @@ extern "C" int lcp2_witness_fill_copies(lcp2_circuit *c, const lcp2_cell *cells,
   out.owner_index = r[FILL_R_OWNER_INDEX];
   if (report) *report = out;
   if (flag.words[0] != ROW_NO_PROBLEM)
-    return ctx->fail(LCP2_E_INVALID, "fill copies: cell " + std::to_string(flag.words[0] >> 8) + ": " + fill_cell_problem_str((u32)(flag.words[0] & 0xFF)) +
-                                         " (found on the device: the valid cells are written and their classes filled)");
+    return ctx->fail(LCP2_E_INVALID, who + ": cell " + std::to_string(flag.words[0] >> 8) + ": " + fill_cell_problem_str((u32)(flag.words[0] & 0xFF)) + device_note);
   if (out.conflicts) {
     auto cell = [](u64 packed) { return "(row " + std::to_string(packed & 0xFFFFFFFFull) + ", wire " + std::to_string(packed >> 32) + ")"; };
-    return ctx->fail(LCP2_E_UNSAT, "fill copies: cell " + std::to_string(out.conflict_index) + " " + cell(r[FILL_R_CONFLICT_CELL]) +
+    return ctx->fail(LCP2_E_UNSAT, who + ": cell " + std::to_string(out.conflict_index) + " " + cell(r[FILL_R_CONFLICT_CELL]) +
                                        " differs from cell " + std::to_string(out.owner_index) + " " + cell(r[FILL_R_OWNER_CELL]) +
                                        ", which gave their copy class its value (" + std::to_string(out.conflicts) + " such cells; the class holds the owner's value)");
   }
   return LCP2_OK;
+}
+}  // namespace
+
+extern "C" int lcp2_witness_fill_copies(lcp2_circuit *c, const lcp2_cell *cells, size_t ncells, lcp2_mem cells_mem, uint64_t *wires,
+                                        lcp2_fill_report *report) {
+  static_assert(sizeof(lcp2_cell) == sizeof(CellDev), "ABI structs must match the kernels'");
+  u64 *w = (u64 *)wires;
+  return copies_call(c, "fill copies", (const CellDev *)cells, ncells, cells_mem, wires, report, 40.0,
+                     " (found on the device: the valid cells are written and their classes filled)",
+                     [w](hipStream_t s, const CellDev *list, u64 count, dim3 list_blocks, dim3 cell_blocks, u32 *class_of, u32 *owner, u64 n, u32 W, u32 NR, u64 routed,
+                         u64 *flag, u64 *res) {
+                       hipLaunchKernelGGL(k_fill_owner, list_blocks, dim3(FILL_THREADS), 0, s, list, count, class_of, owner, w, n, W, NR, flag);
+                       hipLaunchKernelGGL(k_fill_broadcast, cell_blocks, dim3(FILL_THREADS), 0, s, list, class_of, owner, w, routed, res);
+                       hipLaunchKernelGGL(k_fill_conflicts, list_blocks, dim3(FILL_THREADS), 0, s, list, count, class_of, owner, n, W, NR, res);
+                       hipLaunchKernelGGL(k_fill_first_conflict, dim3(1), dim3(1), 0, s, list, class_of, owner, n, NR, res);
+                     });
+}
+
+// the order is the point: the matrix is compared before it is written, and written from words that are not (witness_settle.hpp)
+extern "C" int lcp2_witness_settle_copies(lcp2_circuit *c, const lcp2_cell_ref *sources, size_t nsources, lcp2_mem sources_mem, uint64_t *wires,
+                                          lcp2_fill_report *report) {
+  static_assert(sizeof(lcp2_cell_ref) == sizeof(CellRefDev), "ABI structs must match the kernels'");
+  u64 *w = (u64 *)wires;
+  return copies_call(c, "settle copies", (const CellRefDev *)sources, nsources, sources_mem, wires, report, 48.0,
+                     " (found on the device: the classes of the valid cells are filled)",
+                     [w](hipStream_t s, const CellRefDev *list, u64 count, dim3 list_blocks, dim3 cell_blocks, u32 *class_of, u32 *owner, u64 n, u32 W, u32 NR,
+                         u64 routed, u64 *flag, u64 *res) {
+                       hipLaunchKernelGGL(k_settle_owner, list_blocks, dim3(FILL_THREADS), 0, s, list, count, class_of, owner, n, W, NR, flag);
+                       hipLaunchKernelGGL(k_settle_conflicts, list_blocks, dim3(FILL_THREADS), 0, s, list, count, class_of, owner, (const u64 *)w, n, W, NR, res);
+                       hipLaunchKernelGGL(k_settle_first_conflict, dim3(1), dim3(1), 0, s, list, class_of, owner, n, NR, res);
+                       hipLaunchKernelGGL(k_settle_broadcast, cell_blocks, dim3(FILL_THREADS), 0, s, list, class_of, owner, w, n, routed, res);
+                     });
 }

@@ -649,6 +649,43 @@ int lcp2_witness_fill_copies(lcp2_circuit *c, const lcp2_cell *cells, size_t nce
  * 0xFFFFFFFF for a cell in no class.  Either pointer may be null.  Builds the table if the handle has none yet; refusals as above. */
 int lcp2_circuit_copy_classes(lcp2_circuit *c, uint32_t *class_of, uint64_t *num_classes);
 
+/* COPY CLASSES FILLED FROM THE MATRIX (the same step of plonky2, PartitionWitness::get_full_witness, after a witness plan has run on
+ * the device: the values of the partitions exist only in HBM).  A plan job writes the cells of its own operation; a routed cell that
+ * a copy constraint ties to a job's output and that no job writes - a PublicInputGate wire, an input of a row the plan does not
+ * generate - receives the output here.  The list names SOURCE CELLS and carries no value, so it can be recorded once per circuit
+ * (from the builder's copy classes) and kept in HBM: per proof nothing crosses the bus.  The replay is then: rewrite the leaf IMMs,
+ * lcp2_witness_plan_rows_u32, lcp2_witness_settle_copies, lcp2_prove.  The classes are those of lcp2_witness_fill_copies - the one
+ * table of the handle, built at the first use by either call or by lcp2_circuit_copy_classes.
+ *   what the call writes   a source that is a routed cell of a class makes the class OWNED; the owner is the source with the SMALLEST LIST
+ *           INDEX, and the class's value is the word the matrix held at the owner's cell when the call began - raw, not
+ *           canonicalised.  Every OTHER routed cell of the class - listed or not - receives that word; the owner's own cell is not
+ *           stored to.  A class with no source is not touched: no cell of it is read or written.  A source on a non-routed wire, or
+ *           one that is its own sigma image, is valid and does nothing (no read, no write).  The same cell listed twice is legal.
+ *           The matrix is compared before it is written, and written only from owner cells, which are not written: the result does
+ *           not depend on the order the lanes ran in.
+ *   conflicts   a source whose CANONICAL matrix value, at the start of the call, differs from that of its class's owner.  The call then
+ *           returns LCP2_E_UNSAT with the report complete, lcp2_last_error names both list indices and both cells, and every cell of
+ *           the class - the conflicting ones included - holds the owner's word.  Equal canonical but different raw words (v and
+ *           v + p) are no conflict: the owner's raw word is stored.
+ *   the report   lcp2_fill_report, its fields as for lcp2_witness_fill_copies with "listed cell" read as "source": cells_filled counts
+ *           the routed cells of owned classes that were not listed.
+ *   validation   sources_mem = LCP2_MEM_HOST: row < n and col < num_wires are checked before anything is launched, a refused list
+ *           (LCP2_E_INVALID, "cell N: reason") changes nothing, and the list goes up through the context's pinned staging buffer when
+ *           it fits.  LCP2_MEM_DEVICE: the kernel validates; an invalid entry does nothing and takes part in no class, the rest is
+ *           done, and the call returns LCP2_E_INVALID naming the FIRST refused entry.  nsources = 0 is LCP2_OK, touches nothing and
+ *           builds nothing (the report is zero but for the two indices).
+ * wires: device, [num_wires][n] column-major.  report: host, nullable.
+ * LCP2_E_INVALID: null c or wires, a null list with nsources > 0, a sources_mem above 1; sigma columns that are no permutation of the
+ * routed cell ids, as for lcp2_witness_fill_copies.  LCP2_E_NODEVICE: a verifier-only handle.  LCP2_E_UNSUPPORTED: a sharded handle,
+ * num_routed_wires * n >= 2^32 or nsources >= 2^32.
+ * The proving state of the handle is left alone: the call may come between any two other calls, also between the seams of a proof in
+ * flight.  The context's stream is synchronised on return.  Timing (lcp2_prof_*): LCP2_K_OTHER, one scope per call. */
+typedef struct {
+  uint32_t row, col;
+} lcp2_cell_ref; /* 8 bytes */
+int lcp2_witness_settle_copies(lcp2_circuit *c, const lcp2_cell_ref *sources, size_t nsources, lcp2_mem sources_mem,
+                               uint64_t *wires /* device, column-major [num_wires][n] */, lcp2_fill_report *report /* host, nullable */);
+
 /* ---- a HOST witness without its upload on the critical path.  data.prove(pw) of a fork that runs plonky2's own generators ends up with
  * the full witness in host memory (4.5 GB at n = 2^22); lcp2_prove(.., LCP2_MEM_HOST, ..) copies it first and proves afterwards.  For a
  * sequence of proofs (BASELINE configs[4]: a batch of updates) the copy of witness i + 1 runs while proof i is computed:
