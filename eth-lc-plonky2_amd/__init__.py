@@ -13,6 +13,7 @@ from . import circuit  # noqa: F401,E402
 from . import poseidon_py  # noqa: F401,E402
 from . import recursion_gates  # noqa: F401,E402
 from . import u32_gates  # noqa: F401,E402
+from . import sha_plan  # noqa: F401,E402
 from . import batch  # noqa: F401,E402
 from . import parallel  # noqa: F401,E402
 from . import light_client  # noqa: F401,E402

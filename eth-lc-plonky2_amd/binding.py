@@ -127,6 +127,16 @@ class WitnessPlanU32(ctypes.Structure):
     _fields_ = [("base", WitnessPlan), ("u32_jobs", ctypes.c_void_p), ("nu32", ctypes.c_size_t), ("u32_level_ends", ctypes.c_void_p)]
 
 
+SHA_PLAN_JOB_DTYPE = np.dtype([("first_row", "<u4"), ("first_operand", "<u4")])   # lcp2_sha_plan_job: 16 operands, W0..W15
+SHA_PLAN_OPERANDS = 16
+assert SHA_PLAN_JOB_DTYPE.itemsize == 8
+
+
+class WitnessPlanSha(ctypes.Structure):
+    """lcp2_witness_plan_sha: a witness plan that also holds SHA-256 jobs, in the same levels (lcp2_witness_plan_rows_sha)"""
+    _fields_ = [("base", WitnessPlanU32), ("sha_jobs", ctypes.c_void_p), ("nsha", ctypes.c_size_t), ("sha_level_ends", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -218,6 +228,7 @@ def load_library():
                                          c.c_uint32, c.c_uint64]),
         "lcp2_witness_plan_rows": (c.c_int, [c.c_void_p, c.POINTER(WitnessPlan), c.c_int, c.c_void_p, c.c_uint32, c.c_uint64]),
         "lcp2_witness_plan_rows_u32": (c.c_int, [c.c_void_p, c.POINTER(WitnessPlanU32), c.c_int, c.c_void_p, c.c_uint32, c.c_uint64]),
+        "lcp2_witness_plan_rows_sha": (c.c_int, [c.c_void_p, c.POINTER(WitnessPlanSha), c.c_int, c.c_void_p, c.c_uint32, c.c_uint64]),
         "lcp2_commit_wires_rows_begin": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_commit_wires_chunk": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32]),
         "lcp2_commit_wires_rows_finish": (c.c_int, [c.c_void_p, c.c_void_p]),
@@ -625,6 +636,35 @@ class Context:
         base = WitnessPlan(ptrs[1], counts[1], end_ptrs[1], ptrs[2], counts[2], ptrs[3], counts[3], end_ptrs[2], ptrs[4], counts[4], ends[0].size)
         plan = WitnessPlanU32(base, ptrs[0], counts[0], end_ptrs[0])
         self._check(self.lib.lcp2_witness_plan_rows_u32(self.handle, ctypes.byref(plan), mem, ctypes.c_void_p(wires_dev), int(ncols), int(n)))
+
+    def witness_plan_rows_sha(self, sha_jobs, u32_jobs, rec_jobs, pos_jobs, chain_ends, operands, sha_level_ends, u32_level_ends, rec_level_ends,
+                              pos_level_ends, wires_dev, ncols, n, nsha=None, nu32=None, nrec=None, npos=None, nchains=None, noperands=None):
+        """lcp2_witness_plan_rows_sha: witness_plan_rows_u32 for a plan that also holds SHA-256 jobs (310 rows each, columns 0..107),
+        whose 16 message words are operands of the plan (IMM or CELL); digests are read from the matrix (sha_plan.digest_cell).
+        sha_jobs: SHA_PLAN_JOB_DTYPE records, with the other five lists either all numpy arrays (host lists: validated before
+        anything runs) or all device pointers with nsha, nu32, nrec, npos, nchains and noperands.  The four level tables are always
+        on the host and equally long.  sha_plan.pack_sha_plan returns all ten."""
+        ends = [np.ascontiguousarray(e, dtype=np.uint32).ravel() for e in (sha_level_ends, u32_level_ends, rec_level_ends, pos_level_ends)]
+        if len({e.size for e in ends}) != 1:
+            raise Lcp2Error(-1, "sha_level_ends, u32_level_ends, rec_level_ends and pos_level_ends must have one entry per level each")
+        lists = (sha_jobs, u32_jobs, rec_jobs, pos_jobs, chain_ends, operands)
+        on_host = [isinstance(a, np.ndarray) for a in lists]
+        if any(on_host) != all(on_host):
+            raise Lcp2Error(-1, "the six lists must all be host arrays or all be device pointers")
+        if all(on_host):
+            if [a.dtype for a in lists] != [SHA_PLAN_JOB_DTYPE, U32_PLAN_JOB_DTYPE, REC_JOB_DTYPE, POS_JOB_DTYPE, np.dtype(np.uint32), REC_OPERAND_DTYPE]:
+                raise Lcp2Error(-1, "the lists must be arrays of SHA_PLAN_JOB_DTYPE / U32_PLAN_JOB_DTYPE / REC_JOB_DTYPE / POS_JOB_DTYPE / uint32 / "
+                                    "REC_OPERAND_DTYPE records")
+            keep = [np.ascontiguousarray(a).ravel() for a in lists]
+            counts, ptrs, mem = [a.size for a in keep], [a.ctypes.data if a.size else None for a in keep], MEM_HOST
+        else:
+            if None in (nsha, nu32, nrec, npos, nchains, noperands):
+                raise Lcp2Error(-1, "device lists need nsha, nu32, nrec, npos, nchains and noperands")
+            counts, ptrs, mem = [int(nsha), int(nu32), int(nrec), int(npos), int(nchains), int(noperands)], [a or None for a in lists], MEM_DEVICE
+        end_ptrs = [e.ctypes.data if e.size else None for e in ends]
+        base = WitnessPlan(ptrs[2], counts[2], end_ptrs[2], ptrs[3], counts[3], ptrs[4], counts[4], end_ptrs[3], ptrs[5], counts[5], ends[0].size)
+        plan = WitnessPlanSha(WitnessPlanU32(base, ptrs[1], counts[1], end_ptrs[1]), ptrs[0], counts[0], end_ptrs[0])
+        self._check(self.lib.lcp2_witness_plan_rows_sha(self.handle, ctypes.byref(plan), mem, ctypes.c_void_p(wires_dev), int(ncols), int(n)))
 
     def verify_batch(self, circuit_data, proofs, public_inputs, mem=MEM_HOST, count=None, head="host"):
         """lcp2_verify_batch: data.verify for a batch of proofs of one circuit (any CircuitData, verifier-only ones included), Merkle

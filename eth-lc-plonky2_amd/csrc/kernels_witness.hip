@@ -8,7 +8,9 @@
 //                     record (message, schedule, per-round (a, e), chaining values)
 //   k_sha_fill_rows   one lane per circuit ROW (310 per hash): expands the record into that row's cells (words, bit
 //                     decompositions, carries) with column-major stores, so lanes of a wave write runs of a column
-// plus k_scatter_cells for the handful of non-SHA cells (constants, arithmetic glue, public inputs).
+// plus k_scatter_cells for the handful of non-SHA cells (constants, arithmetic glue, public inputs), and, for a hash that is a job of
+// a recorded witness plan, k_sha_plan_jobs: both steps fused, one wave per hash, the record in LDS (further down, with the other
+// kernels of a plan's levels).
 #include "internal.hpp"
 #include "sha_layout.hpp"
 #include "sha_rows.hpp"
@@ -18,6 +20,7 @@
 #include "rec_rows.hpp"
 #include "pos_plan.hpp"
 #include "u32_plan.hpp"
+#include "sha_plan.hpp"
 
 namespace lcp2 {
 
@@ -225,6 +228,68 @@ void launch_u32_plan_rows(hipStream_t s, const U32PlanJobDev *jobs, u64 base, u6
   if (begin >= end) return;
   hipLaunchKernelGGL(k_u32_plan_rows, dim3((unsigned)((end - begin + U32_PLAN_THREADS - 1) / U32_PLAN_THREADS)), dim3(U32_PLAN_THREADS), 0, s,
                      jobs, base, begin, end, operands, noperands, wires, ncols, n, flags, gate, marker);
+}
+
+// One 64-LANE WAVE per SHA-256 job of one LEVEL of lcp2_witness_plan_rows_sha, record and rows fused (sha_plan.hpp
+// sha_plan_job_lane is the one-lane reference of this kernel and writes the same cells; tests/emu/emu_plan_sha.cpp runs it on the
+// CPU).  The pair k_sha_jobs_level / k_sha_fill_rows would need a second launch per level, 1 344 bytes of record scratch per job and
+// a per-job "valid" word; here the record lives in LDS for the life of the block and digests travel between levels only through the
+// matrix.  A block is one wave, so the barriers below are the wave's own and a refused wave leaves nobody waiting.
+//   load and check  every lane reads the 8-byte job (one address) and tests it; lane k < 16 reads operand record k (16 neighbouring
+//                   records, 256 bytes), checks it before any index of it is used, loads its cell if it is a CELL, canonicalises
+//                   and applies the value check.  The verdict is a minimum over the wave in the order of the reference - structure
+//                   by operand index, then values by operand index - and is the same in every lane: a refused wave leaves together,
+//                   after lane 0 has folded the job into flags[3] and the family marker into flags[0] (row_flag.hpp).
+//   compress        the 16 words go into the record in LDS, lane 0 runs both compressions into it (sha_rows.hpp sha_words_record:
+//                   336 words, the text of k_sha_jobs_level); the other lanes wait at the barrier.
+//   fill            lane t writes rows t, t + 64, .. below 310 through sha_row_cells, as k_sha_fill_rows does from HBM: a store of
+//                   the wave covers 64 consecutive rows of one column, 512 contiguous bytes.
+// All 16 operands are loaded before the first store, so a CELL inside the job's own rows yields the word from before the call.
+constexpr u32 SHA_PLAN_THREADS = 64;
+__global__ __launch_bounds__(SHA_PLAN_THREADS) void k_sha_plan_jobs(const ShaPlanJobDev *__restrict__ jobs, u64 base, u64 begin, u64 end,
+                                                                     const RecOperandDev *__restrict__ operands, u64 noperands, u64 *wires,
+                                                                     u32 ncols, u64 n, u64 *flags, u64 gate, u64 marker) {
+  __shared__ uint32_t rec[SHA_REC_WORDS];
+  const u64 i = begin + blockIdx.x;
+  const u32 lane = threadIdx.x;
+  if (i >= end) return;
+  if ((flags[0] >> 8) < gate) return;  // a job of an earlier level was refused: this level writes nothing
+  const ShaPlanJobDev job = jobs[i - base];
+  u32 problem = sha_plan_job_problem(job, noperands, n);  // the same in every lane
+  u32 verdict = problem ? problem : 0xFFFFu;
+  u64 v = 0;
+  if (!problem && lane < SHA_PLAN_OPERANDS) {
+    const RecOperandDev o = operands[(u64)job.first_operand + lane];
+    problem = sha_plan_operand_problem(o, ncols, n);
+    if (problem) verdict = lane << 8 | problem;
+    else {
+      v = gl_canon(o.src == PLAN_CELL ? wires[(u64)o.col * n + o.v] : o.v);
+      if ((problem = sha_plan_value_problem(v)) != 0) verdict = (SHA_PLAN_OPERANDS + lane) << 8 | problem;
+    }
+  }
+#pragma unroll
+  for (u32 m = 1; m < 64; m <<= 1) verdict = min(verdict, (u32)__shfl_xor((int)verdict, (int)m, 64));
+  if (verdict != 0xFFFFu) {
+    if (lane == 0) {
+      atomicMin((unsigned long long *)flags + 3, (unsigned long long)row_refusal(i, verdict & 0xFF));
+      atomicMin((unsigned long long *)flags, (unsigned long long)row_refusal(marker, ROW_SHA_FAMILY));
+    }
+    return;
+  }
+  if (lane < SHA_PLAN_OPERANDS) rec[SHA_REC_IN + lane] = (uint32_t)v;
+  __syncthreads();
+  if (lane == 0) sha_words_record(rec + SHA_REC_IN, rec);
+  __syncthreads();
+  for (u32 lr = lane; lr < SHA_ROWS; lr += SHA_PLAN_THREADS) {
+    u64 *W = wires + job.first_row + lr;
+    sha_row_cells(rec, lr, [&](u32 col, u64 x) { W[(u64)col * n] = x; });
+  }
+}
+void launch_sha_plan_jobs(hipStream_t s, const ShaPlanJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
+                          u64 *wires, u32 ncols, u64 n, u64 *flags, u64 gate, u64 marker) {
+  if (begin >= end) return;
+  hipLaunchKernelGGL(k_sha_plan_jobs, dim3((unsigned)(end - begin)), dim3(SHA_PLAN_THREADS), 0, s, jobs, base, begin, end, operands, noperands,
+                     wires, ncols, n, flags, gate, marker);
 }
 
 void launch_sha_jobs_level(hipStream_t s, const ShaJobDev *jobs, u32 first, u32 count, const uint32_t *words_in, uint32_t *rec) {

@@ -182,6 +182,12 @@ void launch_pos_plan_chains(hipStream_t s, const PosJobDev *jobs, u64 npos, cons
 struct U32PlanJobDev;
 void launch_u32_plan_rows(hipStream_t s, const U32PlanJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
                           u64 *wires, u32 ncols, u64 n, u64 *flags, u64 gate, u64 marker);
+// lcp2_witness_plan_rows_sha (kernels_witness.hip k_sha_plan_jobs, sha_plan.hpp): the SHA-256 jobs [begin, end) of one level, one
+// 64-lane wave each, with the shifted indices of launch_rec_gate_rows (jobs[0] is job `base`); operands: the WHOLE list; flags: the
+// four words of row_flag.hpp, gate the key of this level and marker the index a refused job folds into flags[0]
+struct ShaPlanJobDev;
+void launch_sha_plan_jobs(hipStream_t s, const ShaPlanJobDev *jobs, u64 base, u64 begin, u64 end, const RecOperandDev *operands, u64 noperands,
+                          u64 *wires, u32 ncols, u64 n, u64 *flags, u64 gate, u64 marker);
 // *flag = 1 if a word of p[r * pitch + i] (r < rows, i < width) is a non-zero field element (flag zeroed by the caller)
 void launch_any_nonzero(hipStream_t s, const u64 *p, u64 pitch, u64 width, u32 rows, unsigned long long *flag);
 

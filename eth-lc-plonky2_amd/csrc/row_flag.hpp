@@ -1,7 +1,7 @@
 // The refusal flag of the row generators that validate a job list on the device (lcp2_u32_gate_rows, lcp2_rec_gate_rows,
-// lcp2_witness_plan_rows, lcp2_witness_plan_rows_u32).
+// lcp2_witness_plan_rows, lcp2_witness_plan_rows_u32, lcp2_witness_plan_rows_sha).
 //
-// One 64-bit word per call, two for a plan, three for a plan with u32 jobs.  The entry point sets it to ROW_NO_PROBLEM before the
+// One 64-bit word per call, two for a plan, three for a plan with u32 jobs, four for one with SHA jobs.  The entry point sets it to ROW_NO_PROBLEM before the
 // first launch; a lane whose job is
 // refused writes no cell and folds row_refusal(index, problem) into the word with a minimum (the kernels: atomicMin; tests/emu: a
 // compare), so after the last launch the word names the FIRST refused job of the list and why (u32_problem_str / rec_problem_str),
@@ -61,6 +61,24 @@ inline PlanRefusal plan_refusal_u32(const u64 *words, const uint32_t *rec_level_
   for (size_t l = 0; l < nlevels; l++)
     if (shifted >= plan_gate(l ? u32_level_ends[l - 1] : 0, l) && shifted < u32_level_ends[l] + plan_shift(l)) return {2, problem, shifted - plan_shift(l)};
   return {2, problem, 0};
+}
+
+// A plan with SHA-256 jobs (lcp2_witness_plan_rows_sha) runs a FOURTH family after the rec jobs: per level the rec jobs, the SHA
+// jobs (k_sha_plan_jobs), the u32 jobs, the chains.  A refused SHA job of level l folds row_refusal(end_l + l + 1, ROW_SHA_FAMILY)
+// into flags[0] - the key of a refused u32 job or chain, one below the u32 marker in the problem byte, so the minimum orders the
+// four families rec / SHA / u32 / PoseidonGate and every word above keeps its meaning - and its own
+//   flags[3]  the minimum of row_refusal(SHA job + plan_shift(l), problem) over the refused SHA jobs, shifted per level like
+//             flags[2]; read when flags[0] carries ROW_SHA_FAMILY.
+// family 3: a SHA job (sha_plan_problem_str).  A call without SHA jobs keeps two or three words and the decodes above.
+constexpr u64 ROW_SHA_FAMILY = 0xFD;
+inline PlanRefusal plan_refusal_sha(const u64 *words, const uint32_t *rec_level_ends, const uint32_t *u32_level_ends, const uint32_t *sha_level_ends,
+                                    size_t nlevels) {
+  if (words[0] == ROW_NO_PROBLEM || (words[0] & 0xFF) != ROW_SHA_FAMILY) return plan_refusal_u32(words, rec_level_ends, u32_level_ends, nlevels);
+  const u32 problem = (u32)(words[3] & 0xFF);
+  const u64 shifted = words[3] >> 8;
+  for (size_t l = 0; l < nlevels; l++)
+    if (shifted >= plan_gate(l ? sha_level_ends[l - 1] : 0, l) && shifted < sha_level_ends[l] + plan_shift(l)) return {3, problem, shifted - plan_shift(l)};
+  return {3, problem, 0};
 }
 
 }  // namespace lcp2

@@ -42,13 +42,13 @@ struct Stage {
   }
 };
 
-// The refusal flag of a call whose kernels validate jobs (row_flag.hpp), in scratch slot 1: one word, the two of a plan, or the three of a plan
-// with u32 jobs
+// The refusal flag of a call whose kernels validate jobs (row_flag.hpp), in scratch slot 1: one word, the two of a plan, the three of a plan
+// with u32 jobs, or the four of a plan with SHA jobs
 struct RefusalFlag {
   lcp2_ctx *ctx;
   size_t nwords = 1;
   u64 *d = nullptr;
-  u64 words[3] = {0, 0, 0};
+  u64 words[4] = {0, 0, 0, 0};
   int begin() {
     LCP2_TRY(scratch_ensure(ctx, 1, nwords * sizeof(u64), (void **)&d));
     LCP2_HIP(ctx, hipMemsetAsync(d, 0xFF, nwords * sizeof(u64), ctx->stream));  // ROW_NO_PROBLEM

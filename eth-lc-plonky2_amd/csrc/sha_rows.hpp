@@ -1,8 +1,8 @@
 // One two_to_one_sha256, from its 16 message words to every cell of its 310 rows (lcp2_sha256_witness), and one scattered cell
 // (lcp2_scatter_cells).
 //
-// The lanes of the two SHA-256 witness kernels as functions: sha_job_record is the lane of k_sha_jobs_level (message gather, both
-// compressions, the 336-word record of sha_layout.hpp), sha_row_cells the lane of k_sha_fill_rows (one circuit row of the record
+// The lanes of the two SHA-256 witness kernels as functions: sha_job_record is the lane of k_sha_jobs_level (message gather, then
+// sha_words_record: both compressions, the 336-word record of sha_layout.hpp; k_sha_plan_jobs and sha_plan.hpp share the latter), sha_row_cells the lane of k_sha_fill_rows (one circuit row of the record
 // as (column, value) pairs through a store callback), sha_jobs_problem the validation lcp2_sha256_witness (witness_rows.hip) runs
 // on the host before anything is launched.  kernels_witness.hip calls the lanes with stores into the column-major witness
 // matrix; tests/emu/emu_sha.cpp compiles the same text for the CPU and runs the grids as loops.  The row layout is the one of
@@ -82,17 +82,15 @@ inline ShaProblem sha_jobs_problem(const ShaJobDev *jobs, size_t njobs, const ui
 }
 
 // ------------------------------------------------------------------ the lane of k_sha_jobs_level
-// Job j of a level: gathers its 16 message words (words_in, or digests in the records of jobs of earlier levels), runs the
-// compression of the data block and of the constant padding block, and writes record j of `rec`.
-LCP2_SHA_LANE void sha_job_record(const ShaJobDev &job, u32 j, const uint32_t *words_in, uint32_t *rec) {
-  uint32_t *R = rec + (u64)j * SHA_REC_WORDS;
+// From 16 message words to the whole record R (SHA_REC_WORDS words): the compression of the data block and of the constant padding
+// block.  msg may be R + SHA_REC_IN itself (k_sha_plan_jobs gathers the words into the record first): every word is read before
+// the first store.
+LCP2_SHA_LANE void sha_words_record(const uint32_t *msg, uint32_t *R) {
   uint32_t w[16];
 #pragma unroll
-  for (int i = 0; i < 16; i++) {
-    int s = job.in_src[i];
-    w[i] = s >= 0 ? words_in[s] : rec[(u64)((~s) >> 3) * SHA_REC_WORDS + SHA_REC_DIGEST + ((~s) & 7)];
-    R[SHA_REC_IN + i] = w[i];
-  }
+  for (int i = 0; i < 16; i++) w[i] = msg[i];
+#pragma unroll
+  for (int i = 0; i < 16; i++) R[SHA_REC_IN + i] = w[i];
   uint32_t chain[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) chain[i] = WSHA_IV[i];
@@ -130,6 +128,17 @@ LCP2_SHA_LANE void sha_job_record(const ShaJobDev &job, u32 j, const uint32_t *w
 #pragma unroll
     for (int i = 0; i < 8; i++) O[i] = chain[i];
   }
+}
+// Job j of a level: gathers its 16 message words (words_in, or digests in the records of jobs of earlier levels) and writes
+// record j of `rec` from them (sha_words_record).
+LCP2_SHA_LANE void sha_job_record(const ShaJobDev &job, u32 j, const uint32_t *words_in, uint32_t *rec) {
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    int s = job.in_src[i];
+    w[i] = s >= 0 ? words_in[s] : rec[(u64)((~s) >> 3) * SHA_REC_WORDS + SHA_REC_DIGEST + ((~s) & 7)];
+  }
+  sha_words_record(w, rec + (u64)j * SHA_REC_WORDS);
 }
 
 // state word helpers on a record: a_t / e_t = register a / e AFTER round t of compression c; negative t = chaining input

@@ -386,6 +386,43 @@ typedef struct {
 int lcp2_witness_plan_rows_u32(lcp2_ctx *ctx, const lcp2_witness_plan_u32 *plan, lcp2_mem lists_mem,
                                uint64_t *wires /* device, column-major [ncols >= 135][n] */, uint32_t ncols, uint64_t n);
 
+/* A witness plan that also holds this repository's SHA-256 rows: the jobs of lcp2_sha256_witness with their 16 message words as
+ * OPERANDS of the plan's one operand list, as the fourth family of a plan.  One replay then fills a circuit that mixes SHA rows,
+ * u32 / BigUint rows, recursion rows and PoseidonGate chains; a message word may be any cell (a u32 result, a BaseSum limb, a public
+ * input) and a digest may feed a u32 / comparison / rec job or a chain of a later level, with no trip to the host.  `base` is the
+ * plan of lcp2_witness_plan_rows_u32, unchanged.
+ * A SHA job takes 16 operands from operands[first_operand] on: W0..W15.  An operand is LCP2_PLAN_IMM or LCP2_PLAN_CELL
+ * (LCP2_PLAN_PREV is refused as "operand src above 1"), is canonicalised when read, and its canonical value must be below 2^32.
+ * The job writes columns 0..107 of the rows first_row .. first_row + 309, ALL of them, with exactly the values lcp2_sha256_witness
+ * writes for the same 16 message words (csrc/sha_layout.hpp), and no other cell; n need not be a power of two.  Chaining goes
+ * through the matrix: DIGEST word i (0..7) of a job is the cell (row first_row + 307 + i / 3, column 3 (i % 3) + 2), and MESSAGE
+ * word W_t (0..15) is the cell (row first_row + 48 + 2 t, column 5); eth_lc_plonky2_amd.sha_plan has both as digest_cell /
+ * message_cell.  The call returns no digests: read the cells.
+ * Levels: level l holds the SHA jobs [sha_level_ends[l-1], sha_level_ends[l]) beside the level's rec jobs, u32 jobs and chains; the
+ * launches of a level go to the context's stream in the order rec, SHA, u32, chains, one 64-lane wave per SHA job, with no host
+ * wait between levels.  A job may read any cell the matrix held before the call or that an EARLIER level of any family writes;
+ * reading what the same level writes is the caller's error and is not detected.  One case is defined: a SHA job reads all 16
+ * operands before its first store, so a CELL inside the job's own rows yields the word from before the call.
+ * LCP2_MEM_HOST: the lists are validated completely - rec jobs, then SHA jobs, then u32 jobs, then PoseidonGate jobs; structure, and
+ * the values that are IMM - before anything is written, and go up through the pinned staging buffer; the SHA jobs go into scratch
+ * slot 3 of the context after the u32 plan jobs, at an offset rounded to 16 bytes.  LCP2_MEM_DEVICE: the kernels validate, and no
+ * index is used before it is checked.  CELL values are only seen in the kernel: the refused job writes nothing, the valid jobs of
+ * its level and of earlier levels are written, every later level writes nothing in all four families, and the call returns
+ * LCP2_E_INVALID naming the first refused job: "plan rows: sha job N: <reason>".  If several families refuse in one level the rec
+ * job is named first, then the SHA job, then the u32 job, then the PoseidonGate job.
+ * Refused SHA jobs: first_row + 310 > n, first_operand + 16 > noperands, an operand src above 1, a CELL with col >= ncols or
+ * v >= n; by VALUE an operand of 2^32 or more.  The argument checks are those of lcp2_witness_plan_rows_u32, with sha_jobs /
+ * sha_level_ends among the lists; ncols >= 135 as there.  All counts zero is LCP2_OK; with nsha = 0 the call IS
+ * lcp2_witness_plan_rows_u32(&plan->base, ...).  The context's stream is synchronised on return. */
+typedef struct { uint32_t first_row, first_operand; } lcp2_sha_plan_job;   /* 8 bytes; 16 operands: W0..W15 */
+typedef struct {
+  lcp2_witness_plan_u32 base;                       /* rec jobs, u32 jobs, PoseidonGate chains, the ONE operand list, nlevels: as above */
+  const lcp2_sha_plan_job *sha_jobs; size_t nsha;   /* with the lists (lists_mem) */
+  const uint32_t *sha_level_ends;                   /* host, [nlevels], ascending, last == nsha */
+} lcp2_witness_plan_sha;
+int lcp2_witness_plan_rows_sha(lcp2_ctx *ctx, const lcp2_witness_plan_sha *plan, lcp2_mem lists_mem,
+                               uint64_t *wires /* device, column-major [ncols >= 135][n] */, uint32_t ncols, uint64_t n);
+
 /* device buffers for callers that keep the witness resident in HBM */
 int lcp2_buffer_alloc(lcp2_ctx *ctx, size_t bytes, void **dev);
 int lcp2_buffer_free(lcp2_ctx *ctx, void *dev);
