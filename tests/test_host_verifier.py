@@ -201,6 +201,7 @@ def _variant(m, base_bits, **kw):
     dict(cap_height=9),                  # above the LDE tree of a 2^5-row circuit: sibling counts would underflow
     dict(quotient_degree_factor=0),
     dict(proof_of_work_bits=0),          # a shift by 64
+    dict(proof_of_work_bits=41),         # above what fri_proof_of_work scans for
     dict(degree_bits=40),
     dict(num_query_rounds=65),
     dict(num_challenges=3),
@@ -223,6 +224,19 @@ def test_verifier_create_checks_the_parameters(oracle, kw):
         assert e.value.status in (-1, -6)
     finally:
         circ.params = good
+
+
+@pytest.mark.parametrize("bits", [1, 40])
+def test_verifier_create_accepts_the_bounds_of_proof_of_work_bits(oracle, bits):
+    """1 and 40 bits are the ends of the accepted range (0 and 41: the list above); at 1 bit the handle verifies an oracle proof"""
+    import eth_lc_plonky2_amd as m
+    circ, wires, pis = m.circuit.synthetic_circuit(_variant(m, 5, proof_of_work_bits=bits), seed=3)
+    oc = oracle_lib.OracleCircuit(oracle, circ)
+    vd = m.CircuitData.verifier_only(circ, *oc.digest())
+    if bits == 1:
+        vd.verify(oc.prove(wires, pis), pis)
+    vd.close()
+    oc.close()
 
 
 @pytest.mark.parametrize("arities", [[31], [4, 4, 4], [5, 5], [0], [4, 4]])
