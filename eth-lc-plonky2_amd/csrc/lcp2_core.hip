@@ -358,7 +358,7 @@ extern "C" int lcp2_ntt_batch(lcp2_ctx *ctx, uint64_t *data, size_t ncols, uint3
   DeviceNttBackend be{ctx};
   NttHost<DeviceNttBackend> ntt(be);
   if (log_n == 0) {
-    // size-1 transform: identity
+    launch_canon_copy(ctx->stream, s.d, s.d, ncols, nullptr);  // size-1 transform: the identity on the field element, canonical like every other size
   } else if (!inverse) {
     ProfScope ps(ctx, LCP2_K_LDE, 16.0 * n * ncols);
     ntt.forward(s.d, n, tmp.u(), n, log_n, (u32)ncols, shift, 0);
@@ -392,6 +392,7 @@ extern "C" int lcp2_lde_batch(lcp2_ctx *ctx, const uint64_t *coeffs, uint64_t *o
   if (log_n == 0) {
     for (size_t c = 0; c < ncols; c++)  // constant polynomial: every evaluation equals the coefficient
       for (u64 i = 0; i < N; i++) LCP2_HIP(ctx, hipMemcpyAsync(so.d + c * N + i, si.d + c, sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+    launch_canon_copy(ctx->stream, so.d, so.d, ncols * N, nullptr);  // canonical words, like every other size
   } else {
     ProfScope ps(ctx, LCP2_K_LDE, (double)ncols * (8.0 * n + 8.0 * N));
     ntt.forward(si.d, n, so.d, N, log_n, (u32)ncols, GL_GENERATOR, rate_bits);

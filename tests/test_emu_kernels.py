@@ -150,6 +150,45 @@ def test_emu_lde_light_client_step_shape(oracle, emu, computed_scale):
         assert (lde[c:c + 1] == lde_leaf_order(oracle, x[c:c + 1] % np.uint64(P))).all()
 
 
+@pytest.mark.parametrize("lg,ncols", [(3, 3), (13, 2), (14, 3), (16, 2)])
+@pytest.mark.parametrize("rate", [1, 2, 4, 5])
+def test_emu_lde_over_rates(oracle, emu, lg, ncols, rate):
+    """the LDE at coset counts other than 8 (tests/test_lde_rates.py runs these on the GPU): the [z] rows of the two-level (lg 3, 13)
+    and one-level (lg 14, 16) coset-scale tables and the block bitrev(z) a coset is stored to, in the plain kernel's phases"""
+    rng = np.random.default_rng(lg * 100 + rate)
+    n = 1 << lg
+    x = rand_field(rng, (ncols, n), canonical=False)
+    lde = np.zeros((ncols, n << rate), dtype=np.uint64)
+    assert emu.emu_ntt_forward(vp(x), vp(lde), lg, ncols, 7, rate) == 0
+    assert (lde == lde_leaf_order(oracle, x % np.uint64(P), rate)).all()
+
+
+def test_emu_lde_strided_walk_reads_its_coset_row(oracle, emu):
+    """from 2^17 on (S <= 9) the threads tile the runs of a slab evenly and the plain kernel's load walks the one-level coset-scale
+    table by constant strides from sc.lo + z * stride (NttPass::load, strided_walk); below that it goes through scale_at.  No
+    other emulation test reads that row base with more than one coset outside the prefetching form."""
+    lg, n, ncols, rate = 17, 1 << 17, 2, 2
+    rng = np.random.default_rng(1702)
+    x = rand_field(rng, (ncols, n), canonical=False)
+    lde = np.zeros((ncols, n << rate), dtype=np.uint64)
+    assert emu.emu_ntt_forward(vp(x), vp(lde), lg, ncols, 7, rate) == 0
+    assert (lde == lde_leaf_order(oracle, x % np.uint64(P), rate)).all()
+
+
+@pytest.mark.parametrize("computed_scale", [False, True])
+def test_emu_lde_light_client_step_shape_at_rate_4(oracle, emu, computed_scale):
+    """the prefetching kernel's phases with 16 cosets instead of 8: the [z][2^lg] rows of the one-level table (FMODE 1) and the
+    [z][16] rows of the computed scale (FMODE 2).  4 columns are the fewest for which both passes take it at 2^19 and rate 4: the
+    strided pass has 64 * ncols * 16 slabs and needs 4096 (ntt.hpp ntt_pf_slabs_per_wg).  As many words as the rate-3 test above."""
+    lg, n, ncols, rate = 19, 1 << 19, 4, 4
+    rng = np.random.default_rng(1940 + computed_scale)
+    x = rand_field(rng, (ncols, n), canonical=False)
+    lde = np.zeros((ncols, n << rate), dtype=np.uint64)
+    assert emu.emu_ntt_forward(vp(x), vp(lde), lg, ncols, 7, rate | (0x100 if computed_scale else 0)) == 2  # both passes
+    cols = [0, 3]
+    assert (lde[cols] == lde_leaf_order(oracle, x[cols] % np.uint64(P), rate)).all()
+
+
 def test_emu_plain_and_coset_forward_light_client_step_shape(oracle, emu):
     # the same strided shape without a factor (FMODE 0) and with the table factor of a single coset (FMODE 1 / 2)
     lg, n = 19, 1 << 19
