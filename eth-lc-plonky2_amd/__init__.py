@@ -11,6 +11,7 @@ from .build import build_native, build_host  # noqa: F401
 from . import binding  # noqa: F401,E402
 from . import circuit  # noqa: F401,E402
 from . import poseidon_py  # noqa: F401,E402
+from . import proof_compress  # noqa: F401,E402
 from . import recursion_gates  # noqa: F401,E402
 from . import u32_gates  # noqa: F401,E402
 from . import sha_plan  # noqa: F401,E402

@@ -288,6 +288,11 @@ def load_library():
         "lcp2_verify_batch": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_size_t, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p]),
         "lcp2_verify_batch_ex": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_size_t, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p,
                                            c.c_uint32]),
+        "lcp2_proof_compressed_words_max": (c.c_size_t, [c.POINTER(Params)]),
+        "lcp2_proof_compress": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "lcp2_proof_decompress": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]),
+        "lcp2_verify_batch_compressed": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p,
+                                                   c.c_uint32]),
         "lcp2_last_challenges": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_gate_program_degree": (c.c_int, [c.c_void_p, c.c_size_t, c.c_uint32, c.POINTER(c.c_uint32)]),
         "lcp2_circuit_gate_tiers": (c.c_int, [c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p]),
@@ -1168,6 +1173,62 @@ class CircuitData:
         if rc == -7:
             raise ProofRejected(failed.value)
         self._check(rc)
+
+    def compress(self, proof, public_inputs):
+        """lcp2_proof_compress: the compressed proof (pruned Merkle multiproofs, see include/lcp2.h; parity unpinned).  Host only.
+        Lcp2Error with status -7 for a proof that could not be given back word for word."""
+        pr, pis = _np_u64(proof).ravel(), _np_u64(public_inputs).ravel()
+        out, words = np.zeros(self.lib.lcp2_proof_compressed_words_max(ctypes.byref(self.circ.params)), dtype=np.uint64), ctypes.c_size_t(0)
+        rc = self.lib.lcp2_proof_compress(self.handle, _ptr(pr), pr.size, _ptr(pis), pis.size, _ptr(out), out.size, ctypes.byref(words))
+        if rc:
+            raise Lcp2Error(rc, self.lib.lcp2_status_str(rc).decode())
+        return out[:words.value].copy()
+
+    def decompress(self, comp, public_inputs):
+        """lcp2_proof_decompress: the full proof of a compressed one; Lcp2Error with status -1 for a word count that is not the one
+        its query indices imply.  Host only."""
+        cp, pis = _np_u64(comp).ravel(), _np_u64(public_inputs).ravel()
+        out = np.zeros(self.proof_words, dtype=np.uint64)
+        rc = self.lib.lcp2_proof_decompress(self.handle, _ptr(cp), cp.size, _ptr(pis), pis.size, _ptr(out), out.size)
+        if rc:
+            raise Lcp2Error(rc, self.lib.lcp2_status_str(rc).decode())
+        return out
+
+    def verify_batch_compressed(self, comps, public_inputs, head="host", ctx=None, offsets=None, mem=MEM_HOST):
+        """lcp2_verify_batch_compressed on `ctx` (default: the handle's own context): comps is a list of compressed proofs, or with
+        `offsets` (count + 1 word offsets) one array of them back to back - with mem=MEM_DEVICE a device pointer.  public_inputs:
+        (count, num_public_inputs).  Returns the int32 array of failed checks, as Context.verify_batch does."""
+        ctx = ctx or self.ctx
+        if ctx is None:
+            raise Lcp2Error(-1, "a verifier-only handle has no context: pass ctx")
+        if head not in VERIFY_HEADS:
+            raise Lcp2Error(-1, "head is 'host' or 'device'")
+        if offsets is None:
+            parts = [_np_u64(p).ravel() for p in comps]
+            offsets = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
+            comps = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+        off = _np_u64(offsets).ravel()
+        count = off.size - 1
+        if count <= 0:
+            return np.zeros(0, dtype=np.int32)
+        if mem == MEM_HOST:
+            keep = _np_u64(comps).ravel()
+            if keep.size < int(off[-1]):
+                raise Lcp2Error(-1, "offsets reach past comps")
+            if not keep.size:
+                keep = np.zeros(1, dtype=np.uint64)  # (empty proofs are still proofs: check 1)
+            ptr = _ptr(keep)
+        else:
+            ptr = ctypes.c_void_p(comps)
+        pis = _np_u64(public_inputs).ravel()
+        npi = pis.size // count
+        if npi * count != pis.size:
+            raise Lcp2Error(-1, "public_inputs is not count rows")
+        checks = np.zeros(count, dtype=np.int32)
+        rc = self.lib.lcp2_verify_batch_compressed(ctx.handle, self.handle, ptr, _ptr(off), count, mem, _ptr(pis), npi, _ptr(checks), VERIFY_HEADS[head])
+        if rc != -7:
+            ctx._check(rc)
+        return checks
 
     def verifier_data_bytes(self):
         """VerifierOnlyCircuitData::to_bytes: constants_sigmas_cap then circuit_digest"""

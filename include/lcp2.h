@@ -894,6 +894,42 @@ int lcp2_verify_batch(lcp2_ctx *ctx, const lcp2_circuit *c, const uint64_t *proo
 int lcp2_verify_batch_ex(lcp2_ctx *ctx, const lcp2_circuit *c, const uint64_t *proofs, size_t proof_words, size_t count, lcp2_mem proofs_mem,
                          const uint64_t *public_inputs, size_t num_public_inputs, int32_t *failed_checks, uint32_t flags);
 
+/* ---- compressed proofs: pruned Merkle multiproofs (plonky2's proof.compress() / decompress() / verify_compressed(); [RECALL] of the
+ * idea, the reference holds no compressed proof and plonky2's sources are not vendored - so this layout is PARITY UNPINNED, and it
+ * differs from plonky2's on purpose in one place: the evaluation at the queried position of every FRI step is KEPT, so that
+ * decompression needs no folding arithmetic).  With L = lcp2_proof_layout_of(p), R = num_query_rounds, x_q the query indices the
+ * verifier derives from the transcript, trees t = 0..3 the initial oracles and 4 + l FRI layer l, the leaf index of query q being x_q
+ * in an initial tree and x_q >> (a_0 + .. + a_l) in layer l, a compressed proof is, in words:
+ *   1. the words [0, L.queries) of the proof;  2. its final_poly words and the pow_witness;
+ *   3. for t = 0, 1, ... and inside a tree for q = 0 .. R - 1: the leaf of (t, q) iff no q' < q has the same leaf index; then for
+ *      level l = 0 .. d_t - 1 with y = idx >> l the sibling digest iff no q' < q has idx' >> l == y and no q' at all has
+ *      idx' >> l == y ^ 1.
+ * No length fields: the word count is a function of the parameters and the indices.  Host only, no device work:
+ * lcp2_proof_compressed_words_max: the most a compressed proof takes (0 for parameters the library refuses).
+ * lcp2_proof_compress: LCP2_OK with *out_words words in out; LCP2_E_INVALID for a wrong length or out_cap < *out_words (*out_words is
+ *   set, out untouched); LCP2_E_VERIFY, nothing written, for a proof it could not give back: one whose proof of work fails (there are
+ *   no indices then), or in which a dropped leaf or sibling differs from its first occurrence or from the digest recomputed from the
+ *   other paths.  Whenever it returns LCP2_OK, lcp2_proof_decompress of the result is the proof word for word.
+ * lcp2_proof_decompress: LCP2_E_INVALID, proof untouched, for a word count that is not the one the indices imply (nothing is read past
+ *   comp_words).  A compressed proof whose proof of work fails has no indices: its query section is zeroed and lcp2_verify names check 2. */
+#define LCP2_COMPRESSED_SCRATCH_BYTES ((size_t)64 << 20)
+size_t lcp2_proof_compressed_words_max(const lcp2_params *p);
+int lcp2_proof_compress(const lcp2_circuit *c, const uint64_t *proof, size_t proof_words, const uint64_t *public_inputs, size_t num_public_inputs,
+                        uint64_t *out, size_t out_cap, size_t *out_words);
+int lcp2_proof_decompress(const lcp2_circuit *c, const uint64_t *comp, size_t comp_words, const uint64_t *public_inputs, size_t num_public_inputs,
+                          uint64_t *proof, size_t proof_words);
+/* lcp2_verify_batch_ex for compressed proofs.  comps: the compressed proofs back to back, in host or device memory (comps_mem);
+ * offsets: host, count + 1 ascending word offsets, proof i being comps[offsets[i] .. offsets[i + 1]).  flags, public_inputs,
+ * failed_checks, return codes and count == 0 as lcp2_verify_batch_ex; a public-input length that is not the circuit's, offsets that
+ * do not ascend and null arguments are LCP2_E_INVALID with failed_checks untouched.  The verdict of proof i is what lcp2_verify
+ * reports for lcp2_proof_decompress of it, and check 1 (encoding) where that refuses.  Per chunk the unchanged words are scattered
+ * into full-layout proofs in scratch slot 0, the head gives the query indices, k_decompress_paths rebuilds every tree's multiproof
+ * (each shared node hashed once) into them, and the kernels of lcp2_verify_batch run on them unchanged.  A chunk holds
+ * min(4096, LCP2_COMPRESSED_SCRATCH_BYTES / (8 * lcp2_proof_words), what the pinned staging serves) proofs, at least one.
+ * Timing: LCP2_K_OTHER. */
+int lcp2_verify_batch_compressed(lcp2_ctx *ctx, const lcp2_circuit *c, const uint64_t *comps, const uint64_t *offsets, size_t count, lcp2_mem comps_mem,
+                                 const uint64_t *public_inputs, size_t num_public_inputs, int32_t *failed_checks, uint32_t flags);
+
 /* ---- byte serialisation of a proof: plonky2 0.1.4 util/serialization.rs `write_proof_with_public_inputs`
  * ([RECALL] of the published format; the reference holds no serialised proof - src/main.rs:230-233 moves the object - so
  * this layout is PARITY UNPINNED).  Little-endian throughout: a field element is its canonical u64, an extension element two
