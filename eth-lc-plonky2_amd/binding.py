@@ -172,6 +172,22 @@ class ChallengerState(ctypes.Structure):
                 ("input_len", ctypes.c_uint32), ("output_len", ctypes.c_uint32)]
 
 
+class FriConfig(ctypes.Structure):
+    """lcp2_fri_config: a FriConfig with its reduction schedule"""
+    _fields_ = [("rate_bits", ctypes.c_uint32), ("cap_height", ctypes.c_uint32), ("proof_of_work_bits", ctypes.c_uint32),
+                ("num_query_rounds", ctypes.c_uint32), ("num_fri_layers", ctypes.c_uint32), ("fri_arity_bits", ctypes.c_uint32 * 8)]
+
+
+class FriRange(ctypes.Structure):
+    _fields_ = [("oracle", ctypes.c_uint32), ("first_poly", ctypes.c_uint32), ("num_polys", ctypes.c_uint32)]
+
+
+class FriInstance(ctypes.Structure):
+    """lcp2_fri_instance (plonky2 FriInstanceInfo): build one with fri_instance(), which keeps the range arrays alive"""
+    _fields_ = [("num_oracles", ctypes.c_uint32), ("num_points", ctypes.c_uint32), ("num_ranges", ctypes.c_uint32 * 4),
+                ("ranges", ctypes.POINTER(FriRange) * 4)]
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64.so / libhsa-runtime64.so.  Two HIP runtimes in one
     process cannot both own the GPU, and torch tensors / streams are only meaningful to the runtime that made
@@ -279,6 +295,13 @@ def load_library():
         "lcp2_challenger_observe": (c.c_int, [c.POINTER(ChallengerState), c.c_void_p, c.c_size_t]),
         "lcp2_challenger_get": (c.c_int, [c.POINTER(ChallengerState), c.c_void_p, c.c_size_t]),
         "lcp2_hash_no_pad": (c.c_int, [c.c_void_p, c.c_size_t, c.c_void_p]),
+        "lcp2_fri_config_of": (c.c_int, [c.c_uint32] * 7 + [c.POINTER(FriConfig)]),
+        "lcp2_oracle_eval": (c.c_int, [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]),
+        "lcp2_fri_openings_words": (c.c_size_t, [c.POINTER(FriConfig), c.c_uint32, c.c_void_p, c.POINTER(FriInstance)]),
+        "lcp2_fri_prove_openings": (c.c_int, [c.c_void_p, c.c_void_p, c.POINTER(FriInstance), c.c_void_p, c.POINTER(FriConfig),
+                                              c.POINTER(ChallengerState), c.c_void_p, c.c_size_t]),
+        "lcp2_fri_verify_openings": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint32, c.POINTER(FriInstance), c.c_void_p, c.POINTER(FriConfig),
+                                               c.POINTER(ChallengerState), c.c_void_p, c.c_size_t, c.POINTER(c.c_int32)]),
         "lcp2_circuit_create_sharded": (c.c_int, [c.c_void_p, c.POINTER(CircuitDesc), c.c_uint32, c.c_uint32, c.POINTER(c.c_void_p)]),
         "lcp2_circuit_set_constants_cap": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_quotient_values": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p]),
@@ -345,6 +368,58 @@ def params_config(degree_bits, num_constants=4, rate_bits=3, cap_height=4, proof
     return p
 
 
+def fri_config(log_n, rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28, arity_bits=4, final_poly_bits=5, schedule=None):
+    """lcp2_fri_config_of: a FriConfig for polynomials of 2^log_n coefficients under ConstantArityBits(arity_bits, final_poly_bits);
+    schedule: a list of arity bits to use instead of the derived one"""
+    lib, cfg = load_library(), FriConfig()
+    rc = lib.lcp2_fri_config_of(log_n, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, arity_bits, final_poly_bits, ctypes.byref(cfg))
+    if rc:
+        raise Lcp2Error(rc, lib.lcp2_status_str(rc).decode())
+    if schedule is not None:
+        cfg.num_fri_layers = len(schedule)
+        for i in range(8):
+            cfg.fri_arity_bits[i] = schedule[i] if i < len(schedule) else 0
+    return cfg
+
+
+def fri_instance(num_oracles, points_ranges):
+    """lcp2_fri_instance from points_ranges = [[(oracle, first_poly, num_polys), ...] per point]; the arrays live in the result"""
+    inst = FriInstance()
+    inst.num_oracles, inst.num_points = num_oracles, len(points_ranges)
+    inst._keep = []
+    for b, ranges in enumerate(points_ranges[:4]):
+        arr = (FriRange * max(len(ranges), 1))(*[FriRange(*r) for r in ranges])
+        inst._keep.append(arr)
+        inst.num_ranges[b] = len(ranges)
+        inst.ranges[b] = ctypes.cast(arr, ctypes.POINTER(FriRange))
+    return inst
+
+
+def fri_openings_words(cfg, log_n, oracle_cols, inst):
+    """lcp2_fri_openings_words: the length of the proof of lcp2_fri_prove_openings, 0 for a refused shape"""
+    cols = np.ascontiguousarray(oracle_cols, dtype=np.uint32)
+    return load_library().lcp2_fri_openings_words(ctypes.byref(cfg), log_n, _ptr(cols), ctypes.byref(inst))
+
+
+def fri_verify_openings(caps, oracle_cols, log_n, inst, points, cfg, challenger_state, proof):
+    """lcp2_fri_verify_openings (host only): 0 if accepted, else the failed check 1..7; Lcp2Error for a refused call.
+    challenger_state is updated to the state after the query indices."""
+    lib = load_library()
+    caps = [np.ascontiguousarray(np.asarray(c, dtype=np.uint64).ravel()) for c in caps]
+    cap_ptrs = (ctypes.c_void_p * len(caps))(*[c.ctypes.data for c in caps])
+    cols = np.ascontiguousarray(oracle_cols, dtype=np.uint32)
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).ravel())
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    failed = ctypes.c_int32(0)
+    rc = lib.lcp2_fri_verify_openings(cap_ptrs, _ptr(cols), log_n, ctypes.byref(inst), _ptr(pts), ctypes.byref(cfg), ctypes.byref(challenger_state),
+                                      _ptr(pr), pr.size, ctypes.byref(failed))
+    if rc == 0:
+        return 0
+    if rc == -7:
+        return failed.value
+    raise Lcp2Error(rc, lib.lcp2_status_str(rc).decode())
+
+
 class Oracle:
     """PolynomialBatch handle (device resident)."""
 
@@ -362,6 +437,13 @@ class Oracle:
         sib = np.zeros((k, max(nsib, 0), 4), dtype=np.uint64)
         self.ctx._check(self.ctx.lib.lcp2_oracle_open(self.handle, _ptr(idx), k, _ptr(leaves), _ptr(sib)))
         return leaves, sib
+
+    def eval(self, points):
+        """lcp2_oracle_eval: every polynomial of the batch at the extension points [k][2] -> [k][ncols][2], canonical"""
+        pts = _np_u64(points).reshape(-1, 2)
+        out = np.zeros((pts.shape[0], self.ncols, 2), dtype=np.uint64)
+        self.ctx._check(self.ctx.lib.lcp2_oracle_eval(self.handle, _ptr(pts), pts.shape[0], _ptr(out)))
+        return out
 
     def read(self, coeffs=True, lde=True):
         n = 1 << self.log_n
@@ -509,6 +591,18 @@ class Context:
         o = Oracle(self, h, ncols, log_n, rate_bits, cap_height, cap)
         o.block_first, o.block_count = block_first, block_count
         return o
+
+    def fri_prove_openings(self, oracles, inst, points, cfg, challenger_state):
+        """lcp2_fri_prove_openings (PolynomialBatch::prove_openings for a bare FriInstanceInfo): the proof - the openings, then a
+        FriProof; challenger_state is updated to the state after the query indices"""
+        handles = (ctypes.c_void_p * len(oracles))(*[o.handle for o in oracles])
+        cols = np.array([o.ncols for o in oracles], dtype=np.uint32)
+        words = self.lib.lcp2_fri_openings_words(ctypes.byref(cfg), oracles[0].log_n if oracles else 0, _ptr(cols), ctypes.byref(inst))
+        proof = np.zeros(max(words, 1), dtype=np.uint64)
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).ravel())
+        self._check(self.lib.lcp2_fri_prove_openings(self.handle, handles, ctypes.byref(inst), _ptr(pts), ctypes.byref(cfg),
+                                                     ctypes.byref(challenger_state), _ptr(proof), words))
+        return proof[:words]
 
     # ---- device buffers
     def buffer_zero(self, dev_ptr, words):

@@ -792,6 +792,79 @@ int lcp2_challenger_observe(lcp2_challenger *ch, const uint64_t *values, size_t 
 int lcp2_challenger_get(lcp2_challenger *ch, uint64_t *out, size_t count);   /* challenges pop from the back of the output buffer */
 int lcp2_hash_no_pad(const uint64_t *values, size_t count, uint64_t out[4]); /* PoseidonHash::hash_no_pad (public-input hash) */
 
+/* ------------------------------------------------------------------ openings of bare oracles
+ * PolynomialBatch::prove_openings / verify_fri_proof (plonky2 fri/oracle.rs, fri/verifier.rs) for ANY FriInstanceInfo over
+ * oracles made by lcp2_commit_values / lcp2_commit_coeffs: what lcp2_fri_open does for the one instance of a Plonk proof, without a
+ * circuit handle - the commitment layer a STARK prover (starky) reaches through the same two calls.  PARITY UNPINNED, like the rest
+ * of the opening phase: pinned are the proof against an independent model of the verifier (eth_lc_plonky2_amd.fri_openings) and the
+ * openings against Horner evaluation.
+ *   instance   batch b = the point points[b] and the polynomials of ranges[b][0 .. num_ranges[b]), in range order; a range is
+ *           num_polys >= 1 columns of one oracle from first_poly on and must lie inside it; a polynomial may appear under several
+ *           points; a point without a range, num_oracles outside [1, LCP2_FRI_MAX_ORACLES] and num_points outside
+ *           [1, LCP2_FRI_MAX_POINTS] are LCP2_E_INVALID.
+ *   config     all oracles of a call share log_n, rate_bits and cap_height with cfg (LCP2_E_INVALID otherwise); the bounds of cfg are
+ *           those of lcp2_params_config, with proof_of_work_bits 0 .. 40 and 1 .. 64 query rounds.  A coset-sharded oracle
+ *           (lcp2_commit_cosets) is LCP2_E_UNSUPPORTED.
+ *   points     two u64 each, reduced mod p.  A point that is 0 is LCP2_E_INVALID in the prover and the verifier (the division by
+ *           X - zeta goes through the inverse powers of zeta, as in lcp2_fri_open); lcp2_last_error names the point index and nothing
+ *           has been touched.  Every other point is taken, a point of the subgroup H or of the LDE coset too: the prover divides
+ *           in coefficient form, which is exact there.  The verifier cannot divide at a queried x that equals a point: check 7.
+ *   proof      lcp2_fri_openings_words words (0 for an instance or config the library refuses), in this order:
+ *             openings          for each point, for each of its ranges in order, for each polynomial: 2 words
+ *             FRI caps          num_fri_layers x (4 << cap_height) words
+ *             query rounds      num_query_rounds x query_words; inside a round, for oracle o = 0 .. num_oracles - 1 the leaf
+ *                               (oracle_cols[o] words) followed by log_n + rate_bits - cap_height sibling digests; then for FRI
+ *                               layer l 2 << fri_arity_bits[l] words of evaluations followed by the layer's sibling digests
+ *             final polynomial  2 << (log_n - sum of the arity bits) words
+ *             PoW witness       1 word
+ *           i.e. the openings followed by a FriProof in the word order of a Plonk proof from LCP2_SECTION_FRI_CAP0 on.  One function
+ *           (csrc/fri_openings.hpp fo_make_layout) derives every offset for prover and verifier; fri_openings.py restates it.
+ *   transcript  that of lcp2_fri_open: ch comes in as the caller left it (the caps of the oracles are the caller's to observe, as in
+ *           plonky2); the call observes the openings in layout order, draws alpha, per layer observes the cap and draws beta,
+ *           observes the final polynomial, the PoW witness (the smallest one; 0 with proof_of_work_bits = 0), draws the PoW
+ *           response and the query indices; ch goes out in the state after the indices, from prover and verifier alike.
+ *   combination  plonky2's: with C_b = sum_j alpha^j f_j over the polynomials of batch b in order, the committed polynomial is
+ *           sum_b alpha^(polynomials of the batches after b) (C_b - C_b(zeta_b)) / (X - zeta_b)   (ReducingFactor::shift_poly);
+ *           for the two batches of a Plonk proof this is the polynomial lcp2_fri_open commits.
+ * lcp2_fri_config_of: a FriConfig with the ConstantArityBits(arity_bits, final_poly_bits) schedule for polynomials of 2^log_n
+ *   coefficients - the schedule, bounds and refusals of lcp2_params_config.
+ * lcp2_oracle_eval: every polynomial of the batch at k extension points (any u64 pairs), from the coefficients on the device
+ *   (chunked Horner and a reduction, the kernels behind the openings of lcp2_fri_open); out is canonical.  k = 0 is LCP2_OK.
+ * lcp2_fri_prove_openings: device work on the context's stream; the oracles must belong to ctx.  Host outputs are complete on
+ *   return.  Scratch slots 0 to 2 of the context hold the work area.  Timing: LCP2_K_OPENINGS, LCP2_K_FRI, LCP2_K_POW.
+ * lcp2_fri_verify_openings: host only, no context.  caps[o]: the cap of oracle o (4 << cap_height words).  LCP2_E_INVALID for a
+ *   refused instance / config / point or a proof_words that is not lcp2_fri_openings_words (nothing is read then); otherwise LCP2_OK
+ *   or LCP2_E_VERIFY with *failed_check (nullable; 0 when accepted):
+ *     1 a word of the proof is not canonical     2 proof of work              3 Merkle path of an initial oracle
+ *     4 Merkle path of a FRI layer               5 fold consistency           6 final polynomial
+ *     7 a query index lands on an opened point (x = zeta_b: the quotient cannot be evaluated there)
+ *   Checks 1 and 2 come first; then the queries in order, and inside a query the paths of the oracles in order (3), the points (7),
+ *   then per layer the consistency of the carried value (5) and the layer's path (4), and the final polynomial (6): the first
+ *   failure met is the one reported. */
+#define LCP2_FRI_MAX_ORACLES 8
+#define LCP2_FRI_MAX_POINTS  4
+typedef struct {
+  uint32_t rate_bits, cap_height, proof_of_work_bits, num_query_rounds;
+  uint32_t num_fri_layers, fri_arity_bits[LCP2_MAX_FRI_LAYERS];
+} lcp2_fri_config;
+typedef struct { uint32_t oracle, first_poly, num_polys; } lcp2_fri_range;
+/* plonky2 FriInstanceInfo: batch b = the point points[b] and the polynomials of its ranges, in range order */
+typedef struct {
+  uint32_t num_oracles, num_points;
+  uint32_t num_ranges[LCP2_FRI_MAX_POINTS];
+  const lcp2_fri_range *ranges[LCP2_FRI_MAX_POINTS];
+} lcp2_fri_instance;
+int lcp2_fri_config_of(uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, uint32_t pow_bits, uint32_t num_query_rounds,
+                       uint32_t arity_bits, uint32_t final_poly_bits, lcp2_fri_config *out);
+int lcp2_oracle_eval(lcp2_oracle *o, const uint64_t *points /* [k][2] */, size_t k, uint64_t *out /* [k][ncols][2], host */);
+size_t lcp2_fri_openings_words(const lcp2_fri_config *cfg, uint32_t log_n, const uint32_t *oracle_cols, const lcp2_fri_instance *inst);
+int lcp2_fri_prove_openings(lcp2_ctx *ctx, lcp2_oracle *const *oracles, const lcp2_fri_instance *inst,
+                            const uint64_t *points /* [num_points][2] */, const lcp2_fri_config *cfg,
+                            lcp2_challenger *ch, uint64_t *proof, size_t proof_words);
+int lcp2_fri_verify_openings(const uint64_t *const *caps, const uint32_t *oracle_cols, uint32_t log_n,
+                             const lcp2_fri_instance *inst, const uint64_t *points, const lcp2_fri_config *cfg,
+                             lcp2_challenger *ch, const uint64_t *proof, size_t proof_words, int32_t *failed_check);
+
 /* ---- one proof sharded over the GPUs of a node by LDE coset (BASELINE configs[3]).
  * A sharded circuit holds the leaf blocks [block_first, block_first + block_count) of every LDE and Merkle tree
  * (block_count a power of two dividing 2^rate_bits, block_first aligned to it, cap_height >= rate_bits so that a block is
