@@ -7,13 +7,15 @@ directory name follows the project ("eth-lc-plonky2_amd"); import it as
 """
 from .binding import (CircuitData, ProofRejected, Context, Lcp2Error, Oracle, Params, load_library, standard_params, params_config,  # noqa: F401
                       MEM_DEVICE, MEM_HOST, KERNEL_FAMILIES, WitnessReport, GOLDILOCKS_P, proof_to_bytes, proof_from_bytes, proof_layout,
-                      FriConfig, FriRange, FriInstance, fri_config, fri_instance, fri_openings_words, fri_verify_openings)
+                      FriConfig, FriRange, FriInstance, fri_config, fri_instance, fri_openings_words, fri_verify_openings,
+                      StarkDesc, StarkProgram, StarkViolation, stark_proof_words, stark_verify)
 from .build import build_native, build_host  # noqa: F401
 from . import binding  # noqa: F401,E402
 from . import circuit  # noqa: F401,E402
 from . import poseidon_py  # noqa: F401,E402
 from . import proof_compress  # noqa: F401,E402
 from . import fri_openings  # noqa: F401,E402
+from . import stark  # noqa: F401,E402
 from . import recursion_gates  # noqa: F401,E402
 from . import u32_gates  # noqa: F401,E402
 from . import sha_plan  # noqa: F401,E402

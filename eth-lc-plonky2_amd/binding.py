@@ -188,6 +188,23 @@ class FriInstance(ctypes.Structure):
                 ("ranges", ctypes.POINTER(FriRange) * 4)]
 
 
+class StarkProgram(ctypes.Structure):
+    _fields_ = [("code_offset", ctypes.c_uint32), ("code_len", ctypes.c_uint32), ("num_constraints", ctypes.c_uint32)]
+
+
+class StarkDesc(ctypes.Structure):
+    """lcp2_stark_desc: build one with stark.pack_stark_desc(), which keeps the code and immediate arrays alive"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("width", ctypes.c_uint32), ("num_public_inputs", ctypes.c_uint32), ("num_challenges", ctypes.c_uint32),
+                ("quotient_degree_bits", ctypes.c_uint32), ("fri", FriConfig), ("first_row", StarkProgram), ("transition", StarkProgram),
+                ("last_row", StarkProgram), ("code", ctypes.c_void_p), ("code_words", ctypes.c_size_t), ("imm", ctypes.c_void_p),
+                ("num_imm", ctypes.c_size_t), ("num_regs", ctypes.c_uint32)]
+
+
+class StarkViolation(ctypes.Structure):
+    """lcp2_stark_violation: kind 0 first / 1 transition / 2 last, the constraint's index within its program, the row"""
+    _fields_ = [("kind", ctypes.c_uint32), ("constraint", ctypes.c_uint32), ("row", ctypes.c_uint64)]
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64.so / libhsa-runtime64.so.  Two HIP runtimes in one
     process cannot both own the GPU, and torch tensors / streams are only meaningful to the runtime that made
@@ -302,6 +319,10 @@ def load_library():
                                               c.POINTER(ChallengerState), c.c_void_p, c.c_size_t]),
         "lcp2_fri_verify_openings": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint32, c.POINTER(FriInstance), c.c_void_p, c.POINTER(FriConfig),
                                                c.POINTER(ChallengerState), c.c_void_p, c.c_size_t, c.POINTER(c.c_int32)]),
+        "lcp2_stark_proof_words": (c.c_size_t, [c.POINTER(StarkDesc)]),
+        "lcp2_stark_prove": (c.c_int, [c.c_void_p, c.POINTER(StarkDesc), c.c_void_p, c.c_int, c.c_void_p, c.POINTER(ChallengerState), c.c_void_p,
+                                       c.c_size_t, c.POINTER(StarkViolation)]),
+        "lcp2_stark_verify": (c.c_int, [c.POINTER(StarkDesc), c.c_void_p, c.POINTER(ChallengerState), c.c_void_p, c.c_size_t, c.POINTER(c.c_int32)]),
         "lcp2_circuit_create_sharded": (c.c_int, [c.c_void_p, c.POINTER(CircuitDesc), c.c_uint32, c.c_uint32, c.POINTER(c.c_void_p)]),
         "lcp2_circuit_set_constants_cap": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_quotient_values": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p]),
@@ -413,6 +434,26 @@ def fri_verify_openings(caps, oracle_cols, log_n, inst, points, cfg, challenger_
     failed = ctypes.c_int32(0)
     rc = lib.lcp2_fri_verify_openings(cap_ptrs, _ptr(cols), log_n, ctypes.byref(inst), _ptr(pts), ctypes.byref(cfg), ctypes.byref(challenger_state),
                                       _ptr(pr), pr.size, ctypes.byref(failed))
+    if rc == 0:
+        return 0
+    if rc == -7:
+        return failed.value
+    raise Lcp2Error(rc, lib.lcp2_status_str(rc).decode())
+
+
+def stark_proof_words(desc):
+    """lcp2_stark_proof_words: the length of the proof of lcp2_stark_prove, 0 for a refused description"""
+    return load_library().lcp2_stark_proof_words(ctypes.byref(desc))
+
+
+def stark_verify(desc, public_inputs, challenger_state, proof):
+    """lcp2_stark_verify (host only): 0 if accepted, else the failed check 1..9; Lcp2Error for a refused call.  challenger_state
+    is updated as the verifier leaves it."""
+    lib = load_library()
+    pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    failed = ctypes.c_int32(0)
+    rc = lib.lcp2_stark_verify(ctypes.byref(desc), _ptr(pis), ctypes.byref(challenger_state), _ptr(pr), pr.size, ctypes.byref(failed))
     if rc == 0:
         return 0
     if rc == -7:
@@ -602,6 +643,29 @@ class Context:
         pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).ravel())
         self._check(self.lib.lcp2_fri_prove_openings(self.handle, handles, ctypes.byref(inst), _ptr(pts), ctypes.byref(cfg),
                                                      ctypes.byref(challenger_state), _ptr(proof), words))
+        return proof[:words]
+
+    def stark_prove(self, desc, trace, public_inputs, challenger_state, mem=MEM_HOST):
+        """lcp2_stark_prove: the proof of the AIR `desc` (stark.pack_stark_desc) for trace [width][n] - a numpy array, or a device
+        pointer with mem=MEM_DEVICE; challenger_state is updated as the opening layer leaves it.  A violated constraint raises
+        Lcp2Error with status -5 and the StarkViolation in its `violation` attribute."""
+        words = self.lib.lcp2_stark_proof_words(ctypes.byref(desc))
+        proof = np.zeros(max(words, 1), dtype=np.uint64)
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if mem == MEM_HOST:
+            trace = _np_u64(trace)
+            tp = _ptr(trace)
+        else:
+            tp = ctypes.c_void_p(trace)
+        violation = StarkViolation()
+        rc = self.lib.lcp2_stark_prove(self.handle, ctypes.byref(desc), tp, mem, _ptr(pis), ctypes.byref(challenger_state), _ptr(proof), words,
+                                       ctypes.byref(violation))
+        if rc == -5:
+            detail = self.lib.lcp2_last_error(self.handle)
+            e = Lcp2Error(rc, self.lib.lcp2_status_str(rc).decode() + (": " + detail.decode() if detail else ""))
+            e.violation = violation
+            raise e
+        self._check(rc)
         return proof[:words]
 
     # ---- device buffers

@@ -275,10 +275,12 @@ inline u32 fo_verify_head(const FoLayout &L, const gl2 *points, const u64 *proof
   return pow_ok ? 0 : FO_CHECK_POW;
 }
 
-// lcp2_fri_verify_openings without its ABI dress: LCP2_OK / LCP2_E_VERIFY / LCP2_E_INVALID (why says why)
+// lcp2_fri_verify_openings without its ABI dress: LCP2_OK / LCP2_E_VERIFY / LCP2_E_INVALID (why says why).  after_head(L): a check
+// of the caller's between checks 1 and 2 and the queries (0, or the number it reports): the STARK verifier's identity (stark.hpp).
+template <class AfterHead>
 inline int fo_verify_openings(const u64 *const *caps, const u32 *oracle_cols, u32 log_n, const lcp2_fri_instance *inst, const u64 *points,
                               const lcp2_fri_config *cfg, lcp2_challenger *chs, const u64 *proof, size_t proof_words, int32_t *failed_check,
-                              std::string &why) {
+                              std::string &why, AfterHead after_head) {
   if (failed_check) *failed_check = 0;
   u32 point_polys[FO_MAX_POINTS] = {0};
   gl2 z[FO_MAX_POINTS];
@@ -294,6 +296,7 @@ inline int fo_verify_openings(const u64 *const *caps, const u32 *oracle_cols, u3
   FoChallenge c = {};
   u32 failed = fo_verify_head(L, z, proof, ch, c);
   if (failed != FO_CHECK_CANON) ch.save((u64 *)chs->sponge, (u64 *)chs->input, chs->input_len, (u64 *)chs->output, chs->output_len);
+  if (!failed) failed = after_head(L);
   if (!failed) {
     // the caps enter the paths as field elements: reduced copies
     std::vector<u64> cap_words((size_t)inst->num_oracles * L.capw);
@@ -308,6 +311,11 @@ inline int fo_verify_openings(const u64 *const *caps, const u32 *oracle_cols, u3
   }
   if (failed_check) *failed_check = (int32_t)failed;
   return failed ? LCP2_E_VERIFY : LCP2_OK;
+}
+inline int fo_verify_openings(const u64 *const *caps, const u32 *oracle_cols, u32 log_n, const lcp2_fri_instance *inst, const u64 *points,
+                              const lcp2_fri_config *cfg, lcp2_challenger *chs, const u64 *proof, size_t proof_words, int32_t *failed_check,
+                              std::string &why) {
+  return fo_verify_openings(caps, oracle_cols, log_n, inst, points, cfg, chs, proof, proof_words, failed_check, why, [](const FoLayout &) { return 0u; });
 }
 
 }  // namespace lcp2

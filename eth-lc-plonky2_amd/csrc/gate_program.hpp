@@ -155,4 +155,24 @@ void eval_gates_filtered(Alg &A, const lcp2_gate *gates, size_t num_gates, const
   }
 }
 
+// Degree bound of a program's constraints in the column polynomials (each of degree < n): the program walked over degree bounds,
+// where a sum has the larger degree of its terms and a product the sum of its factors', saturating at DEGREE_CAP.
+constexpr uint32_t DEGREE_CAP = 1u << 20;
+struct DegreeAlg {
+  using V = uint32_t; using S = uint32_t;
+  static V hi(V a, V b) { return a > b ? a : b; }
+  V wire(uint32_t) { return 1; }    V gate_const(uint32_t) { return 1; }    V imm(uint64_t) { return 0; }    V pi(uint32_t) { return 0; }    S scalar(uint64_t) { return 0; }
+  V add(V a, V b) { return hi(a, b); }    V sub(V a, V b) { return hi(a, b); }    V mul(V a, V b) { return a + b < DEGREE_CAP ? a + b : DEGREE_CAP; }
+  V mul_add(V a, V b, V acc) { return hi(acc, mul(a, b)); }
+  V scale_add(V x, S, V acc) { return hi(x, acc); }
+};
+inline uint32_t program_degree(const uint32_t *code, size_t first, size_t len, size_t nregs) {
+  uint32_t reg[MAX_REGS + MDS_WIDTH] = {0};
+  (void)nregs;  // validated against MAX_REGS by every caller
+  DegreeAlg A;
+  uint32_t deg = 0;
+  walk_program(A, code, first, len, (const uint64_t *)nullptr, reg, [&](uint32_t d) { deg = d > deg ? d : deg; });
+  return deg;
+}
+
 }  // namespace gate_program

@@ -78,23 +78,7 @@ const char *validate_programs(const lcp2_circuit_desc *d) {
   return nullptr;
 }
 
-// Degree bound of a gate's constraints in the wire and constant polynomials (each of degree < n): the program walked over degree
-// bounds, where a sum has the larger degree of its terms and a product the sum of its factors', saturating at DEGREE_CAP.
-constexpr u32 DEGREE_CAP = 1u << 20;
-struct DegreeAlg {
-  using V = u32; using S = u32;
-  V wire(u32) { return 1; }    V gate_const(u32) { return 1; }    V imm(u64) { return 0; }    V pi(u32) { return 0; }    S scalar(u64) { return 0; }
-  V add(V a, V b) { return std::max(a, b); }    V sub(V a, V b) { return std::max(a, b); }    V mul(V a, V b) { return std::min(a + b, DEGREE_CAP); }
-  V mul_add(V a, V b, V acc) { return std::max(acc, mul(a, b)); }
-  V scale_add(V x, S, V acc) { return std::max(x, acc); }
-};
-u32 program_degree(const uint32_t *code, size_t first, size_t len, size_t nregs) {
-  std::vector<u32> reg(std::max<size_t>(nregs, 1), 0);
-  DegreeAlg A;
-  u32 deg = 0;
-  gp::walk_program(A, code, first, len, (const u64 *)nullptr, reg.data(), [&](u32 d) { deg = std::max(deg, d); });
-  return deg;
-}
+using gp::program_degree;  // the degree bound of a program's constraints (gate_program.hpp)
 
 // The half tier of K6 (prover_kernels.hpp QuotientTiers), from the derived degrees alone.  Per selector group the gates of degree
 // <= 2^(q-1) are taken by falling degree and put first-fit into bundles with max degree + size - 1 <= 2^(q-1).

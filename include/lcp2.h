@@ -865,6 +865,65 @@ int lcp2_fri_verify_openings(const uint64_t *const *caps, const uint32_t *oracle
                              const lcp2_fri_instance *inst, const uint64_t *points, const lcp2_fri_config *cfg,
                              lcp2_challenger *ch, const uint64_t *proof, size_t proof_words, int32_t *failed_check);
 
+/* ------------------------------------------------------------------ AIR proofs (STARKs) over the openings of bare oracles
+ * The engine of a starky proof: a trace of `width` columns and n = 2^log_n rows, constraints on a row and its successor, the
+ * quotient, and the two calls above for the commitment layer.  PARITY UNPINNED: starky is not at hand, so the proof is pinned
+ * against an independent model (eth_lc_plonky2_amd.stark), not against starky's bytes.  No permutation, lookup or cross-table
+ * argument, no blinding; the verifier is host only.
+ *   programs   three gate programs in the instruction format above (every op 0 .. 9), any of them empty: first_row, transition,
+ *           last_row.  Operand kinds are re-read: WIRE idx < width is column idx of the local row, WIRE width <= idx < 2 width is
+ *           column idx - width of the next row, PI idx < num_public_inputs is the public input itself (not a hash), IMM and REG
+ *           as in a gate program; CONST is LCP2_E_INVALID.  Constraints are taken in program order; the registers are zero at
+ *           the start of each program.  width is 1 .. 32767 (both rows must fit the 16-bit operand index; lcp2_commit_values
+ *           takes up to 65535 columns), num_regs <= 64, num_challenges 1 .. 4.
+ *   combination  (starky ConstraintConsumer) the constraints of first_row, transition, last_row form one list c_0 .. c_{m-1}; per
+ *           challenge alpha the Horner pass acc <- acc alpha + f(c_i) c_i runs over it, with f = L_first for first-row, (X - g^-1)
+ *           for transition and L_last for last-row constraints, g the generator of H and L_k(X) = g^k Z_H(X) / (n (X - g^k)).  The
+ *           quotient acc / Z_H is evaluated on the first 2^q n leaves of the trace LDE (the coset 7 H_{2^q n} in leaf order, as the
+ *           Plonk quotient), brought to coefficients, split into Q = 2^q chunks of n per challenge (chunk k of challenge c is
+ *           column c Q + k) and committed like lcp2_commit_coeffs.  With deg = lcp2_gate_program_degree of a program, deg > Q is
+ *           LCP2_E_INVALID, as are q > fri.rate_bits and everything lcp2_fri_prove_openings refuses of fri and log_n.
+ *   transcript  ch comes in as the caller left it (binding the AIR's identity is the caller's to do).  The call observes the
+ *           public inputs (reduced) and the trace cap, draws num_challenges alphas (base field), observes the quotient cap, draws
+ *           zeta (extension) and hands over to lcp2_fri_prove_openings with the instance { zeta: all trace columns, all
+ *           quotient columns; g zeta: all trace columns }; ch goes out as that call leaves it.  zeta = 0 is that call's refusal.
+ *   proof      lcp2_stark_proof_words words (0 for a refused description): trace cap, quotient cap (4 << cap_height words each),
+ *           then exactly the words of lcp2_fri_openings_words for the instance.  One function (csrc/stark.hpp st_make_layout)
+ *           derives the offsets for both sides.
+ *   witness check  before anything is committed the same constraint text runs over the n rows of the trace as given: the next
+ *           row of row i is row (i + 1) mod n; transition constraints are not enforced on row n - 1, first-row constraints on
+ *           row 0 only, last-row constraints on row n - 1 only; values are compared canonically (any u64 is accepted and
+ *           reduced).  A violation is LCP2_E_UNSAT with *violation (nullable) the one with the smallest (row, index in the list):
+ *           kind 0 first / 1 transition / 2 last, the constraint's index within its program, the row.  Nothing is committed then.
+ * lcp2_stark_prove: trace [width][n] values on H in natural row order, host or device.  Device work on the context's stream; all
+ *   four scratch slots of the context are used, the two oracles live for the call only.  Host outputs are complete on return.
+ *   Timing: there is no family of its own - the check and the quotient kernel are booked under LCP2_K_QUOTIENT, the transform of
+ *   the quotient under LCP2_K_INTT, commitments and openings under the families of lcp2_commit_* and lcp2_fri_prove_openings.
+ * lcp2_stark_verify: host only, no context.  LCP2_E_INVALID for a refused description or a proof_words that is not
+ *   lcp2_stark_proof_words (nothing is read then); otherwise LCP2_OK or LCP2_E_VERIFY with *failed_check (nullable; 0 when accepted):
+ *     1 .. 7 as lcp2_fri_verify_openings reports them     8 a word of the two caps is not canonical     9 the quotient identity
+ *     vanishing_c(zeta) == Z_H(zeta) sum_k chunk_{c,k}(zeta) zeta^(n k) fails for a challenge
+ *   in this order: 8; the opening layer's checks 1 and 2; 9; the rest of the opening layer's checks. */
+typedef struct { uint32_t code_offset, code_len, num_constraints; } lcp2_stark_program;   /* in instructions */
+typedef struct {
+  uint32_t log_n;                 /* n = 2^log_n trace rows */
+  uint32_t width;                 /* trace columns */
+  uint32_t num_public_inputs;
+  uint32_t num_challenges;        /* 1..4 alphas */
+  uint32_t quotient_degree_bits;  /* q, 0..fri.rate_bits: Q = 2^q quotient chunks per challenge */
+  lcp2_fri_config fri;
+  lcp2_stark_program first_row, transition, last_row;   /* any of them may be empty (code_len 0) */
+  const uint32_t *code; size_t code_words; const uint64_t *imm; size_t num_imm; uint32_t num_regs;  /* <= 64 */
+} lcp2_stark_desc;
+typedef struct { uint32_t kind /* 0 first, 1 transition, 2 last */, constraint; uint64_t row; } lcp2_stark_violation;
+
+size_t lcp2_stark_proof_words(const lcp2_stark_desc *d);   /* 0 for a refused description */
+int lcp2_stark_prove(lcp2_ctx *ctx, const lcp2_stark_desc *d, const uint64_t *trace /* [width][n] values on H, natural order */,
+                     lcp2_mem trace_mem, const uint64_t *public_inputs, lcp2_challenger *ch,
+                     uint64_t *proof, size_t proof_words, lcp2_stark_violation *violation /* nullable */);
+int lcp2_stark_verify(const lcp2_stark_desc *d, const uint64_t *public_inputs, lcp2_challenger *ch,
+                      const uint64_t *proof, size_t proof_words, int32_t *failed_check /* nullable */);
+
 /* ---- one proof sharded over the GPUs of a node by LDE coset (BASELINE configs[3]).
  * A sharded circuit holds the leaf blocks [block_first, block_first + block_count) of every LDE and Merkle tree
  * (block_count a power of two dividing 2^rate_bits, block_first aligned to it, cap_height >= rate_bits so that a block is
