@@ -1,5 +1,6 @@
 // The circuit handle and what the prover's host units (prover.hip, prover_build.hip, prover_stages.hip, prover_open.hip) share.
-// No kernel unit includes this.
+// fri_commit.hpp, the FRI back end of prover_open.hip and fri_openings.hip, builds on the copy helpers here and declares its own
+// functions.  No kernel unit includes this.
 #pragma once
 #include <array>
 #include <cstring>

@@ -1,9 +1,9 @@
 // Openings of bare oracles: lcp2_fri_config_of, lcp2_oracle_eval, lcp2_fri_openings_words, lcp2_fri_prove_openings and
 // lcp2_fri_verify_openings (include/lcp2.h).  PolynomialBatch::prove_openings for any FriInstanceInfo, without a circuit handle: the
 // k_open_* kernels below compose and divide the instance's batches (fri_openings.hpp holds their text) and gather the query answers
-// of all oracles; evaluation, scan, LDE, leaf hashing, Merkle levels, fold, proof of work and the FRI-layer gathers go through the
-// launchers the Plonk opening (prover_open.hip) uses, and the transcript through the same host challenger.
-#include "circuit_state.hpp"
+// of all oracles.  Column evaluation and the whole FRI back end - layer commitments, commit phase, proof of work, query indices, the
+// FRI-layer answers - are fri_commit.hip, the text the Plonk opening (prover_open.hip) runs too, over the work area carved here.
+#include "fri_commit.hpp"
 #include "fri_openings.hpp"
 
 using namespace lcp2;
@@ -53,27 +53,6 @@ __global__ __launch_bounds__(64) void k_open_gather_leaves(OpenGather g, const u
 }
 
 namespace {
-u32 eval_chunk_len(u64 n) { return (u32)std::min<u64>(n, EVAL_CHUNK); }
-size_t eval_table_words(u64 n) { return 512 + 2 * (size_t)(n / eval_chunk_len(n)); }
-// the power tables of z for polynomials of n coefficients: once per point
-void eval_tables(hipStream_t s, u64 n, gl2 z, u64 *d_tab) {
-  launch_eval_tables(s, z.c0, z.c1, eval_chunk_len(n), (u32)(n / eval_chunk_len(n)), d_tab);
-}
-// `ncols` (<= 65535: they are the grid's y) coefficient columns [ncols][n] at z: d_out[2 * ncols] (the launchers of the Plonk
-// openings; d_tab: eval_tables of z, d_partial: scratch)
-void eval_columns(hipStream_t s, const u64 *coeffs, u32 ncols, u64 n, gl2 z, const u64 *d_tab, u64 *d_partial, u64 *d_out) {
-  EvalArgs a{};
-  a.coeffs = coeffs; a.col_stride = n;
-  a.chunk_len = eval_chunk_len(n);
-  a.items = (a.chunk_len + 255) / 256;
-  a.nchunks = (u32)(n / a.chunk_len);
-  const gl2 zs = gl2_pow(z, 256);
-  a.zstep[0] = zs.c0; a.zstep[1] = zs.c1;
-  a.zpow_t = d_tab; a.zpow_chunk = d_tab + 512;
-  a.partial = d_partial;
-  launch_eval_polys(s, a, ncols, d_out);
-}
-
 // Host vectors that asynchronous copies read (pageable memory) must outlive those copies on EVERY way out of a call: declared
 // after the vectors, this synchronises the stream before they are destroyed, on the error returns too.
 struct SyncOnExit {
@@ -185,7 +164,7 @@ extern "C" int lcp2_fri_prove_openings(lcp2_ctx *ctx, lcp2_oracle *const *oracle
   Carve A, D, T;
   const size_t nchunks = n / eval_chunk_len(n);
   const size_t a_planes = A.take(2 * (size_t)NP * n), a_scan = A.take(scan_scratch_words(n, 2 * NP)), a_c0 = A.take(2 * n), a_c1 = A.take(2 * n);
-  size_t a_vals[LCP2_MAX_FRI_LAYERS], d_dig[LCP2_MAX_FRI_LAYERS], d_off[LCP2_MAX_FRI_LAYERS], side_leaf[LCP2_MAX_FRI_LAYERS], side_sib[LCP2_MAX_FRI_LAYERS];
+  size_t a_vals[LCP2_MAX_FRI_LAYERS], d_dig[LCP2_MAX_FRI_LAYERS], d_off[LCP2_MAX_FRI_LAYERS];
   // what asynchronous copies read from the host: level_off, weights, mask, idx - and the guard that keeps them alive long enough
   std::vector<u64> level_off[LCP2_MAX_FRI_LAYERS], weights, idx;
   std::vector<u32> mask;
@@ -206,17 +185,21 @@ extern "C" int lcp2_fri_prove_openings(lcp2_ctx *ctx, lcp2_oracle *const *oracle
   const size_t t_tables = T.take(NP * fo_table_words(zh, hi_count)), t_weights = T.take((size_t)total_cols * 2 * FO_MAX_POINTS), t_mask = T.take((total_cols + 1) / 2);
   const size_t t_evtab = T.take(eval_table_words(n)), t_partial = T.take(2 * (size_t)max_range * nchunks), t_open = T.take(2 * (size_t)L.total_polys);
   const size_t t_idx = T.take((size_t)Qn * (1 + layers)), t_rounds = T.take((size_t)Qn * L.query_words), t_pow = T.take(1);
-  size_t t_side = 0;
-  for (u32 l = 0; l < layers; l++) {
-    side_leaf[l] = t_side; t_side += (size_t)Qn * (2u << L.arity_bits[l]);
-    side_sib[l] = t_side; t_side += (size_t)Qn * 4 * L.step_sib[l];
-  }
-  const size_t t_sidebuf = T.take(t_side);
+  // what fri_commit.hpp works on, first by its shape (the side buffer of the layer answers follows from it), then by its pointers
+  FriWork w{};
+  w.log_n = log_n; w.rate_bits = cfg->rate_bits; w.cap_height = cfg->cap_height; w.num_layers = layers;
+  w.final_len = L.final_len; w.pow_bits = cfg->proof_of_work_bits; w.num_queries = Qn;
+  for (u32 l = 0; l < layers; l++) { w.arity_bits[l] = L.arity_bits[l]; w.layer[l].nlevels = (u32)level_off[l].size(); }
+  FriSide side_at;
+  const size_t t_side = fri_side_layout(w, 0, side_at), t_sidebuf = T.take(t_side);
   LCP2_TRY(scratch_ensure(ctx, 0, A.words * 8, (void **)&A.base));
   LCP2_TRY(scratch_ensure(ctx, 1, D.words * 8 + 8, (void **)&D.base));
   LCP2_TRY(scratch_ensure(ctx, 2, T.words * 8, (void **)&T.base));
-  for (u32 l = 0; l < layers; l++)
+  w.fri_c[0] = A.base + a_c0; w.fri_c[1] = A.base + a_c1; w.d_pow = T.base + t_pow;
+  for (u32 l = 0; l < layers; l++) {
+    w.layer[l] = {A.base + a_vals[l], D.base + d_dig[l], D.base + d_off[l], level_off[l].data(), w.layer[l].nlevels};
     LCP2_HIP(ctx, hipMemcpyAsync(D.base + d_off[l], level_off[l].data(), level_off[l].size() * 8, hipMemcpyHostToDevice, s));
+  }
 
   // ---- openings: every range of every point evaluated from the coefficients, one copy back
   memset(proof, 0, L.total * 8);
@@ -246,7 +229,6 @@ extern "C" int lcp2_fri_prove_openings(lcp2_ctx *ctx, lcp2_oracle *const *oracle
   a.num_oracles = NO; a.num_points = NP; a.n = n;
   a.weights = T.base + t_weights; a.mask = (const u32 *)(T.base + t_mask); a.tables = T.base + t_tables;
   a.zh = zh; a.hi_count = hi_count; a.planes = A.base + a_planes;
-  u64 *fri_c[2] = {A.base + a_c0, A.base + a_c1};
   {
     OpenPoints P{};
     for (u32 b = 0; b < NP; b++) { P.z[b][0] = z[b].c0; P.z[b][1] = z[b].c1; }
@@ -265,79 +247,16 @@ extern "C" int lcp2_fri_prove_openings(lcp2_ctx *ctx, lcp2_oracle *const *oracle
     hipLaunchKernelGGL(k_open_tables, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, P, NP, zh, hi_count, T.base + t_tables);
     hipLaunchKernelGGL(k_open_compose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     launch_scan(s, false, a.planes, a.planes, A.base + a_scan, n, true, 2 * NP, n);
-    hipLaunchKernelGGL(k_open_divide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, fri_c[0], fri_c[0] + n);
+    hipLaunchKernelGGL(k_open_divide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, w.fri_c[0], w.fri_c[0] + n);
   }
   LCP2_HIP(ctx, hipGetLastError());
 
-  // ---- FRI commit phase: per layer LDE of the two planes, leaves, Merkle levels, cap; then the fold
-  DeviceNttBackend be{ctx};
-  NttHost<DeviceNttBackend> ntt(be);
-  u64 m = n, shift = GL_GENERATOR;
-  int cur = 0;
-  for (u32 l = 0; l < layers; l++) {
-    const u32 ab = L.arity_bits[l], arity = 1u << ab;
-    const u64 nvals = m << cfg->rate_bits, nleaves = nvals >> ab;
-    u32 lgm = 0;
-    while ((1ull << lgm) < m) lgm++;
-    u64 *vals = A.base + a_vals[l], *dig = D.base + d_dig[l];
-    {
-      ProfScope ps(ctx, LCP2_K_FRI, 16.0 * m + 16.0 * nvals + 32.0 * nleaves);
-      ntt.forward(fri_c[cur], m, vals, nvals, lgm, 2, shift, cfg->rate_bits);
-      if (be.status) return be.status;
-      launch_hash_ext_leaves(s, vals, vals + nvals, arity, nleaves, dig, ctx->d_rc);
-      for (size_t k = 1; k < level_off[l].size(); k++)
-        launch_merkle_level(s, dig + 4 * level_off[l][k - 1], dig + 4 * level_off[l][k], nleaves >> k, ctx->d_rc);
-    }
-    LCP2_HIP(ctx, hipGetLastError());
-    u64 *cap = proof + L.fri_caps + (u64)l * L.capw;
-    LCP2_TRY(download(ctx, cap, dig + 4 * level_off[l].back(), (size_t)L.capw * 8));
-    ch.observe_n(cap, L.capw);
-    const gl2 beta = ch.get_ext();
-    {
-      ProfScope ps(ctx, LCP2_K_FRI, 16.0 * m + 16.0 * (m >> ab));
-      launch_fri_fold(s, fri_c[cur], fri_c[cur] + m, fri_c[cur ^ 1], fri_c[cur ^ 1] + (m >> ab), m >> ab, arity, beta.c0, beta.c1);
-    }
-    cur ^= 1;
-    m >>= ab;
-    shift = gl_pow(shift, arity);
-  }
-  if (m != L.final_len) return ctx->fail(LCP2_E_INVALID, "internal: final polynomial length mismatch");
-  {
-    std::vector<u64> f(2 * m);
-    LCP2_TRY(download(ctx, f.data(), fri_c[cur], 2 * m * 8));
-    for (u64 i = 0; i < m; i++) { proof[L.final_poly + 2 * i] = f[i]; proof[L.final_poly + 2 * i + 1] = f[m + i]; }
-  }
-  ch.observe_n(proof + L.final_poly, 2 * (size_t)L.final_len);
+  // ---- the FRI back end: commit phase, proof of work (0 bits: witness 0, nothing launched), query indices
+  LCP2_TRY(fri_commit_phase(ctx, w, ch, false, proof + L.fri_caps, nullptr, proof + L.final_poly));
+  LCP2_TRY(fri_proof_of_work(ctx, w, ch, proof + L.pow_witness));
+  fri_draw_indices(w, ch, idx);
 
-  // ---- proof of work: the smallest witness (0 bits: every witness passes, 0 is the smallest)
-  u64 witness = 0;
-  if (cfg->proof_of_work_bits) {
-    PowArgs pa{};
-    ch.pow_state(pa.state, pa.pos);
-    pa.bits = cfg->proof_of_work_bits; pa.rc = ctx->d_rc; pa.result = T.base + t_pow;
-    const u64 batch = 1ull << 20;
-    witness = ~0ull;
-    ProfScope ps(ctx, LCP2_K_POW, 0.0);
-    for (u64 start = 0; witness == ~0ull; start += batch) {
-      if (start >= (1ull << 44)) return ctx->fail(LCP2_E_UNSUPPORTED, "proof of work not found");
-      { SmallWords w{}; w.v[0] = ~0ull; launch_set_words(s, pa.result, w, 1); }
-      pa.start = start;
-      launch_pow_search(s, pa, batch);
-      LCP2_TRY(download(ctx, &witness, pa.result, 8));
-    }
-  }
-  proof[L.pow_witness] = witness;
-  ch.observe(witness);
-  const u64 response = ch.get();
-  if (cfg->proof_of_work_bits && (response >> (64 - cfg->proof_of_work_bits)) != 0) return ctx->fail(LCP2_E_HIP, "internal: proof-of-work self check failed");
-
-  // ---- query indices and answers
-  idx.assign((size_t)Qn * (1 + layers), 0);
-  for (u32 q = 0; q < Qn; q++) {
-    u64 xi = ch.get() % N;
-    idx[q] = xi;
-    for (u32 l = 0; l < layers; l++) { xi >>= L.arity_bits[l]; idx[(size_t)(1 + l) * Qn + q] = xi; }
-  }
+  // ---- query answers
   u64 *d_idx = T.base + t_idx, *d_rounds = T.base + t_rounds, *d_side = T.base + t_sidebuf;
   LCP2_HIP(ctx, hipMemcpyAsync(d_idx, idx.data(), idx.size() * 8, hipMemcpyHostToDevice, s));
   {
@@ -351,14 +270,9 @@ extern "C" int lcp2_fri_prove_openings(lcp2_ctx *ctx, lcp2_oracle *const *oracle
     hipLaunchKernelGGL(k_open_gather_leaves, dim3(Qn, NO), dim3(64), 0, s, g, d_idx, d_rounds);
   }
   {
-    u64 nvals = N;
-    for (u32 l = 0; l < layers; l++) {
-      const u32 arity = 1u << L.arity_bits[l];
-      const u64 *d_leaf = d_idx + (size_t)(1 + l) * Qn;
-      launch_gather_ext_leaves(s, A.base + a_vals[l], A.base + a_vals[l] + nvals, arity, d_leaf, Qn, d_side + side_leaf[l]);
-      launch_gather_digests(s, D.base + d_dig[l], D.base + d_off[l], L.step_sib[l], d_leaf, Qn, d_side + side_sib[l]);
-      nvals >>= L.arity_bits[l];
-    }
+    const u64 *d_leaf[LCP2_MAX_FRI_LAYERS];
+    for (u32 l = 0; l < layers; l++) d_leaf[l] = d_idx + (size_t)(1 + l) * Qn;
+    fri_gather_layers(ctx, w, d_leaf, d_side, side_at);
   }
   LCP2_HIP(ctx, hipGetLastError());
   {
@@ -367,14 +281,7 @@ extern "C" int lcp2_fri_prove_openings(lcp2_ctx *ctx, lcp2_oracle *const *oracle
     LCP2_TRY(d.add(proof + L.queries, d_rounds, (size_t)Qn * L.query_words * 8));
     LCP2_TRY(d.add(side.data(), d_side, t_side * 8));
     LCP2_TRY(d.wait());  // also the end of every use of idx and level_off by the stream
-    for (u32 q = 0; q < Qn; q++) {
-      u64 *R = proof + L.queries + (size_t)q * L.query_words;
-      for (u32 l = 0; l < layers; l++) {
-        const u32 words = 2u << L.arity_bits[l];
-        memcpy(R + L.step_off[l], side.data() + side_leaf[l] + (size_t)q * words, words * 8);
-        memcpy(R + L.step_off[l] + words, side.data() + side_sib[l] + (size_t)q * 4 * L.step_sib[l], (size_t)L.step_sib[l] * 32);
-      }
-    }
+    fri_scatter_layers(w, side.data(), side_at, proof + L.queries, L.query_words, L.step_off, [](u32) { return false; });
   }
   ch.save((u64 *)chs->sponge, (u64 *)chs->input, chs->input_len, (u64 *)chs->output, chs->output_len);
   return LCP2_OK;

@@ -1,5 +1,5 @@
 // Host orchestration of the prover: lcp2_prove (= data.prove(pw)) and the C ABI of its seams.  build() is prover_build.hip, the
-// stages are prover_stages.hip and prover_open.hip, the handle they share is circuit_state.hpp.
+// stages are prover_stages.hip and prover_open.hip (whose FRI back end is fri_commit.hip), the handle they share is circuit_state.hpp.
 //
 // Follows plonky2 0.1.4 plonk/prover.rs::prove step by step; every heavy step is a
 // kernel from kernels_*.hip on the context's stream.  The Fiat-Shamir challenger (row a14: a few hundred

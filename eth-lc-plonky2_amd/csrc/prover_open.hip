@@ -1,29 +1,28 @@
 // The batched opening (OpeningSet::new + PolynomialBatch::prove_openings): openings, final polynomial, FRI commit phase, proof of
-// work and the query answers.  Host orchestration over the kernels of kernels_prover.hip / kernels_hash.hip.
+// work and the query answers.  Host orchestration over the kernels of kernels_prover.hip / kernels_hash.hip.  What is the Plonk
+// opening's own is here: its openings, its compose / scan / divide, the initial-tree gathers, the share of a coset-sharded circuit
+// and the three phases; the FRI back end (layer commitment, commit phase, proof of work, query indices, layer answers) is
+// fri_commit.hip, shared with the openings of bare oracles (fri_openings.hip).
 #include "circuit_state.hpp"
+#include "fri_commit.hpp"
 
 using namespace lcp2;
 
 namespace {
-// evaluate `ncols` coefficient columns at z; results (ext) land in d_out[2 * ncols].  d_tab: the power tables of z (eval_tables)
-u32 eval_chunk_len(u64 n) { return (u32)std::min<u64>(n, EVAL_CHUNK); }
-size_t eval_table_words(u64 n) { return 512 + 2 * (size_t)(n / eval_chunk_len(n)); }
-void eval_tables(lcp2_circuit *c, gl2 z, u64 *d_tab) {  // z travels in the kernel arguments: no staging copy, no synchronisation
-  const u64 n = 1ull << c->p.degree_bits;
-  launch_eval_tables(c->ctx->stream, z.c0, z.c1, eval_chunk_len(n), (u32)(n / eval_chunk_len(n)), d_tab);
-}
-void eval_columns(lcp2_circuit *c, const u64 *coeffs, u32 ncols, gl2 z, u64 *d_out, const u64 *d_tab) {
-  const u64 n = 1ull << c->p.degree_bits;
-  EvalArgs a{};
-  a.coeffs = coeffs; a.col_stride = n;
-  a.chunk_len = eval_chunk_len(n);
-  a.items = (a.chunk_len + 255) / 256;
-  a.nchunks = (u32)(n / a.chunk_len);
-  const gl2 zs = gl2_pow(z, 256);
-  a.zstep[0] = zs.c0; a.zstep[1] = zs.c1;
-  a.zpow_t = d_tab; a.zpow_chunk = d_tab + 512;
-  a.partial = c->partial.u();
-  launch_eval_polys(c->ctx->stream, a, ncols, d_out);
+// the FRI work area of the handle (allocated by prover_build.hip), as fri_commit.hpp takes it
+FriWork fri_work_of(lcp2_circuit *c) {
+  const lcp2_params &p = c->p;
+  FriWork w{};
+  w.log_n = p.degree_bits; w.rate_bits = p.rate_bits; w.cap_height = p.cap_height; w.num_layers = p.num_fri_layers;
+  w.final_len = (u32)ProofLayout(p).final_len; w.pow_bits = p.proof_of_work_bits; w.num_queries = p.num_query_rounds;
+  w.fri_c[0] = c->fri_c[0].u(); w.fri_c[1] = c->fri_c[1].u();
+  for (u32 l = 0; l < p.num_fri_layers; l++) {
+    w.arity_bits[l] = p.fri_arity_bits[l];
+    w.layer[l] = {c->fri_vals[l].u(), c->fri_dig[l].u(), c->fri_d_level_off[l].u(), c->fri_level_off[l].data(), (u32)c->fri_level_off[l].size()};
+  }
+  w.d_pow = c->small.u() + SMALL_POW;
+  w.bf = c->bf; w.bc = c->bc;
+  return w;
 }
 }  // namespace
 
@@ -60,16 +59,18 @@ int lcp2::fri_open_openings(lcp2_circuit *c, u64 *proof) {
   u32 at_col[5], first_col[4], num_cols[4], pos = 0, share_cols = 0;
   for (int o = 0; o < 4; o++) { c->column_share(oracles[o]->ncols, first_col[o], num_cols[o]); share_cols += num_cols[o]; }
   ProfScope ps(ctx, LCP2_K_OPENINGS, 8.0 * n * (share_cols + CH));
-  eval_tables(c, zeta, d_tab);
+  hipStream_t s = e.s;
+  u64 *d_partial = c->partial.u();
+  eval_tables(s, n, zeta, d_tab);
   const bool with_next = !c->sharded() || c->bf == 0;
-  if (with_next) eval_tables(c, g_zeta, d_tab_g);
+  if (with_next) eval_tables(s, n, g_zeta, d_tab_g);
   for (int o = 0; o < 4; o++) {
     at_col[o] = pos;
-    if (num_cols[o]) eval_columns(c, oracles[o]->coeffs.u() + (size_t)first_col[o] * n, num_cols[o], zeta, d_open + 2 * pos, d_tab);
+    if (num_cols[o]) eval_columns(s, oracles[o]->coeffs.u() + (size_t)first_col[o] * n, num_cols[o], n, zeta, d_tab, d_partial, d_open + 2 * pos);
     pos += num_cols[o];
   }
   at_col[4] = pos;
-  if (with_next) { eval_columns(c, c->zs.coeffs.u(), CH, g_zeta, d_open + 2 * pos, d_tab_g); pos += CH; }
+  if (with_next) { eval_columns(s, c->zs.coeffs.u(), CH, n, g_zeta, d_tab_g, d_partial, d_open + 2 * pos); pos += CH; }
   LCP2_HIP(ctx, hipGetLastError());
   LCP2_TRY(download(ctx, tmp.data(), d_open, (size_t)2 * pos * 8));
   for (int o = 0; o < 4; o++)
@@ -84,38 +85,6 @@ int lcp2::fri_open_openings(lcp2_circuit *c, u64 *proof) {
   if (with_next) memcpy(proof + L.op_zs_next, tmp.data() + 2 * at_col[4], 2 * CH * 8);
   fo.phase = 1;
   return LCP2_OK;
-}
-
-// LDE of the coefficients in fri_c[cur] (m of them, zero padding to 8m implicit), leaf hashing and Merkle levels of FRI layer l;
-// the cap lands in the proof.  Layer 0 of a sharded circuit covers its own leaf blocks.
-static int fri_commit_layer(lcp2_circuit *c, u32 l, int cur, u64 m, u64 shift, u64 *proof) {
-  StageEnv e(c);
-  LCP2_TRY(e.status);
-  lcp2_ctx *ctx = e.ctx; const lcp2_params &p = e.p; const ProofLayout &L = e.L; hipStream_t s = e.s;
-  const u32 ab = p.fri_arity_bits[l], arity = 1u << ab;
-  const bool part = l == 0 && c->sharded();
-  u32 lgm = 0;
-  while ((1ull << lgm) < m) lgm++;
-  const u64 nvals = part ? (u64)c->bc * m : m << p.rate_bits, nleaves = nvals >> ab;
-  u64 *vals = c->fri_vals[l].u();
-  {
-    ProfScope ps(ctx, LCP2_K_FRI, 16.0 * m + 16.0 * nvals + 32.0 * nleaves);
-    // coset_fft of the zero-padded coefficients = 2^rate_bits coset transforms of the m coefficients; leaf order out
-    if (part) e.ntt.forward(c->fri_c[cur].u(), m, vals, nvals, lgm, 2, shift, p.rate_bits, c->bf, c->bc);
-    else e.ntt.forward(c->fri_c[cur].u(), m, vals, nvals, lgm, 2, shift, p.rate_bits);
-    if (e.be.status) return e.be.status;
-    launch_hash_ext_leaves(s, vals, vals + nvals, arity, nleaves, c->fri_dig[l].u(), ctx->d_rc);
-    const auto &off = c->fri_level_off[l];
-    for (size_t k = 1; k < off.size(); k++)
-      launch_merkle_level(s, c->fri_dig[l].u() + 4 * off[k - 1], c->fri_dig[l].u() + 4 * off[k], nleaves >> k, ctx->d_rc);
-  }
-  LCP2_HIP(ctx, hipGetLastError());
-  u64 *cap = proof + L.fri_caps + l * L.capw;
-  const u64 *d_cap = c->fri_dig[l].u() + 4 * c->fri_level_off[l].back();
-  if (!part) return download(ctx, cap, d_cap, L.capw * 8);
-  Download d(ctx);
-  LCP2_TRY(queue_cap(d, c, d_cap, cap));
-  return d.wait();
 }
 
 int lcp2::fri_open_commit(lcp2_circuit *c, u64 *proof) {
@@ -164,68 +133,22 @@ int lcp2::fri_open_commit(lcp2_circuit *c, u64 *proof) {
     launch_divide_finalize(s, a, c->fri_c[0].u(), c->fri_c[0].u() + n);
   }
   LCP2_HIP(ctx, hipGetLastError());
-  if (p.num_fri_layers) LCP2_TRY(fri_commit_layer(c, 0, 0, n, GL_GENERATOR, proof));
+  // FRI layer 0 here, so that the shards can exchange its cap before the last phase; a sharded circuit covers its own leaf blocks
+  if (p.num_fri_layers) {
+    const FriWork w = fri_work_of(c);
+    u64 *cap = proof + L.fri_caps;
+    LCP2_TRY(fri_commit_layer(ctx, w, 0, 0, n, GL_GENERATOR, c->sharded() ? nullptr : cap));
+    if (c->sharded()) {
+      Download d(ctx);
+      LCP2_TRY(queue_cap(d, c, w.d_cap(0), cap));
+      LCP2_TRY(d.wait());
+    }
+  }
   fo.phase = 2;
   return LCP2_OK;
 }
 
-// ---- the last phase in its four steps; each continues from what the one before left in c->fo and the proof
 namespace {
-// K8: the FRI commit phase (layer 0 is committed already) down to the final polynomial
-int fri_commit_phase(lcp2_circuit *c, u64 *proof) {
-  lcp2_ctx *ctx = c->ctx; const lcp2_params &p = c->p; hipStream_t s = ctx->stream; HostChallenger &ch = c->fo.ch;
-  const ProofLayout L(p);
-  u64 m = 1ull << p.degree_bits;  // number of (possibly) non-zero coefficients; the zero padding to 8m is implicit
-  u64 shift = GL_GENERATOR;
-  int cur = 0;
-  for (u32 l = 0; l < p.num_fri_layers; l++) {
-    const u32 ab = p.fri_arity_bits[l], arity = 1u << ab;
-    if (l) LCP2_TRY(fri_commit_layer(c, l, cur, m, shift, proof));
-    ch.observe_n(proof + L.fri_caps + l * L.capw, L.capw);
-    gl2 beta = ch.get_ext();
-    c->fo.fri_betas[l] = beta;
-    {
-      ProfScope ps(ctx, LCP2_K_FRI, 16.0 * m + 16.0 * (m >> ab));
-      launch_fri_fold(s, c->fri_c[cur].u(), c->fri_c[cur].u() + m, c->fri_c[cur ^ 1].u(), c->fri_c[cur ^ 1].u() + (m >> ab), m >> ab, arity, beta.c0, beta.c1);
-    }
-    cur ^= 1;
-    m >>= ab;
-    shift = gl_pow(shift, arity);
-  }
-  if (m != L.final_len) return ctx->fail(LCP2_E_INVALID, "internal: final polynomial length mismatch");
-  std::vector<u64> f(2 * m);
-  LCP2_TRY(download(ctx, f.data(), c->fri_c[cur].u(), 2 * m * 8));
-  for (u64 i = 0; i < m; i++) { proof[L.final_poly + 2 * i] = f[i]; proof[L.final_poly + 2 * i + 1] = f[m + i]; }
-  ch.observe_n(proof + L.final_poly, 2 * L.final_len);
-  return LCP2_OK;
-}
-
-// K9: proof of work, minimum witness
-int fri_proof_of_work(lcp2_circuit *c, u64 *proof) {
-  lcp2_ctx *ctx = c->ctx; const lcp2_params &p = c->p; hipStream_t s = ctx->stream; HostChallenger &ch = c->fo.ch;
-  u64 res = ~0ull;
-  {
-    PowArgs a{};
-    ch.pow_state(a.state, a.pos);
-    a.bits = p.proof_of_work_bits; a.rc = ctx->d_rc;
-    u64 *d_res = c->small.u() + SMALL_POW;
-    a.result = d_res;
-    const u64 batch = 1ull << 20;
-    ProfScope ps(ctx, LCP2_K_POW, 0.0);
-    for (u64 start = 0; res == ~0ull; start += batch) {
-      if (start >= (1ull << 44)) return ctx->fail(LCP2_E_UNSUPPORTED, "proof of work not found");
-      { SmallWords w{}; w.v[0] = ~0ull; launch_set_words(s, d_res, w, 1); }
-      a.start = start;
-      launch_pow_search(s, a, batch);
-      LCP2_TRY(download(ctx, &res, d_res, 8));
-    }
-  }
-  c->fo.pow_witness = proof[ProofLayout(p).pow_witness] = res;
-  ch.observe(res);
-  if ((ch.get() >> (64 - p.proof_of_work_bits)) != 0) return ctx->fail(LCP2_E_HIP, "internal: proof-of-work self check failed");
-  return LCP2_OK;
-}
-
 // a sharded circuit answers the initial-tree and FRI-layer-0 parts of the queries whose leaf it holds and leaves zeros for
 // the others (its share of the proof); the smaller FRI layers are replicated on every rank
 bool holds_leaf(const lcp2_circuit *c, u64 leaf) {
@@ -235,18 +158,12 @@ bool holds_leaf(const lcp2_circuit *c, u64 leaf) {
 
 // the query indices: drawn from the challenger, uploaded as [1 + layers][Qn] global leaves, [Qn] local leaves of the initial
 // trees, [Qn] local leaves of FRI layer 0
-int fri_query_indices(lcp2_circuit *c, u64 *) {
+int fri_query_indices(lcp2_circuit *c, const FriWork &w) {
   lcp2_ctx *ctx = c->ctx; const lcp2_params &p = c->p;
   std::vector<u64> &idx = c->fo.idx, &up = c->fo.idx_up;
   const u32 Qn = p.num_query_rounds;
-  const u64 n = 1ull << p.degree_bits, N = n << p.rate_bits;
-  idx.assign(Qn * (1 + p.num_fri_layers), 0);
-  for (u32 q = 0; q < Qn; q++) {
-    u64 x = c->fo.ch.get() % N;
-    idx[q] = x;
-    u64 xi = x;
-    for (u32 l = 0; l < p.num_fri_layers; l++) { xi >>= p.fri_arity_bits[l]; idx[(1 + l) * Qn + q] = xi; }
-  }
+  const u64 n = 1ull << p.degree_bits;
+  fri_draw_indices(w, c->fo.ch, idx);
   up = idx;
   for (u32 q = 0; q < Qn; q++) up.push_back(holds_leaf(c, idx[q]) ? idx[q] - (u64)c->bf * n : 0);
   for (u32 q = 0; q < Qn; q++) up.push_back(p.num_fri_layers ? up[idx.size() + q] >> p.fri_arity_bits[0] : 0);  // layer-0 leaf, local
@@ -260,55 +177,44 @@ int fri_query_indices(lcp2_circuit *c, u64 *) {
 }
 
 // query phase: gather leaves and Merkle paths on the device, one copy back, and scatter them into the query rounds of the proof
-int fri_answer_queries(lcp2_circuit *c, u64 *proof) {
+int fri_answer_queries(lcp2_circuit *c, const FriWork &w, u64 *proof) {
   lcp2_ctx *ctx = c->ctx; const lcp2_params &p = c->p; hipStream_t s = ctx->stream;
   const ProofLayout L(p);
   const std::vector<u64> &idx = c->fo.idx;
   const auto oracles = c->oracles();
   const u32 Qn = p.num_query_rounds;
-  const u64 n = 1ull << p.degree_bits, N = n << p.rate_bits, nlocal = (u64)c->nblocks() * n;
   u64 *d_idx = c->q_idx.u();
   const u64 *d_idx_local = d_idx + idx.size(), *d_idx_local0 = d_idx_local + Qn;
   u64 *buf = c->q_buf.u();
   size_t pos = 0;
-  size_t o_leaf[4], o_sib[4], f_leaf[LCP2_MAX_FRI_LAYERS], f_sib[LCP2_MAX_FRI_LAYERS];
+  size_t o_leaf[4], o_sib[4];
   for (int o = 0; o < 4; o++) {
     o_leaf[o] = pos; pos += (size_t)Qn * oracles[o]->ncols;
     o_sib[o] = pos; pos += (size_t)Qn * L.q_init_sib * 4;
+  }
+  FriSide side;
+  pos = fri_side_layout(w, pos, side);
+  if (pos * 8 > c->q_buf.bytes) return ctx->fail(LCP2_E_INVALID, "internal: query workspace too small");
+  for (int o = 0; o < 4; o++) {
     const lcp2_oracle &O = *oracles[o];
     launch_gather_rows(s, O.lde.u(), O.nleaves(), O.ncols, d_idx_local, Qn, buf + o_leaf[o]);
     launch_gather_digests(s, O.digests.u(), O.d_level_off.u(), O.nlevels() - 1, d_idx_local, Qn, buf + o_sib[o]);
   }
-  for (u32 l = 0; l < p.num_fri_layers; l++) {
-    const u32 arity = 1u << p.fri_arity_bits[l];
-    u64 nvals = N;  // values of layer l: N >> (arity bits of the layers before it)
-    for (u32 k = 0; k < l; k++) nvals >>= p.fri_arity_bits[k];
-    if (l == 0) nvals = nlocal;
-    const u64 *d_leaf = l == 0 ? d_idx_local0 : d_idx + (1 + l) * Qn;
-    f_leaf[l] = pos; pos += (size_t)Qn * 2 * arity;
-    f_sib[l] = pos; pos += (size_t)Qn * L.q_step_sib[l] * 4;
-    launch_gather_ext_leaves(s, c->fri_vals[l].u(), c->fri_vals[l].u() + nvals, arity, d_leaf, Qn, buf + f_leaf[l]);
-    launch_gather_digests(s, c->fri_dig[l].u(), c->fri_d_level_off[l].u(), (u32)L.q_step_sib[l], d_leaf, Qn, buf + f_sib[l]);
-  }
+  const u64 *d_leaf[LCP2_MAX_FRI_LAYERS];  // layer 0 by its local leaves, the replicated layers by their global ones
+  for (u32 l = 0; l < p.num_fri_layers; l++) d_leaf[l] = l == 0 ? d_idx_local0 : d_idx + (1 + l) * Qn;
+  fri_gather_layers(ctx, w, d_leaf, buf, side);
   LCP2_HIP(ctx, hipGetLastError());
-  if (pos * 8 > c->q_buf.bytes) return ctx->fail(LCP2_E_INVALID, "internal: query workspace too small");
   std::vector<u64> h(pos);
   LCP2_TRY(download(ctx, h.data(), buf, pos * 8));
   for (u32 q = 0; q < Qn; q++) {
     u64 *R = proof + L.queries + (size_t)q * L.query_words;
-    const bool mine = holds_leaf(c, idx[q]);
-    for (int o = 0; o < 4 && mine; o++) {
+    for (int o = 0; o < 4 && holds_leaf(c, idx[q]); o++) {
       u32 nc = oracles[o]->ncols;
       memcpy(R + L.q_init_off[o], h.data() + o_leaf[o] + (size_t)q * nc, nc * 8);
       memcpy(R + L.q_init_off[o] + nc, h.data() + o_sib[o] + (size_t)q * L.q_init_sib * 4, L.q_init_sib * 32);
     }
-    for (u32 l = 0; l < p.num_fri_layers; l++) {
-      if (l == 0 && !mine) continue;
-      const u32 arity = 1u << p.fri_arity_bits[l];
-      memcpy(R + L.q_step_off[l], h.data() + f_leaf[l] + (size_t)q * 2 * arity, 2 * arity * 8);
-      memcpy(R + L.q_step_off[l] + 2 * arity, h.data() + f_sib[l] + (size_t)q * L.q_step_sib[l] * 4, L.q_step_sib[l] * 32);
-    }
   }
+  fri_scatter_layers(w, h.data(), side, proof + L.queries, L.query_words, L.q_step_off, [&](u32 q) { return !holds_leaf(c, idx[q]); });
   // Shares must SUM to the proof (RCCL has no bitwise reductions): the words every rank holds identically (openings,
   // FRI caps, the smaller FRI layers, final polynomial, PoW witness) are contributed by the rank that holds leaf block 0 only.
   if (c->sharded() && c->bf != 0) {
@@ -326,8 +232,13 @@ int lcp2::fri_open_finish(lcp2_circuit *c, u64 *proof) {
   LCP2_TRY(select_device(c->ctx));
   if (c->fo.phase != 2) return c->ctx->fail(LCP2_E_INVALID, "lcp2_fri_open_finish: call lcp2_fri_open_commit first");
   c->fo.phase = 0;
-  LCP2_TRY(fri_commit_phase(c, proof));
-  LCP2_TRY(fri_proof_of_work(c, proof));
-  LCP2_TRY(fri_query_indices(c, proof));
-  return fri_answer_queries(c, proof);
+  lcp2_ctx *ctx = c->ctx; FriOpenState &fo = c->fo;
+  const ProofLayout L(c->p);
+  const FriWork w = fri_work_of(c);
+  // K8: the commit phase (layer 0 is committed already) down to the final polynomial; K9: proof of work, minimum witness
+  LCP2_TRY(fri_commit_phase(ctx, w, fo.ch, true, proof + L.fri_caps, fo.fri_betas, proof + L.final_poly));
+  LCP2_TRY(fri_proof_of_work(ctx, w, fo.ch, proof + L.pow_witness));
+  fo.pow_witness = proof[L.pow_witness];
+  LCP2_TRY(fri_query_indices(c, w));
+  return fri_answer_queries(c, w, proof);
 }

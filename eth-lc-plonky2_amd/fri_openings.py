@@ -290,9 +290,10 @@ def path(levels, index):
     return out
 
 
-def prove(coeff_cols_per_oracle, cfg, log_n, points_ranges, points, challenger, oracles=None):
+def prove(coeff_cols_per_oracle, cfg, log_n, points_ranges, points, challenger, oracles=None, first_witness=0):
     """(proof words, caps of the oracles); the challenger ends in the state after the query indices.  oracles: the commit() of every
-    oracle, where the caller has them already"""
+    oracle, where the caller has them already.  first_witness: where the proof-of-work scan starts - a caller that has shown by other
+    means that no smaller witness passes spares the model a scan of millions of permutations in Python"""
     oracle_cols = [len(c) for c in coeff_cols_per_oracle]
     L = layout(cfg, log_n, oracle_cols, points_ranges)
     points = [(int(z[0]) % P, int(z[1]) % P) for z in points]
@@ -332,7 +333,7 @@ def prove(coeff_cols_per_oracle, cfg, log_n, points_ranges, points, challenger, 
     assert len(coeffs) == L.final_len
     proof[L.final_poly:L.final_poly + 2 * L.final_len] = [w for c in coeffs for w in c]
     ch.observe(proof[L.final_poly:L.final_poly + 2 * L.final_len])
-    witness = 0
+    witness = first_witness
     while cfg.proof_of_work_bits:
         trial = Challenger()
         trial.sponge, trial.inp, trial.out = ch.words()

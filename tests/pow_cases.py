@@ -8,7 +8,7 @@ import numpy as np
 import oracle_lib
 
 P = oracle_lib.P
-BATCH = 1 << 20       # fri_proof_of_work (csrc/prover_open.hip): candidates per k_pow_search launch
+BATCH = 1 << 20       # fri_proof_of_work (csrc/fri_commit.hip): candidates per k_pow_search launch
 LATE_BITS = 20        # proof_of_work_bits of the late-batch cases
 POW_CHECK = 2         # the verdict of a proof whose proof-of-work response has a leading one (orc_verify, lcp2_verify, lcp2_verify_batch)
 CANON_CHECK = 1       # a proof word >= p
@@ -113,9 +113,9 @@ class PendingCount:
 
 
 def walk(t, p, words_of):
-    """the prover's observes and draws from the circuit digest to the final polynomial (prove() in oracle/plonk.c; fri_open_commit and
-    fri_commit_phase in csrc/prover_open.hip) on a transcript `t` with observe(x) and draw(count); words_of(first, count) is what is
-    observed for a span of the proof.  Returns the drawn values by name."""
+    """the prover's observes and draws from the circuit digest to the final polynomial (prove() in oracle/plonk.c; fri_open_commit in
+    csrc/prover_open.hip and fri_commit_phase in csrc/fri_commit.hip) on a transcript `t` with observe(x) and draw(count);
+    words_of(first, count) is what is observed for a span of the proof.  Returns the drawn values by name."""
     CH, NC, NR, W, Q = p.num_challenges, p.num_constants, p.num_routed_wires, p.num_wires, p.quotient_degree_factor
     npp = -(-NR // Q) - 1
     capw = 4 << p.cap_height

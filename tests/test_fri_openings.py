@@ -131,6 +131,73 @@ def test_openings_of_bare_oracles(gpu_ctx, oracle, name):
             gpu_ctx.buffer_free(p)
 
 
+# The proof-of-work search of the bare path beyond its first batch of 2^20 candidates (fri_proof_of_work in csrc/fri_commit.hip, the loop
+# test_pow_search.py pins through the Plonk prover): the smallest case with at least two FRI layers, on a transcript seed and at the fewest
+# proof-of-work bits under which the minimum witness lies beyond the first batch.  Both were found on the CPU alone: the model prover's
+# challenger up to the final polynomial, then every candidate from 0 upwards through the oracle's permutation.  Among the first seed
+# words 13 to 24 at 20 bits, 23 gives the witness nearest the start of the second batch; under that seed the minimum witness is 46 696
+# at 18 bits and 1 122 902 at 19 (and at 20).
+LATE_POW_CASE, LATE_POW_BITS, LATE_POW_SEED, LATE_POW_WITNESS = "3_overlap", 19, 23, 1122902
+
+
+def test_proof_of_work_beyond_the_first_batch(gpu_ctx, oracle):
+    from types import SimpleNamespace
+    import eth_lc_plonky2_amd as m
+    from eth_lc_plonky2_amd import fri_openings as fo
+    import pow_cases
+    deep = [oc.case(n) for n in oc.CASES if oc.case(n).cfg.num_fri_layers >= 2]   # smallest: the shortest proof (and no larger an LDE than any)
+    assert LATE_POW_CASE == min(deep, key=lambda k: fo.layout(k.cfg, k.log_n, k.cols, k.points_ranges).total).name
+    assert all(oc.CASES[LATE_POW_CASE][0] + oc.CASES[LATE_POW_CASE][1] <= k.log_n + k.rate_bits for k in deep)
+    c = oc.case(LATE_POW_CASE)
+    log_n, rate, cap, _, _, how, _, queries, _, _ = oc.CASES[LATE_POW_CASE]
+    cfg = m.fri_config(log_n, rate, cap, LATE_POW_BITS, queries, 1, log_n, schedule=how[1])
+    assert cfg.num_fri_layers == c.cfg.num_fri_layers >= 2 and cfg.proof_of_work_bits == LATE_POW_BITS
+    seed = [LATE_POW_SEED] + oc.transcript_seed(c)[1:]
+    coeffs = oc.coefficients(c)
+    pts = oc.points(c, "random")
+    L = fo.layout(cfg, c.log_n, c.cols, c.points_ranges)
+    oracles = [gpu_ctx.commit_coeffs(k, c.rate_bits, c.cap_height) for k in coeffs]
+    try:
+        caps = [o.cap.ravel() for o in oracles]
+        ch = m.binding.Challenger()
+        ch.observe(seed)
+        proof = gpu_ctx.fri_prove_openings(oracles, c.inst, pts, cfg, ch.state)
+    finally:
+        for o in oracles:
+            o.close()
+    witness = int(proof[L.pow_witness])
+    print("proof-of-work witness", witness, "batch", witness // pow_cases.BATCH)
+    assert pow_cases.BATCH <= witness < 2 * pow_cases.BATCH and witness == LATE_POW_WITNESS
+    # the minimum: the model's transcript of this proof up to the final polynomial, then the oracle's permutation on every candidate below
+    before = fo.Challenger()
+    before.observe(seed)
+    before.observe(proof[:L.fri_caps])
+    before.get_ext()
+    for l in range(len(L.arity)):
+        before.observe(proof[L.fri_caps + l * L.capw:L.fri_caps + (l + 1) * L.capw])
+        before.get_ext()
+    before.observe(proof[L.final_poly:L.final_poly + 2 * L.final_len])
+    sponge, pending, _ = before.words()
+    state = SimpleNamespace(s=np.array(sponge, dtype=np.uint64), inp=pending)
+    assert pow_cases.next_solution(oracle, state, -1, LATE_POW_BITS) == witness
+    # the model prover's proof, word for word (its own scan starts at the witness: the candidates below it were just ruled out)
+    pch = fo.Challenger()
+    pch.observe(seed)
+    model_proof, model_caps = fo.prove([[list(map(int, col)) for col in k] for k in coeffs], cfg, c.log_n, c.points_ranges, pts, pch, first_witness=witness)
+    assert all(np.array_equal(a, b) for a, b in zip(model_caps, caps))
+    assert np.array_equal(model_proof, proof)
+    assert pch.words() == fo.state_words(ch.state)
+    # both verifiers
+    vch = m.binding.Challenger()
+    vch.observe(seed)
+    assert m.fri_verify_openings(caps, c.cols, c.log_n, c.inst, pts, cfg, vch.state, proof) == 0
+    assert fo.state_words(vch.state) == fo.state_words(ch.state)
+    mch = fo.Challenger()
+    mch.observe(seed)
+    assert fo.verify(caps, cfg, c.log_n, c.cols, c.points_ranges, pts, mch, proof) == 0
+    assert mch.words() == fo.state_words(ch.state)
+
+
 def test_prover_refusals(gpu_ctx):
     """LCP2_E_INVALID before anything is touched: zeta = 0 (the point index is named), a config that is not the oracles', a wrong
     proof length; LCP2_E_UNSUPPORTED for a coset-sharded oracle"""
