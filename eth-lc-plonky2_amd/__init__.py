@@ -8,7 +8,7 @@ directory name follows the project ("eth-lc-plonky2_amd"); import it as
 from .binding import (CircuitData, ProofRejected, Context, Lcp2Error, Oracle, Params, load_library, standard_params, params_config,  # noqa: F401
                       MEM_DEVICE, MEM_HOST, KERNEL_FAMILIES, WitnessReport, GOLDILOCKS_P, proof_to_bytes, proof_from_bytes, proof_layout,
                       FriConfig, FriRange, FriInstance, fri_config, fri_instance, fri_openings_words, fri_verify_openings,
-                      StarkDesc, StarkProgram, StarkViolation, stark_proof_words, stark_verify)
+                      StarkDesc, StarkPerm, StarkPermPair, StarkProgram, StarkViolation, stark_proof_words, stark_verify)
 from .build import build_native, build_host  # noqa: F401
 from . import binding  # noqa: F401,E402
 from . import circuit  # noqa: F401,E402

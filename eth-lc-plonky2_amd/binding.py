@@ -201,8 +201,19 @@ class StarkDesc(ctypes.Structure):
 
 
 class StarkViolation(ctypes.Structure):
-    """lcp2_stark_violation: kind 0 first / 1 transition / 2 last, the constraint's index within its program, the row"""
+    """lcp2_stark_violation: kind 0 first / 1 transition / 2 last, the constraint's index within its program, the row; kind 3: the
+    running product of Z number `constraint` of a permutation argument does not close (row n - 1)"""
     _fields_ = [("kind", ctypes.c_uint32), ("constraint", ctypes.c_uint32), ("row", ctypes.c_uint64)]
+
+
+class StarkPermPair(ctypes.Structure):
+    _fields_ = [("first", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
+class StarkPerm(ctypes.Structure):
+    """lcp2_stark_perm: build one with stark.pack_stark_perm(), which keeps the pair and column arrays alive"""
+    _fields_ = [("num_pairs", ctypes.c_uint32), ("pairs", ctypes.c_void_p), ("columns", ctypes.c_void_p), ("num_column_pairs", ctypes.c_size_t),
+                ("batch_size", ctypes.c_uint32)]
 
 
 def _share_torch_hip_runtime():
@@ -323,6 +334,11 @@ def load_library():
         "lcp2_stark_prove": (c.c_int, [c.c_void_p, c.POINTER(StarkDesc), c.c_void_p, c.c_int, c.c_void_p, c.POINTER(ChallengerState), c.c_void_p,
                                        c.c_size_t, c.POINTER(StarkViolation)]),
         "lcp2_stark_verify": (c.c_int, [c.POINTER(StarkDesc), c.c_void_p, c.POINTER(ChallengerState), c.c_void_p, c.c_size_t, c.POINTER(c.c_int32)]),
+        "lcp2_stark_perm_proof_words": (c.c_size_t, [c.POINTER(StarkDesc), c.POINTER(StarkPerm)]),
+        "lcp2_stark_prove_perm": (c.c_int, [c.c_void_p, c.POINTER(StarkDesc), c.POINTER(StarkPerm), c.c_void_p, c.c_int, c.c_void_p, c.POINTER(ChallengerState),
+                                            c.c_void_p, c.c_size_t, c.POINTER(StarkViolation)]),
+        "lcp2_stark_verify_perm": (c.c_int, [c.POINTER(StarkDesc), c.POINTER(StarkPerm), c.c_void_p, c.POINTER(ChallengerState), c.c_void_p, c.c_size_t,
+                                             c.POINTER(c.c_int32)]),
         "lcp2_circuit_create_sharded": (c.c_int, [c.c_void_p, c.POINTER(CircuitDesc), c.c_uint32, c.c_uint32, c.POINTER(c.c_void_p)]),
         "lcp2_circuit_set_constants_cap": (c.c_int, [c.c_void_p, c.c_void_p]),
         "lcp2_quotient_values": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p]),
@@ -441,19 +457,25 @@ def fri_verify_openings(caps, oracle_cols, log_n, inst, points, cfg, challenger_
     raise Lcp2Error(rc, lib.lcp2_status_str(rc).decode())
 
 
-def stark_proof_words(desc):
-    """lcp2_stark_proof_words: the length of the proof of lcp2_stark_prove, 0 for a refused description"""
-    return load_library().lcp2_stark_proof_words(ctypes.byref(desc))
+def stark_proof_words(desc, perm=None):
+    """lcp2_stark_proof_words (with perm, a StarkPerm: lcp2_stark_perm_proof_words): the length of the proof of lcp2_stark_prove, 0 for
+    a refused description"""
+    if perm is None:
+        return load_library().lcp2_stark_proof_words(ctypes.byref(desc))
+    return load_library().lcp2_stark_perm_proof_words(ctypes.byref(desc), ctypes.byref(perm))
 
 
-def stark_verify(desc, public_inputs, challenger_state, proof):
-    """lcp2_stark_verify (host only): 0 if accepted, else the failed check 1..9; Lcp2Error for a refused call.  challenger_state
-    is updated as the verifier leaves it."""
+def stark_verify(desc, public_inputs, challenger_state, proof, perm=None):
+    """lcp2_stark_verify (with perm, a StarkPerm: lcp2_stark_verify_perm; host only): 0 if accepted, else the failed check 1..9;
+    Lcp2Error for a refused call.  challenger_state is updated as the verifier leaves it."""
     lib = load_library()
     pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
     pr = np.ascontiguousarray(proof, dtype=np.uint64)
     failed = ctypes.c_int32(0)
-    rc = lib.lcp2_stark_verify(ctypes.byref(desc), _ptr(pis), ctypes.byref(challenger_state), _ptr(pr), pr.size, ctypes.byref(failed))
+    if perm is None:
+        rc = lib.lcp2_stark_verify(ctypes.byref(desc), _ptr(pis), ctypes.byref(challenger_state), _ptr(pr), pr.size, ctypes.byref(failed))
+    else:
+        rc = lib.lcp2_stark_verify_perm(ctypes.byref(desc), ctypes.byref(perm), _ptr(pis), ctypes.byref(challenger_state), _ptr(pr), pr.size, ctypes.byref(failed))
     if rc == 0:
         return 0
     if rc == -7:
@@ -645,11 +667,12 @@ class Context:
                                                      ctypes.byref(challenger_state), _ptr(proof), words))
         return proof[:words]
 
-    def stark_prove(self, desc, trace, public_inputs, challenger_state, mem=MEM_HOST):
-        """lcp2_stark_prove: the proof of the AIR `desc` (stark.pack_stark_desc) for trace [width][n] - a numpy array, or a device
-        pointer with mem=MEM_DEVICE; challenger_state is updated as the opening layer leaves it.  A violated constraint raises
-        Lcp2Error with status -5 and the StarkViolation in its `violation` attribute."""
-        words = self.lib.lcp2_stark_proof_words(ctypes.byref(desc))
+    def stark_prove(self, desc, trace, public_inputs, challenger_state, mem=MEM_HOST, perm=None):
+        """lcp2_stark_prove (with perm, a StarkPerm of stark.pack_stark_perm: lcp2_stark_prove_perm): the proof of the AIR `desc`
+        (stark.pack_stark_desc) for trace [width][n] - a numpy array, or a device pointer with mem=MEM_DEVICE; challenger_state is
+        updated as the opening layer leaves it.  A violated constraint raises Lcp2Error with status -5 and the StarkViolation in its
+        `violation` attribute."""
+        words = stark_proof_words(desc, perm)
         proof = np.zeros(max(words, 1), dtype=np.uint64)
         pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
         if mem == MEM_HOST:
@@ -658,8 +681,12 @@ class Context:
         else:
             tp = ctypes.c_void_p(trace)
         violation = StarkViolation()
-        rc = self.lib.lcp2_stark_prove(self.handle, ctypes.byref(desc), tp, mem, _ptr(pis), ctypes.byref(challenger_state), _ptr(proof), words,
-                                       ctypes.byref(violation))
+        if perm is None:
+            rc = self.lib.lcp2_stark_prove(self.handle, ctypes.byref(desc), tp, mem, _ptr(pis), ctypes.byref(challenger_state), _ptr(proof), words,
+                                           ctypes.byref(violation))
+        else:
+            rc = self.lib.lcp2_stark_prove_perm(self.handle, ctypes.byref(desc), ctypes.byref(perm), tp, mem, _ptr(pis), ctypes.byref(challenger_state),
+                                                _ptr(proof), words, ctypes.byref(violation))
         if rc == -5:
             detail = self.lib.lcp2_last_error(self.handle)
             e = Lcp2Error(rc, self.lib.lcp2_status_str(rc).decode() + (": " + detail.decode() if detail else ""))

@@ -868,8 +868,8 @@ int lcp2_fri_verify_openings(const uint64_t *const *caps, const uint32_t *oracle
 /* ------------------------------------------------------------------ AIR proofs (STARKs) over the openings of bare oracles
  * The engine of a starky proof: a trace of `width` columns and n = 2^log_n rows, constraints on a row and its successor, the
  * quotient, and the two calls above for the commitment layer.  PARITY UNPINNED: starky is not at hand, so the proof is pinned
- * against an independent model (eth_lc_plonky2_amd.stark), not against starky's bytes.  No permutation, lookup or cross-table
- * argument, no blinding; the verifier is host only.
+ * against an independent model (eth_lc_plonky2_amd.stark), not against starky's bytes.  Permutation arguments go through the _perm
+ * calls further down; no lookup or cross-table argument, no blinding; the verifier is host only.
  *   programs   three gate programs in the instruction format above (every op 0 .. 9), any of them empty: first_row, transition,
  *           last_row.  Operand kinds are re-read: WIRE idx < width is column idx of the local row, WIRE width <= idx < 2 width is
  *           column idx - width of the next row, PI idx < num_public_inputs is the public input itself (not a hash), IMM and REG
@@ -915,7 +915,7 @@ typedef struct {
   lcp2_stark_program first_row, transition, last_row;   /* any of them may be empty (code_len 0) */
   const uint32_t *code; size_t code_words; const uint64_t *imm; size_t num_imm; uint32_t num_regs;  /* <= 64 */
 } lcp2_stark_desc;
-typedef struct { uint32_t kind /* 0 first, 1 transition, 2 last */, constraint; uint64_t row; } lcp2_stark_violation;
+typedef struct { uint32_t kind /* 0 first, 1 transition, 2 last, 3 permutation (lcp2_stark_prove_perm) */, constraint; uint64_t row; } lcp2_stark_violation;
 
 size_t lcp2_stark_proof_words(const lcp2_stark_desc *d);   /* 0 for a refused description */
 int lcp2_stark_prove(lcp2_ctx *ctx, const lcp2_stark_desc *d, const uint64_t *trace /* [width][n] values on H, natural order */,
@@ -923,6 +923,51 @@ int lcp2_stark_prove(lcp2_ctx *ctx, const lcp2_stark_desc *d, const uint64_t *tr
                      uint64_t *proof, size_t proof_words, lcp2_stark_violation *violation /* nullable */);
 int lcp2_stark_verify(const lcp2_stark_desc *d, const uint64_t *public_inputs, lcp2_challenger *ch,
                       const uint64_t *proof, size_t proof_words, int32_t *failed_check /* nullable */);
+
+/* ---- permutation arguments of an AIR (starky 0.1.2 Stark::permutation_pairs / permutation_batch_size, permutation.rs): the trace
+ * columns lhs_0 .. lhs_{k-1} of a pair, read as rows of k-tuples, are a permutation of the columns rhs_0 .. rhs_{k-1}.  PARITY
+ * UNPINNED like the calls above; pinned against eth_lc_plonky2_amd.stark.  With perm == NULL or num_pairs == 0 the three calls ARE
+ * the three calls above: same word count, same proof, same transcript.  Otherwise, with CH = num_challenges and Q = 2^q:
+ *   instances  the ordered list of (pair p, challenge c), p major: t = p CH + c.  Instance t belongs to Z number z = t / B at
+ *           position i = t mod B (B = batch_size); numZ = ceil(num_pairs CH / B), the last batch may be partial.
+ *   refusals   (LCP2_E_INVALID, lcp2_last_error says which, nothing is launched) num_pairs above 64; a pair with count == 0 or a
+ *           run [first, first + count) outside `columns`; num_column_pairs above 4096; a column >= width; batch_size outside
+ *           [1, Q] (the all-rows constraint below has degree B + 1, and (B + 1)(n - 1) - n < Q n iff B <= Q); numZ above 64;
+ *           everything lcp2_stark_prove refuses, and everything the opening layer refuses of the three-oracle instance.
+ *   transcript  public inputs and trace cap as above; then B challenge sets of CH pairs (beta, gamma) are drawn in the base field -
+ *           set 0 first, inside a set beta then gamma for c = 0 .. CH - 1 - and instance (z, i) with challenge c uses pair c of set
+ *           i; the Z columns are made and committed and their cap is observed; the CH alphas are drawn; the quotient cap is
+ *           observed, zeta drawn, and lcp2_fri_prove_openings takes over.
+ *   Z columns  for an instance over the column pairs (l_0, r_0) .. (l_{k-1}, r_{k-1}): lhs(r) = gamma + sum_j beta^j T[l_j][r], rhs(r)
+ *           likewise over the r_j.  Z_z[0] = 1 and Z_z[r + 1] = Z_z[r] prod_i lhs_i(r) / rhs_i(r) over the instances of z; the inverse
+ *           of 0 is 0.
+ *   constraints  appended to the list after last_row, in the same Horner pass: for z = 0 .. numZ - 1 the first-row constraint
+ *           Z_z - 1 (filter L_first); then for each z the ALL-ROWS constraint Z_z(next) prod_i rhs_i(local) - Z_z(local) prod_i
+ *           lhs_i(local), whose filter is 1 (it holds on the wrap-around from row n - 1 to row 0 too).
+ *   oracles    0 the trace, 1 the numZ Z columns (committed from their values on H like the trace), 2 the quotient.  zeta opens all
+ *           columns of all three, g zeta all trace and all Z columns.  The proof: trace cap, Z cap, quotient cap, then the words of
+ *           lcp2_fri_openings_words for that instance (csrc/stark.hpp st_make_layout derives the offsets for both sides).
+ *   witness check  the AIR's own check runs first, as above.  After the challenges are drawn, Z_z[n - 1] ratio_z(n - 1) != 1 for
+ *           some z is LCP2_E_UNSAT with *violation = { kind 3, constraint = the smallest such z, row = n - 1 }; ch is untouched and
+ *           the context proves a good trace afterwards.  This check is probabilistic: columns that are NOT permutations of each
+ *           other pass it for a fraction of about k n / p of the challenges only - negligible, but not zero - and such a proof is
+ *           then a sound proof of a false statement only with that same probability over the verifier's view of the transcript.
+ *   verifier   check 8 covers the three caps, check 9 is the identity over the extended list; the order is that of
+ *           lcp2_stark_verify.
+ * Device work: the per-row ratios (one field inversion shared by four rows of a lane), the running product (the exclusive scan of
+ * the Plonk permutation argument, one batch per Z), the closing check and a second instantiation of the quotient kernel; ratios,
+ * closing check and quotient are booked under LCP2_K_QUOTIENT, the scan under LCP2_K_PERM_Z, the commitment like the trace's. */
+typedef struct { uint32_t first, count; } lcp2_stark_perm_pair;  /* a run of column pairs in `columns` */
+typedef struct {
+  uint32_t num_pairs;  const lcp2_stark_perm_pair *pairs;
+  const uint32_t *columns; size_t num_column_pairs;  /* [num_column_pairs][2]: lhs column, rhs column of the trace */
+  uint32_t batch_size;                               /* B: instances multiplied into one Z */
+} lcp2_stark_perm;
+size_t lcp2_stark_perm_proof_words(const lcp2_stark_desc *d, const lcp2_stark_perm *perm);
+int lcp2_stark_prove_perm (lcp2_ctx*, const lcp2_stark_desc*, const lcp2_stark_perm*, const uint64_t *trace, lcp2_mem,
+                           const uint64_t *public_inputs, lcp2_challenger*, uint64_t *proof, size_t proof_words, lcp2_stark_violation*);
+int lcp2_stark_verify_perm(const lcp2_stark_desc*, const lcp2_stark_perm*, const uint64_t *public_inputs, lcp2_challenger*,
+                           const uint64_t *proof, size_t proof_words, int32_t *failed_check);
 
 /* ---- one proof sharded over the GPUs of a node by LDE coset (BASELINE configs[3]).
  * A sharded circuit holds the leaf blocks [block_first, block_first + block_count) of every LDE and Merkle tree
